@@ -1,21 +1,30 @@
 #!/usr/bin/env python
 """bench.py — Gbase hot-slice throughput on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 A "step" is one pass of the hot slice (reference model.py:1151-1171: S2C field -> 3D warp ->
 G3d -> C2D field -> 3D warp -> depth sum) over one batch of synthetic 512x512 frames, i.e.
 B x [96,16,64,64] appearance volumes already resident in HBM.  Frames are independent, so N GPUs
 run N independent shards (weak scaling, no data-path collective); rank 0 prints ONE JSON line.
 
-Extra objects on the line:
+A plain run sets up, warms up, times the K steps, writes the last step's outputs when
+--dump-outputs is given, and prints the line.  Extra objects on the line:
   roofline     — the dominant kernel (conv3d 3x3x3 96->96 @16x64x64, 60 % of hot-slice FLOPs):
                  algorithmic FLOPs per launch / its average launch duration, measured live with
-                 HIP events on the launch stream during the timed steps, vs the dense f16-MFMA peak,
-                 and `sustained_peak`: the same MFMA stream alone, >= 2 s back to back, with package
-                 power and clock (what the part sustains on this arithmetic at its power limit).
+                 HIP events on the launch stream during the timed steps, vs the dense f16-MFMA peak.
+With --full, also (each in runs of its own, after the timed steps):
+  repeats      — more blocks of the same K steps;
+  side legs    — one_in_flight, `roofline.sustained_peak` (the same MFMA stream alone, >= 2 s back to
+                 back, with package power and clock: what the part sustains on this arithmetic at its
+                 power limit), full_final_conv, roofline_hbm, fp32_exact, eapp_3d_tail, train_step(_autocast),
+                 reenact_1x64, end_to_end(_autocast_fp16), N=1 only;
   cpu_baseline — the CPU oracle (oracle/hotpath_ref.py, ATen CPU ops = what the reference runs on a
                  CPU host) timed on this host on a bounded sample, rank 0, N=1 only.
+
+--dump-outputs DIR: DIR/hot_slice.npy (float32 [B,96,64,64]) is what the last timed step returned
+(rank 0; --mode train: DIR/loss.npy).  Inputs and weights are seeded: the same arguments
+give the same inputs on every run, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -82,17 +91,37 @@ def parse():
                     help="launcher self-test (CPU, gloo): every rank joins the process group, rank 0 prints "
                          '{"stub_worker": true, "ranks": N}; no GPU work')
     ap.add_argument("--reenact-leg", action="store_true",
-                    help="also time BASELINE config 5's per-GPU shard in its serving configuration (channels_last + MIOpen find mode; "
-                         "the default line carries the immediate-mode leg `reenact_1x64`)")
-    ap.add_argument("--e2e-nhwc", action="store_true", help="also time the end-to-end generator with channels_last 2D modules + MIOpen find mode")
+                    help="with --full: also time BASELINE config 5's per-GPU shard in its serving configuration (channels_last + MIOpen "
+                         "find mode; the --full line carries the immediate-mode leg `reenact_1x64`)")
+    ap.add_argument("--e2e-nhwc", action="store_true",
+                    help="with --full: also time the end-to-end generator with channels_last 2D modules + MIOpen find mode")
     ap.add_argument("--extras-budget", type=float, default=100.0, help="seconds of side measurements after which remaining legs are skipped")
     ap.add_argument("--per-op", action="store_true", help="drive the step through the per-op Python schedule instead of the C-side plan")
     ap.add_argument("--full-final-conv", action="store_true",
                     help="evaluate G3d's last upsample + conv on every voxel (default: demand-driven, only what the final warp reads)")
-    ap.add_argument("--repeats", type=int, default=5, help="extra K-step blocks timed after the graded one (their ms/step: `repeats` on the line)")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="extra K-step blocks timed after the graded one (their ms/step: `repeats` on the line; default 5 with --full, else 0)")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the side measurements on the line (fp32_exact, roofline_hbm, end_to_end)")
-    return ap.parse_args()
+                    help="with --full: skip the side measurements on the line (fp32_exact, roofline_hbm, end_to_end)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: the repeat blocks, the side legs and the CPU baseline (a plain run does only the "
+                         "warm-up, the K timed steps and the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned to DIR/<name>.npy (rank 0; float32 stays float32, other dtypes become float64)")
+    args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = 5 if args.full else 0
+    return args
+
+
+def dump_outputs(directory, arrays):
+    """Writes {name: tensor} as directory/<name>.npy (float32 stays float32, anything else becomes float64)."""
+    import numpy as np
+
+    os.makedirs(directory, exist_ok=True)
+    for name, t in arrays.items():
+        a = t.detach().cpu()
+        np.save(os.path.join(directory, name + ".npy"), (a if a.dtype == torch.float32 else a.double()).numpy())
 
 
 def _free_port():
@@ -616,6 +645,8 @@ def train_mode(args, rank, world, dev, dist):
         t = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"loss": loss})
     if rank == 0:
         n_param = sum(p.numel() for p in hot.parameters())
         print(json.dumps({
@@ -762,6 +793,8 @@ def main():
 
         dt, out = timed_block(True)
         dom.active = False
+        if rank == 0 and args.dump_outputs:
+            dump_outputs(args.dump_outputs, {"hot_slice": out})
         prof = None
         if use_plan:   # (the roofline events come from the K graded steps only: read them before the repeat blocks)
             prof = (plan.profile_read(0), plan.profile_read(1))
@@ -859,7 +892,7 @@ def main():
                          "max": round(max(rep_ms), 3), "what": f"{len(rep_ms)} more blocks of the same {args.steps} steps (barrier + synchronize on "
                          "both sides each), after the graded block; the steps of every block rotate over 2 distinct input sets"} if rep_ms else None),
         }
-        if world == 1 and not args.no_extras:
+        if world == 1 and args.full and not args.no_extras:
             # side measurements (N=1 only, never inside the timed region): each leg is timed, and legs that would push the
             # default run past its budget are skipped and say so
             ops.set_conv_hook(None)
@@ -917,7 +950,7 @@ def main():
             line["leg_seconds"] = secs
         if world == 1 and args.torch_gpu_baseline:
             line["torch_rocm_baseline"] = torch_rocm_baseline(dev, B)
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(args.cpu_frames)
         print(json.dumps(line), flush=True)
     if dist is not None:

@@ -112,11 +112,33 @@ def make_backward():
     print("backward.npz", os.path.getsize(os.path.join(OUT, "backward.npz")))
 
 
+def make_reference_modules():
+    """(12) the reference's WarpGeneratorS2C, apply_warping_field and G3d on the small case of
+    tests/test_oracle.py::test_restatement_equals_reference_modules (B=1, 8^3 volume, input seed 5): the outputs (the field
+    stride-2 sampled, plus its per-channel sums) and their sha1, so that the test pins the restatement where the reference cannot
+    be imported."""
+    m = load_reference_model()
+    os.makedirs(OUT, exist_ok=True)
+    sd = R.seeded_gbase_hot_state_dict(WEIGHT_SEED)
+    s2c, g3d = _load(m.WarpGeneratorS2C(512), sd, "warp_generator_s2c."), _load(m.G3d(96), sd, "G3d.")
+    inp = R.seeded_hot_inputs(1, 5, D=8, H=8, W=8)
+    with torch.no_grad():
+        w = s2c(inp["Rs"], inp["ts"], inp["zs"], inp["es"])
+        vc = m.apply_warping_field(inp["vs"], w)
+        out = g3d(vc.clone())
+    path = os.path.join(OUT, "reference_modules.npz")
+    np.savez_compressed(path, s2c_s2=w[:, :, ::2, ::2, ::2].contiguous().numpy(), s2c_chan_sum=w.double().sum(dim=(2, 3, 4)).numpy(),
+                        warped=vc.numpy(), g3d=out.numpy(), s2c_sha1=_sha(w), warped_sha1=_sha(vc), g3d_sha1=_sha(out))
+    print("reference_modules.npz", os.path.getsize(path))
+
+
 def main():
     import sys
 
     if "--only-g2d-head" in sys.argv:
         return make_g2d_head()
+    if "--only-reference-modules" in sys.argv:
+        return make_reference_modules()
     if "--only-backward" in sys.argv:
         return make_backward()
     capture_tables()
@@ -224,6 +246,7 @@ def main():
         json.dump(manifest, f, indent=1, sort_keys=True)
     make_g2d_head()
     make_backward()
+    make_reference_modules()
     for fn in sorted(os.listdir(OUT)):
         print(fn, os.path.getsize(os.path.join(OUT, fn)))
 

@@ -1314,16 +1314,16 @@ def test_end_to_end_autocast_leg_has_a_floor():
 
 
 def test_bench_line_contract_on_one_gpu():
-    """`python bench.py --gpus 1 --steps K --warmup W` (the driver's call, with a small K): ONE JSON line with the contract's keys, the
-    default loop (two batches in flight, one plan per stream), the dominant kernel's roofline quoted from the one-stream leg of the same
-    run with the two-batch reading beside it, and the legs a one-second extras budget still admits."""
+    """`python bench.py --gpus 1 --steps K --warmup W --full` (the driver's call with --full, and a small K): ONE JSON line with the
+    contract's keys, the default loop (two batches in flight, one plan per stream), the dominant kernel's roofline quoted from the
+    one-stream leg of the same run with the two-batch reading beside it, and the legs a one-second extras budget still admits."""
     import json
     import subprocess
     import sys
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2", "--no-cpu-baseline",
-                        "--extras-budget", "1", "--repeats", "2"], capture_output=True, text=True, timeout=900)
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "4", "--warmup", "2", "--full",
+                        "--no-cpu-baseline", "--extras-budget", "1", "--repeats", "2"], capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1
@@ -1353,3 +1353,30 @@ def test_bench_line_contract_on_one_gpu():
     reps = line["repeats"]
     assert len(reps["ms_per_step"]) == 2 and reps["min"] <= reps["median"] <= reps["max"]
     assert "hot_slice_tflops" not in line and line["hot_slice_tflops_executed"] < line["hot_slice_tflops_reference_graph"]
+
+
+def test_bench_plain_run_is_lean_and_dumps_its_outputs(tmp_path):
+    """A plain `python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR`: the headline line and nothing that needs runs of its
+    own (no repeat blocks, side legs or CPU baseline: those are --full's), and DIR/hot_slice.npy = what the last of the K steps
+    returned — the same bits on a second run with the same arguments (seeded inputs and weights)."""
+    import subprocess
+    import sys
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    outs = []
+    for run in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                            "--dump-outputs", str(tmp_path / run)], capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1
+        line = json.loads(lines[0])
+        assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["unit"] == "frames/s"
+        assert abs(line["value"] - 8 * 3 / (line["ms_per_step"] * 3e-3)) / line["value"] < 1e-2
+        assert line["repeats"] is None and "roofline" in line
+        assert not {"one_in_flight", "cpu_baseline", "fp32_exact", "end_to_end", "leg_seconds"} & set(line)
+        assert sorted(os.listdir(tmp_path / run)) == ["hot_slice.npy"]
+        out = np.load(tmp_path / run / "hot_slice.npy")
+        assert out.dtype == np.float32 and out.shape == (8, 96, 64, 64) and np.isfinite(out).all()
+        outs.append(out)
+    assert np.array_equal(outs[0], outs[1])

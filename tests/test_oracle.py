@@ -1,6 +1,6 @@
 """CPU tests of the oracle itself (no GPU): the two restatements (ATen-functional hotpath_ref.py and
 plain-C hotpath_c.c) against each other, against the golden fixtures produced by the reference
-(tests/golden/, oracle/make_golden.py) and — in the build container only — against the imported
+(tests/golden/, oracle/make_golden.py) and — where the reference can be imported — against the live
 reference.  This is what "pins" the oracle."""
 import json
 import math
@@ -148,16 +148,29 @@ def test_c_blocks_vs_golden(oracle_c, sd):
     assert maxabs(oracle_c.flowfield(zsum, sd, "warp_generator_c2d.flowfield."), R.flowfield(zsum, sd, "warp_generator_c2d.flowfield.")) < 1e-4
 
 
-# ------------------------------------------------------------------ against the live reference (container only)
-@pytest.mark.skipif(not reference_available(), reason="/root/reference only exists in the build container")
+# ------------------------------------------------------------------ against the reference's modules
 def test_restatement_equals_reference_modules(sd):
+    """The restatement against what the reference's WarpGeneratorS2C, apply_warping_field and G3d computed for the same inputs:
+    stored outputs (tests/golden/reference_modules.npz, oracle/make_golden.py) everywhere, and bit for bit against the live
+    modules where the reference can be imported."""
+    inp = R.seeded_hot_inputs(1, 5, D=8, H=8, W=8)
+    g = gold("reference_modules")
+    with torch.no_grad():
+        w = R.warp_generator(inp["Rs"], inp["ts"], inp["zs"], inp["es"], sd, "warp_generator_s2c.", True)
+        vc = R.apply_warping_field(inp["vs"], w)
+        out = R.g3d(vc, sd)
+    assert maxabs(w[:, :, ::2, ::2, ::2], g["s2c_s2"]) < 1e-5
+    assert maxabs(w.double().sum(dim=(2, 3, 4)), g["s2c_chan_sum"]) < 1e-6 * np.abs(g["s2c_chan_sum"]).max()
+    assert maxabs(vc, g["warped"]) < 1e-4
+    assert maxabs(out, g["g3d"]) < 1e-5
+    if not reference_available():
+        return
     from oracle.import_reference import load_reference_model
 
     m = load_reference_model()
     s2c, g3d = m.WarpGeneratorS2C(512), m.G3d(96)
     s2c.load_state_dict({k[len("warp_generator_s2c."):]: v for k, v in sd.items() if k.startswith("warp_generator_s2c.")})
     g3d.load_state_dict({k[len("G3d."):]: v for k, v in sd.items() if k.startswith("G3d.")})
-    inp = R.seeded_hot_inputs(1, 5, D=8, H=8, W=8)
     with torch.no_grad():
         w = s2c(inp["Rs"], inp["ts"], inp["zs"], inp["es"])
         assert torch.equal(w, R.warp_generator(inp["Rs"], inp["ts"], inp["zs"], inp["es"], sd, "warp_generator_s2c.", True))

@@ -37,7 +37,7 @@ db=$(find $out/kt -name "*.db" | head -1)
 python tools/agg_summary.py $db 12 40 > $out/${R}_train_kernel_agg.txt
 rm -rf $out/kt
 # 2. the same line without the profiler, same box
-python bench.py --no-cpu-baseline --extras-budget 30 --steps 20 --warmup 5 2>/dev/null | tail -1 > $out/${R}_bench_line_same_box_as_trace.json
+python bench.py --full --no-cpu-baseline --extras-budget 30 --steps 20 --warmup 5 2>/dev/null | tail -1 > $out/${R}_bench_line_same_box_as_trace.json
 # 3. SQ / HBM counters of the dominant conv (the F(2,3) kernel; separate passes, MI355X_MICROARCH.md)
 bash tools/pmc_conv.sh $out/pmc_conv conv3d_k3_f16x3_wino_pp_kernel > $out/pmc_conv.log 2>&1
 cp $out/pmc_conv/conv_pmc.json $out/${R}_pmc_conv.json && stamp $out/${R}_pmc_conv.json conv3d_f16x3_wino_pp.hip mphip_wino_tile.h mphip_f16x3.h
