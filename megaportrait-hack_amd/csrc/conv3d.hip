@@ -810,7 +810,7 @@ static int conv3d_run(const float *x, const float *in_affine, int in_relu, const
         if (rc) return rc;
     }
     if (gn_stats && gn_in_epilogue)
-        rc = groupnorm_stats_from_tiles((const float *)gn_ws, bias, gn_stats, N, Co, S, gn_groups, gn_eps, (int)fp.grid.x / N, f16x3_tile_waves(fp), s, gn_table);
+        rc = groupnorm_stats_from_tiles((const float *)gn_ws, bias, y, gn_stats, N, Co, S, gn_groups, gn_eps, (int)fp.grid.x / N, f16x3_tile_waves(fp), s, gn_table);
     else if (gn_stats)
         rc = groupnorm_stats_launch(y, gn_stats, N, Co, S, gn_groups, gn_eps, gn_ws, s, gn_table);
     return rc;

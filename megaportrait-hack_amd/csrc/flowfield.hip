@@ -43,28 +43,32 @@ __device__ __forceinline__ void ff_finish(const FfParams &p, const float *__rest
                                           double *red /* [2 * NT / 64] */, float *mr /* [2] */) {
     constexpr int S = D * H * W, CNT = CPG * S;
     const int tid = threadIdx.x;
-    float s = 0.0f, ss = 0.0f;
+    // two passes over the values in LDS: the mean, then the sum of squared deviations from it (a one-pass E[x^2] - mean^2 cancels when
+    // the group's |mean| is large against its spread)
+    float s = 0.0f;
+    for (int e = tid; e < CNT; e += NT) s += vals[e];
+    const double ds = ff_wave_sum((double)s);
+    if ((tid & 63) == 0) red[(tid >> 6) * 2] = ds;
+    __syncthreads();
+    double a = 0.0;
+    for (int wv = 0; wv < NT / 64; ++wv) a += red[wv * 2];   // wave order: deterministic (every thread, same order)
+    const double mean_d = a / (double)CNT;
+    const float mf = (float)mean_d;
+    float ss = 0.0f;
     for (int e = tid; e < CNT; e += NT) {
-        const float v = vals[e];
-        s += v;
-        ss += v * v;
+        const float d = vals[e] - mf;
+        ss += d * d;
     }
-    const double ds = ff_wave_sum((double)s), dss = ff_wave_sum((double)ss);
-    if ((tid & 63) == 0) {
-        red[(tid >> 6) * 2] = ds;
-        red[(tid >> 6) * 2 + 1] = dss;
-    }
+    const double dss = ff_wave_sum((double)ss);
+    if ((tid & 63) == 0) red[(tid >> 6) * 2 + 1] = dss;
     __syncthreads();
     if (tid == 0) {
-        double a = 0.0, b = 0.0;
-        for (int wv = 0; wv < NT / 64; ++wv) {   // wave order: deterministic
-            a += red[wv * 2];
-            b += red[wv * 2 + 1];
-        }
-        const double mean = a / (double)CNT;
-        double var = b / (double)CNT - mean * mean;
+        double b = 0.0;
+        for (int wv = 0; wv < NT / 64; ++wv) b += red[wv * 2 + 1];
+        const double dm = mean_d - (double)mf;   // (the deviations were taken from the fp32 mean)
+        double var = b / (double)CNT - dm * dm;
         if (var < 0.0) var = 0.0;
-        mr[0] = (float)mean;
+        mr[0] = mf;
         mr[1] = (float)(1.0 / sqrt(var + (double)p.eps));
     }
     __syncthreads();

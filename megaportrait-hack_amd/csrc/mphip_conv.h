@@ -104,7 +104,8 @@ size_t groupnorm_ws_bytes(int N, int C, int S, int G);
 int groupnorm_stats_launch(const float *x, float *stats, int N, int C, int S, int G, float eps, void *workspace,
                            hipStream_t s, const GnTable *tbl = nullptr);
 // ... from the per-(tile, wave, channel) partial sums (of value - bias) an f16x3 conv launch left in part [C][N*tiles_per_frame][waves][2]
-int groupnorm_stats_from_tiles(const float *part, const float *bias, float *stats, int N, int C, int S, int G, float eps, int tiles_per_frame,
-                               int waves, hipStream_t s, const GnTable *tbl = nullptr);
+// y: the conv's stored output, re-read for a group whose epilogue moments are ill-conditioned (|mean| >> sigma)
+int groupnorm_stats_from_tiles(const float *part, const float *bias, const float *y, float *stats, int N, int C, int S, int G, float eps,
+                               int tiles_per_frame, int waves, hipStream_t s, const GnTable *tbl = nullptr);
 
 }  // namespace mphip

@@ -18,7 +18,39 @@ __device__ __forceinline__ double wave_sum(double v) {
     return v;
 }
 
-// Stage 1: per (sample,group) span [cnt floats, contiguous in NCDHW] -> per-chunk (sum, sumsq).
+// The statistics of every group are accumulated about a pivot K (an element of the group): sum and sum of squares of x - K, then
+// mean = K + s/n, var = q/n - (s/n)^2.  Without it, a group whose |mean| is large against its spread (a DC the weights put into a conv
+// output) loses the variance to the fp32 rounding of x*x: at |mean|/sigma = 300, rstd was off by 2e-4 to 3e-3.
+
+// fp32 per-thread (sum, sum of squares) of p[i] - k over [begin, end): 256 threads, float4 or scalar loads
+__device__ __forceinline__ void gn_span_moments(const float *__restrict__ p, size_t begin, size_t end, bool vec, float k, float &s, float &ss) {
+    if (vec) {
+#pragma unroll 8   // (independent loads: in flight together instead of one round trip per trip; the adds keep their order)
+        for (size_t i = begin + (size_t)threadIdx.x * 4; i < end; i += 1024) {
+            float4 v = *reinterpret_cast<const float4 *>(p + i);
+            v.x -= k; v.y -= k; v.z -= k; v.w -= k;
+            s += (v.x + v.y) + (v.z + v.w);
+            ss += (v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w);
+        }
+    } else {
+        for (size_t i = begin + threadIdx.x; i < end; i += 256) {
+            float v = p[i] - k;
+            s += v;
+            ss += v * v;
+        }
+    }
+}
+
+// (mean, var) of the pivoted sums a = sum(x - k), b = sum((x - k)^2) over cnt elements; biased variance
+__device__ __forceinline__ void gn_pivot_moments(double a, double b, double cnt, double k, double &mean, double &var) {
+    const double d = a / cnt;
+    mean = k + d;
+    var = b / cnt - d * d;
+    if (var < 0.0) var = 0.0;
+}
+
+// Stage 1: per (sample,group) span [cnt floats, contiguous in NCDHW] -> per-chunk (sum, sumsq) of x - K, K = the group's first element
+// (every chunk of a group uses the same pivot, so the partials still add up; gn_finalize_kernel adds it back).
 // fp32 per-thread partials over <=64 elements, wavefront-shuffle + LDS reduction in double.
 __global__ void __launch_bounds__(256)
 gn_partial_kernel(const float *__restrict__ x, double *__restrict__ partial, size_t cnt, int chunks) {
@@ -26,21 +58,9 @@ gn_partial_kernel(const float *__restrict__ x, double *__restrict__ partial, siz
     const float *p = x + (size_t)grp * cnt;
     const size_t begin = (size_t)chunk * GN_CHUNK;
     const size_t end = begin + GN_CHUNK < cnt ? begin + GN_CHUNK : cnt;
+    const float k = p[0];
     float s = 0.0f, ss = 0.0f;
-    if ((cnt & 3) == 0 && (((size_t)p) & 15) == 0) {
-#pragma unroll 8   // (independent loads: in flight together instead of one round trip per trip; the adds keep their order)
-        for (size_t i = begin + (size_t)threadIdx.x * 4; i < end; i += 1024) {
-            float4 v = *reinterpret_cast<const float4 *>(p + i);
-            s += (v.x + v.y) + (v.z + v.w);
-            ss += (v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w);
-        }
-    } else {
-        for (size_t i = begin + threadIdx.x; i < end; i += 256) {
-            float v = p[i];
-            s += v;
-            ss += v * v;
-        }
-    }
+    gn_span_moments(p, begin, end, (cnt & 3) == 0 && (((size_t)p) & 15) == 0, k, s, ss);
     double ds = wave_sum((double)s), dss = wave_sum((double)ss);
     __shared__ double red[8];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -79,30 +99,16 @@ __device__ __forceinline__ unsigned gn_table_entry(const GnTable &t, int n, int 
     return range_bits((t.sqrt_ng * fabsf(amp) + fabsf(off)) * 1.0001f);
 }
 
-__global__ void __launch_bounds__(256)
-gn_stats_direct_kernel(const float *__restrict__ x, float *__restrict__ stats, size_t cnt, float eps, GnTable tbl) {
-    const int grp = blockIdx.x;
-    const float *p = x + (size_t)grp * cnt;
-    double ds = 0.0, dss = 0.0;
+// (mean, var) of one contiguous span of cnt floats, walked by the whole 256-thread workgroup (every thread calls it: barriers inside; the
+// result is valid in thread 0).  Per-chunk fp32 partials like the 2-stage path, about the span's first element.
+__device__ __forceinline__ void gn_block_span_stats(const float *__restrict__ p, size_t cnt, double &mean, double &var) {
     const bool vec = (cnt & 3) == 0 && (((size_t)p) & 15) == 0;
-    // (the split-K aware variant is gn_stats_split_kernel below)
+    const float k = p[0];
+    double ds = 0.0, dss = 0.0;
     for (size_t begin = 0; begin < cnt; begin += GN_CHUNK) {   // same per-chunk fp32 partials as the 2-stage path
         const size_t end = begin + GN_CHUNK < cnt ? begin + GN_CHUNK : cnt;
         float s = 0.0f, ss = 0.0f;
-        if (vec) {
-#pragma unroll 8
-            for (size_t i = begin + (size_t)threadIdx.x * 4; i < end; i += 1024) {
-                float4 v = *reinterpret_cast<const float4 *>(p + i);
-                s += (v.x + v.y) + (v.z + v.w);
-                ss += (v.x * v.x + v.y * v.y) + (v.z * v.z + v.w * v.w);
-            }
-        } else {
-            for (size_t i = begin + threadIdx.x; i < end; i += 256) {
-                float v = p[i];
-                s += v;
-                ss += v * v;
-            }
-        }
+        gn_span_moments(p, begin, end, vec, k, s, ss);
         ds += (double)s;
         dss += (double)ss;
     }
@@ -115,13 +121,21 @@ gn_stats_direct_kernel(const float *__restrict__ x, float *__restrict__ stats, s
         red[wave * 2 + 1] = dss;
     }
     __syncthreads();
-    __shared__ float mr_[2];
     if (threadIdx.x == 0) {
         double a = (red[0] + red[2]) + (red[4] + red[6]);
         double b = (red[1] + red[3]) + (red[5] + red[7]);
-        double mean = a / (double)cnt;
-        double var = b / (double)cnt - mean * mean;
-        if (var < 0.0) var = 0.0;
+        gn_pivot_moments(a, b, (double)cnt, (double)k, mean, var);
+    }
+}
+
+__global__ void __launch_bounds__(256)
+gn_stats_direct_kernel(const float *__restrict__ x, float *__restrict__ stats, size_t cnt, float eps, GnTable tbl) {
+    const int grp = blockIdx.x;
+    // (the split-K aware variant is gn_stats_split_kernel below)
+    double mean, var;
+    gn_block_span_stats(x + (size_t)grp * cnt, cnt, mean, var);
+    __shared__ float mr_[2];
+    if (threadIdx.x == 0) {
         stats[grp * 2] = mr_[0] = (float)mean;
         stats[grp * 2 + 1] = mr_[1] = (float)(1.0 / sqrt(var + (double)eps));
     }
@@ -142,6 +156,8 @@ gn_stats_split_kernel(const float *__restrict__ x, int splits, size_t slab, cons
     const int grp = blockIdx.x;
     const size_t cnt = (size_t)cpg * S, base = (size_t)grp * cnt;
     const int c0 = (int)((base / S) % (size_t)C);
+    float k = sum_slabs(x, splits, slab, base);   // the pivot: the finished value of the group's first element (same bits in every thread)
+    if (bias) k += bias[c0];
     double ds = 0.0, dss = 0.0;
     {   // flat over the (channel, voxel) span so tiny S (FlowField's 4x1x1 level) still uses every lane
         float s = 0.0f, ss = 0.0f;
@@ -150,6 +166,7 @@ gn_stats_split_kernel(const float *__restrict__ x, int splits, size_t slab, cons
             const size_t o = base + e;
             float v = sum_slabs(x, splits, slab, o);
             if (bias) v += bias[c0 + (int)(e / S)];
+            v -= k;
             s += v;
             ss += v * v;
         }
@@ -171,16 +188,15 @@ gn_stats_split_kernel(const float *__restrict__ x, int splits, size_t slab, cons
             a += (red[w * 2] + red[w * 2 + 2]) + (red[w * 2 + 4] + red[w * 2 + 6]);
             b += (red[w * 2 + 1] + red[w * 2 + 3]) + (red[w * 2 + 5] + red[w * 2 + 7]);
         }
-        double mean = a / (double)cnt;
-        double var = b / (double)cnt - mean * mean;
-        if (var < 0.0) var = 0.0;
+        double mean, var;
+        gn_pivot_moments(a, b, (double)cnt, (double)k, mean, var);
         stats[grp * 2] = (float)mean;
         stats[grp * 2 + 1] = (float)(1.0 / sqrt(var + (double)eps));
     }
 }
 
 // Stage 2: (mean, rstd) per (sample,group); biased variance, eps inside the sqrt.
-__global__ void gn_finalize_kernel(const double *__restrict__ partial, float *__restrict__ stats, int ngroups,
+__global__ void gn_finalize_kernel(const float *__restrict__ x, const double *__restrict__ partial, float *__restrict__ stats, int ngroups,
                                    int chunks, double cnt, float eps, GnTable tbl) {
     int g = blockIdx.x * blockDim.x + threadIdx.x;
     unsigned mbits = 0;
@@ -190,9 +206,8 @@ __global__ void gn_finalize_kernel(const double *__restrict__ partial, float *__
             s += partial[((size_t)g * chunks + c) * 2];
             ss += partial[((size_t)g * chunks + c) * 2 + 1];
         }
-        double mean = s / cnt;
-        double var = ss / cnt - mean * mean;
-        if (var < 0.0) var = 0.0;
+        double mean, var;
+        gn_pivot_moments(s, ss, cnt, (double)x[(size_t)g * (size_t)cnt], mean, var);   // (gn_partial_kernel's pivot)
         const float mf = (float)mean, rf = (float)(1.0 / sqrt(var + (double)eps));
         stats[g * 2] = mf;
         stats[g * 2 + 1] = rf;
@@ -396,7 +411,9 @@ __global__ void __launch_bounds__(1024) gn_small_fused_kernel(GnSplitParams q, f
     const size_t base = (size_t)grp * cnt;
     const int c0 = (int)((base / S) % (size_t)p.C);
     const int shift = (S & (S - 1)) == 0 ? __ffs(S) - 1 : -1;  // S is a power of two on every hot-path layer
-    float s = 0.0f, ss = 0.0f;
+    // two passes over the values in LDS: the mean, then the sum of squared deviations from it (exact where a one-pass E[x^2] - mean^2
+    // cancels: a group whose |mean| is large against its spread)
+    float s = 0.0f;
 #pragma unroll 4
     for (int e = threadIdx.x; e < cnt; e += nthr) {
         const int c = shift >= 0 ? (e >> shift) : e / S;
@@ -404,25 +421,31 @@ __global__ void __launch_bounds__(1024) gn_small_fused_kernel(GnSplitParams q, f
         if (q.x_splits > 1 && q.x_bias) v += q.x_bias[c0 + c];
         vals[e] = v;
         s += v;
-        ss += v * v;
     }
-    double ds = wave_sum((double)s), dss = wave_sum((double)ss);
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    if (lane == 0) {
-        red[wave * 2] = ds;
-        red[wave * 2 + 1] = dss;
+    double ds = wave_sum((double)s);
+    if (lane == 0) red[wave] = ds;
+    __syncthreads();
+    double a = 0.0;
+    for (int wv = 0; wv < nwaves; ++wv) a += red[wv];   // (every thread, same order)
+    const double mean_d = a / (double)cnt;
+    const float mf = (float)mean_d;
+    float ss = 0.0f;
+#pragma unroll 4
+    for (int e = threadIdx.x; e < cnt; e += nthr) {
+        const float d = vals[e] - mf;
+        ss += d * d;
     }
+    const double dss = wave_sum((double)ss);
+    if (lane == 0) red[16 + wave] = dss;
     __syncthreads();
     if (threadIdx.x == 0) {
-        double a = 0.0, b = 0.0;
-        for (int wv = 0; wv < nwaves; ++wv) {
-            a += red[wv * 2];
-            b += red[wv * 2 + 1];
-        }
-        double mean = a / (double)cnt;
-        double var = b / (double)cnt - mean * mean;
+        double b = 0.0;
+        for (int wv = 0; wv < nwaves; ++wv) b += red[16 + wv];
+        const double dm = mean_d - (double)mf;   // (the deviations were taken from the fp32 mean)
+        double var = b / (double)cnt - dm * dm;
         if (var < 0.0) var = 0.0;
-        mr[0] = (float)mean;
+        mr[0] = mf;
         mr[1] = (float)(1.0 / sqrt(var + (double)eps));
         if (stats_out) {
             stats_out[grp * 2] = mr[0];
@@ -860,8 +883,8 @@ namespace mphip {
 // fp32; a frame's tiles are consecutive.  One workgroup per (sample, group) folds tiles x waves x channels-of-the-group in double and
 // writes (mean, rstd) (+ the affine table entries, as gn_stats_direct_kernel).
 __global__ void __launch_bounds__(256)
-gn_tile_finalize_kernel(const float *__restrict__ part, const float *__restrict__ bias, float *__restrict__ stats, int tiles_per_frame,
-                        int waves, int C, int cpg, double cnt, double vox_per_row, float eps, GnTable tbl) {
+gn_tile_finalize_kernel(const float *__restrict__ part, const float *__restrict__ bias, const float *__restrict__ y, float *__restrict__ stats,
+                        int tiles_per_frame, int waves, int C, int cpg, double cnt, double vox_per_row, float eps, GnTable tbl) {
     const int grp = blockIdx.x, groups = C / cpg, n = grp / groups, g = grp % groups;
     const int rows = tiles_per_frame * waves;   // (tile, wave) rows of this frame
     const size_t all_rows = (size_t)(gridDim.x / groups) * rows;
@@ -892,12 +915,22 @@ gn_tile_finalize_kernel(const float *__restrict__ part, const float *__restrict_
     }
     __syncthreads();
     __shared__ float mr_[2];
+    __shared__ int redo_;
+    double mean = 0.0, var = 0.0;
     if (threadIdx.x == 0) {
         double a = (red[0] + red[2]) + (red[4] + red[6]);
         double b = (red[1] + red[3]) + (red[5] + red[7]);
-        double mean = a / cnt;
-        double var = b / cnt - mean * mean;
+        mean = a / cnt;
+        var = b / cnt - mean * mean;
         if (var < 0.0) var = 0.0;
+        // var < mean^2 / 256 (|mean| / sigma > 16): the epilogue's fp32 sums of squares lose the variance to cancellation -> this group
+        // again from the stored output (complete: the statistics are only asked of full launches), about a pivot (gn_block_span_stats)
+        redo_ = var * 256.0 < mean * mean;
+    }
+    __syncthreads();
+    if (redo_)   // (workgroup-uniform)
+        gn_block_span_stats(y + (size_t)grp * (size_t)cnt, (size_t)cnt, mean, var);
+    if (threadIdx.x == 0) {
         stats[grp * 2] = mr_[0] = (float)mean;
         stats[grp * 2 + 1] = mr_[1] = (float)(1.0 / sqrt(var + (double)eps));
     }
@@ -931,7 +964,7 @@ int groupnorm_stats_launch(const float *x, float *stats, int N, int C, int S, in
         hipLaunchKernelGGL(gn_stats_direct_kernel, dim3(N * G), dim3(256), 0, s, x, stats, cnt, eps, t);
     } else {
         hipLaunchKernelGGL(gn_partial_kernel, dim3(chunks, N * G), dim3(256), 0, s, x, (double *)workspace, cnt, chunks);
-        hipLaunchKernelGGL(gn_finalize_kernel, dim3(cdiv(N * G, 256)), dim3(256), 0, s, (const double *)workspace, stats,
+        hipLaunchKernelGGL(gn_finalize_kernel, dim3(cdiv(N * G, 256)), dim3(256), 0, s, x, (const double *)workspace, stats,
                            N * G, chunks, (double)cnt, eps, t);
     }
     if (tbl && !t.table)   // (shape outside the fused form: the separate table launch)
@@ -940,8 +973,8 @@ int groupnorm_stats_launch(const float *x, float *stats, int N, int C, int S, in
     return check_launch("groupnorm_stats");
 }
 
-int groupnorm_stats_from_tiles(const float *part, const float *bias, float *stats, int N, int C, int S, int G, float eps, int tiles_per_frame,
-                               int waves, hipStream_t s, const GnTable *tbl) {
+int groupnorm_stats_from_tiles(const float *part, const float *bias, const float *y, float *stats, int N, int C, int S, int G, float eps,
+                               int tiles_per_frame, int waves, hipStream_t s, const GnTable *tbl) {
     GnTable t;
     if (tbl && (N * G <= (int)RANGE_MAX_PARTS) && C / G <= 256) {
         t = *tbl;
@@ -949,7 +982,7 @@ int groupnorm_stats_from_tiles(const float *part, const float *bias, float *stat
         t.cpg = C / G;
         t.sqrt_ng = sqrtf((float)(C / G) * (float)S);
     }
-    hipLaunchKernelGGL(gn_tile_finalize_kernel, dim3(N * G), dim3(256), 0, s, part, bias, stats, tiles_per_frame, waves, C, C / G,
+    hipLaunchKernelGGL(gn_tile_finalize_kernel, dim3(N * G), dim3(256), 0, s, part, bias, y, stats, tiles_per_frame, waves, C, C / G,
                        (double)(C / G) * (double)S, (double)S / ((double)tiles_per_frame * waves), eps, t);
     if (tbl && !t.table)
         hipLaunchKernelGGL(gn_affine_table_kernel, dim3(cdiv((long)N * C, 256)), dim3(256), 0, s, stats, tbl->gamma, tbl->beta, tbl->w2, tbl->b2,

@@ -1263,6 +1263,58 @@ def test_hot_slice_with_unnormalised_activations(dev, hot, sd, M, ops):
     assert ops.f16x3_saturation_count() == 0
 
 
+def test_hot_slice_invariant_to_a_groupnorm_offset(dev, hot, sd, M, monkeypatch):
+    """Metamorphic: one constant c added to the bias of every conv whose output goes straight into a GroupNorm / AdaptiveGroupNorm (G3d's
+    ResBlock3D conv1/conv2, the generators' ResBlock3D_Adaptive conv1/conv2, FlowField's output conv) leaves the reference's output
+    unchanged in exact arithmetic.  c puts those layers at |mean| / sigma ~ 100, where a one-pass fp32 E[x^2] - mean^2 loses the
+    variance.  HIP(shifted) must match the float64 oracle of the shifted slice and HIP(unshifted) to the fp32 oracle's own class."""
+    import re
+
+    keys = [k for k in sd if re.search(r"(G3d\.(down|up)sampling\.\d+\.conv[12]|flowfield\.resblock\d\.conv[12]|flowfield\.conv3x3x3)\.bias$", k)]
+    assert len(keys) == 32
+    inp = R.seeded_hot_inputs(2, INPUT_SEED)
+    record = {}
+
+    def run_oracle(sd_, dt):
+        targets = {id(sd_[k]): k for k in keys}
+        conv = R._conv3d
+
+        def spy(x, w, b=None, *a, **kw):
+            y = conv(x, w, b, *a, **kw)
+            if b is not None and id(b) in targets:
+                yr = y.detach().double().reshape(y.shape[0] * (1 if y.shape[1] == 3 else 32), -1)
+                record[targets[id(b)]] = (yr.mean(-1).abs() / yr.std(-1, unbiased=False)).median().item(), yr.std(-1, unbiased=False).median().item()
+            return y
+
+        monkeypatch.setattr(R, "_conv3d", spy)
+        try:
+            with torch.no_grad():
+                return R.hot_slice(sd=sd_, **{k: v.to(dt) for k, v in inp.items()})
+        finally:
+            monkeypatch.setattr(R, "_conv3d", conv)
+
+    base32 = run_oracle(sd, torch.float32)
+    c = 100.0 * max(sig for _, sig in record.values())
+    sd_s = dict(sd)
+    for k in keys:
+        sd_s[k] = sd[k] + c
+    cpu32 = run_oracle(sd_s, torch.float32).double()
+    truth = run_oracle({k: v.double() for k, v in sd_s.items()}, torch.float64)
+    print(f"offset c = {c:.3g}; |mean|/sigma per layer: " + ", ".join(f"{k.replace('.bias', '')} {r:.0f}" for k, (r, _) in sorted(record.items())))
+    shifted = M.GbaseHotSlice()
+    M.load_hot_state_dict(shifted, sd_s)
+    shifted = shifted.to(dev).eval()
+    with torch.no_grad():
+        got = shifted(**{k: v.to(dev) for k, v in inp.items()}).cpu().double()
+        plain = hot(**{k: v.to(dev) for k, v in inp.items()}).cpu().double()
+    e_hip, e_cpu, e_inv = (got - truth).abs().max().item(), (cpu32 - truth).abs().max().item(), (got - plain).abs().max().item()
+    print(f"shifted slice: HIP {e_hip:.3e}, fp32 CPU oracle {e_cpu:.3e} vs float64; HIP shifted vs unshifted {e_inv:.3e}; fp32 oracle shifted vs "
+          f"unshifted {(cpu32 - base32.double()).abs().max().item():.3e} (|out|max {truth.abs().max():.2f})")
+    assert min(r for r, _ in record.values()) > 30
+    assert e_hip <= max(3.0 * e_cpu, 1e-5)
+    assert e_inv <= max(3.0 * e_cpu, 1e-5)
+
+
 def test_c_abi_from_plain_c(c_abi_exe):
     """tests/c_abi/c_abi_smoke.c: a C99 program (gcc; HIP runtime for memory, no Python/torch) drives libmphip.so through
     include/mphip.h — conv + pool vs host references computed in the C file, and the error-code convention."""
