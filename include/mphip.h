@@ -39,7 +39,7 @@ extern "C" {
 
 /* ABI version of this header.  Bumped whenever an exported signature or a packed layout changes; mphip_version() returns the
  * value the LIBRARY was built with — compare the two after dlopen (the ctypes binding does, and refuses a mismatch). */
-#define MPHIP_ABI_VERSION 14
+#define MPHIP_ABI_VERSION 15
 int mphip_version(void);
 /* hipGraph hygiene (ABI 13).  On ROCm 7.x a MEMSET node of a captured hipGraph is not reliably ordered with its neighbouring kernel nodes
  * (observed twice: stale f16x3 pack headers, r03; a training step's loss that kept its previous value, r04-r05 — ATen's multi-block
@@ -486,6 +486,43 @@ size_t mphip_g3d_workspace_bytes(mphip_hot_slice_plan *plan, int B);
 int mphip_g3d_forward(mphip_hot_slice_plan *plan, const float *x, const float *x_range, float *y, int B, void *workspace,
                       size_t workspace_bytes, void *stream);
 void mphip_hot_slice_plan_destroy(mphip_hot_slice_plan *plan);
+
+/* ------------------------------------------------------------------ model dtypes (ABI 15)
+ * A hot module converted with .half() / .bfloat16() keeps fp32 activations between kernels; only its BOUNDARY tensors are typed.
+ * The entries below read or write them directly: a source volume is widened to fp32 on load (exact), an output is rounded ONCE at
+ * the store, round-to-nearest-even like torch's .to(dtype) (Inf stays Inf, NaN stays NaN; a bf16 NaN is written as 0x7FC0).
+ *   *_typed K2 entries: bitwise equal to the fp32 entry on the widened volume; coordinates, out (fp32) and out_range unchanged.
+ *   *_typed K3 entries: fp32 source, fp32 accumulation exactly as the fp32 entry, then `out` rounded to out_dtype.
+ *   mphip_cast_to_f32_range: y = x widened to fp32 (y may be NULL) and, in the same pass, the range descriptor of the widened values
+ *          (what mphip_absmax_range would write for y).  x 8-byte, y 16-byte aligned for the vector path (any alignment works).
+ *   mphip_cast_from_f32: y = x rounded to `dtype` (F16 / BF16; F32 copies).
+ *   mphip_hot_slice_forward_typed: mphip_hot_slice_forward with vs in vs_dtype and out in out_dtype (the small vectors stay fp32);
+ *          same workspace.  With both F32 it IS mphip_hot_slice_forward.
+ *   mphip_g3d_forward_typed: mphip_g3d_forward with x in x_dtype and y in y_dtype; workspace: mphip_g3d_workspace_bytes_typed.
+ *          A typed x is widened with its range descriptor into the workspace (x_range is then ignored); a typed y is the fp32
+ *          result rounded once.                                                                                                */
+#define MPHIP_DTYPE_F32 0
+#define MPHIP_DTYPE_F16 1
+#define MPHIP_DTYPE_BF16 2
+int mphip_warp_volume_typed(const void *v, int v_dtype, const float *field, const float *lin_d, const float *lin_h, const float *lin_w,
+                            float *out, float *coords_out, int32_t *idx_out, float *out_range, int B, int C, int D, int H, int W,
+                            int fD, int fH, int fW, void *workspace, size_t workspace_bytes, void *stream);
+int mphip_warp_corner_image_typed(const void *v, int v_dtype, void *img, size_t img_bytes, int B, int C, int D, int H, int W, void *stream);
+int mphip_warp_volume_coords_img_typed(const void *v, int v_dtype, const float *coords, float *out, float *out_range, int B, int C, int D,
+                                       int H, int W, void *workspace, size_t workspace_bytes, const void *img, void *stream);
+int mphip_warp_volume_dsum_typed(const float *v, int shared, const float *field, const float *lin_d, const float *lin_h,
+                                 const float *lin_w, void *out, int out_dtype, int B, int C, int D, int H, int W, int fD, int fH, int fW,
+                                 void *workspace, size_t workspace_bytes, void *stream);
+int mphip_warp_volume_dsum_coords_typed(const float *v, const float *coords, void *out, int out_dtype, int B, int C, int D, int H, int W,
+                                        int shared, void *stream);
+int mphip_cast_to_f32_range(const void *x, int dtype, size_t n, float *y, float *range, void *stream);
+int mphip_cast_from_f32(const float *x, void *y, int dtype, size_t n, void *stream);
+int mphip_hot_slice_forward_typed(mphip_hot_slice_plan *plan, const void *vs, int vs_dtype, const float *es, const float *Rs,
+                                  const float *ts, const float *zs, const float *Rd, const float *td, const float *zd, void *out,
+                                  int out_dtype, int B, void *workspace, size_t workspace_bytes, void *stream);
+size_t mphip_g3d_workspace_bytes_typed(mphip_hot_slice_plan *plan, int B, int x_dtype, int y_dtype);
+int mphip_g3d_forward_typed(mphip_hot_slice_plan *plan, const void *x, int x_dtype, const float *x_range, void *y, int y_dtype, int B,
+                            void *workspace, size_t workspace_bytes, void *stream);
 
 /* The reference's reduced-precision policy for the convs (train.py:145,188: the generator step runs under torch.cuda.amp.autocast(), its
  * conv3d calls take f16 operands with fp32 accumulation).  mphip_conv3d_set_half_products(1) makes the CALLING THREAD's subsequent precision-1

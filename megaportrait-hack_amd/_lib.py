@@ -38,6 +38,17 @@ SIGNATURES = {
     "mphip_warp_volume": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p, _sz, _p]),
     "mphip_warp_volume_dsum": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p, _sz, _p]),
     "mphip_warp_volume_dsum_shared": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _i, _p, _sz, _p]),
+    # model dtypes (ABI 15)
+    "mphip_warp_volume_typed": (_i, [_p, _i, _p, _p, _p, _p, _p, _p, _p, _p] + [_i] * 8 + [_p, _sz, _p]),
+    "mphip_warp_corner_image_typed": (_i, [_p, _i, _p, _sz] + [_i] * 5 + [_p]),
+    "mphip_warp_volume_coords_img_typed": (_i, [_p, _i, _p, _p, _p] + [_i] * 5 + [_p, _sz, _p, _p]),
+    "mphip_warp_volume_dsum_typed": (_i, [_p, _i, _p, _p, _p, _p, _p, _i] + [_i] * 8 + [_p, _sz, _p]),
+    "mphip_warp_volume_dsum_coords_typed": (_i, [_p, _p, _p, _i] + [_i] * 5 + [_i, _p]),
+    "mphip_cast_to_f32_range": (_i, [_p, _i, _sz, _p, _p, _p]),
+    "mphip_cast_from_f32": (_i, [_p, _p, _i, _sz, _p]),
+    "mphip_hot_slice_forward_typed": (_i, [_p, _p, _i] + [_p] * 7 + [_p, _i, _i, _p, _sz, _p]),
+    "mphip_g3d_workspace_bytes_typed": (_sz, [_p, _i, _i, _i]),
+    "mphip_g3d_forward_typed": (_i, [_p, _p, _i, _p, _p, _i, _i, _p, _sz, _p]),
     "mphip_conv3d_supported": (_i, [_i, _i, _i, _i, _i, _i, _i, _i]),
     "mphip_packed_weight_bytes": (_sz, [_i, _i, _i, _i]),
     "mphip_pack_conv_weight": (_i, [_p, _p, _i, _i, _i, _i, _p]),
@@ -134,7 +145,7 @@ _lib = None
 # The ABI version the SIGNATURES table above mirrors.  Checked against the library at load time, and against include/mphip.h by
 # tests/test_host.py — NOT read from the header at run time: a relocated / installed package ships libmphip.so without the repository's
 # include/ directory.
-EXPECTED_ABI_VERSION = 14
+EXPECTED_ABI_VERSION = 15
 
 
 def header_abi_version() -> int:

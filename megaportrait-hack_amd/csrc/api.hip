@@ -157,10 +157,89 @@ int absmax_range_launch(const float *x, size_t n, float *range, hipStream_t s) {
     hipLaunchKernelGGL(absmax_range_kernel, dim3(blocks ? blocks : 1), dim3(256), 0, s, x, n, range);
     return check_launch("absmax_range");
 }
+
+// Model dtypes: a half tensor that feeds an f16x3 conv stack is widened to fp32 and its range descriptor written in the same pass — the
+// cast plus absmax_range_kernel's read in one.  Same partial-maximum layout as absmax_range_kernel (the consumer folds the partials: the
+// maximum, and so the operand scale, does not depend on how the tensor was cut into workgroups).  VEC: four elements per step (x 8-byte,
+// y 16-byte aligned); y == nullptr: the range alone.
+template <int DT, bool VEC>
+__global__ void __launch_bounds__(256) cast_range_kernel(const dtype_t<DT> *__restrict__ x, size_t n, float *__restrict__ y,
+                                                         float *__restrict__ range) {
+    unsigned m = 0;
+    size_t done = 0;
+    if (VEC) {
+        struct alignas(8) four { dtype_t<DT> e[4]; };
+        const size_t n4 = n / 4;
+        for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) {
+            const four q = reinterpret_cast<const four *>(x)[i];
+            const float4 v = make_float4(widen(q.e[0]), widen(q.e[1]), widen(q.e[2]), widen(q.e[3]));
+            if (y) reinterpret_cast<float4 *>(y)[i] = v;
+            m = max(max(m, range_bits(v.x)), max(range_bits(v.y), max(range_bits(v.z), range_bits(v.w))));
+        }
+        done = n4 * 4;
+    }
+    const size_t stride = VEC ? 256 : (size_t)gridDim.x * 256;
+    for (size_t i = done + (VEC ? threadIdx.x : (size_t)blockIdx.x * 256 + threadIdx.x); i < n && (!VEC || blockIdx.x == 0); i += stride) {
+        const float v = widen(x[i]);
+        if (y) y[i] = v;
+        m = max(m, range_bits(v));
+    }
+    if (range) range_note_block(m, range, blockIdx.x, gridDim.x);
+}
+
+template <int DT>
+__global__ void __launch_bounds__(256) cast_from_f32_kernel(const float *__restrict__ x, dtype_t<DT> *__restrict__ y, size_t n) {
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) y[i] = narrow<DT>(x[i]);
+}
+
+template <int DT>
+static void launch_cast_range(const void *x, size_t n, float *y, float *range, hipStream_t s) {
+    const bool vec = ((uintptr_t)x & 7) == 0 && ((uintptr_t)y & 15) == 0;
+    const size_t per_block = 256 * 4 * 8;
+    const unsigned blocks = (unsigned)std::min<size_t>(2048, (n + per_block - 1) / per_block);
+    const auto *xt = (const dtype_t<DT> *)x;
+    if (vec) hipLaunchKernelGGL((cast_range_kernel<DT, true>), dim3(blocks ? blocks : 1), dim3(256), 0, s, xt, n, y, range);
+    else     hipLaunchKernelGGL((cast_range_kernel<DT, false>), dim3(blocks ? blocks : 1), dim3(256), 0, s, xt, n, y, range);
+}
+
+int cast_range_launch(const void *x, int dtype, size_t n, float *y, float *range, hipStream_t s) {
+    switch (dtype) {
+        case MPHIP_DTYPE_F32:
+            if (!y) return absmax_range_launch((const float *)x, n, range, s);
+            launch_cast_range<MPHIP_DTYPE_F32>(x, n, y, range, s);
+            break;
+        case MPHIP_DTYPE_F16: launch_cast_range<MPHIP_DTYPE_F16>(x, n, y, range, s); break;
+        case MPHIP_DTYPE_BF16: launch_cast_range<MPHIP_DTYPE_BF16>(x, n, y, range, s); break;
+        default: set_error("cast_to_f32_range: unknown dtype %d", dtype); return MPHIP_EINVAL;
+    }
+    return check_launch("cast_to_f32_range");
+}
+
+int cast_from_f32_launch(const float *x, void *y, int dtype, size_t n, hipStream_t s) {
+    const unsigned blocks = (unsigned)std::min<size_t>(8192, (n + 1023) / 1024);
+    switch (dtype) {
+        case MPHIP_DTYPE_F32: hipLaunchKernelGGL(cast_from_f32_kernel<MPHIP_DTYPE_F32>, dim3(blocks ? blocks : 1), dim3(256), 0, s, x, (float *)y, n); break;
+        case MPHIP_DTYPE_F16: hipLaunchKernelGGL(cast_from_f32_kernel<MPHIP_DTYPE_F16>, dim3(blocks ? blocks : 1), dim3(256), 0, s, x, (_Float16 *)y, n); break;
+        case MPHIP_DTYPE_BF16: hipLaunchKernelGGL(cast_from_f32_kernel<MPHIP_DTYPE_BF16>, dim3(blocks ? blocks : 1), dim3(256), 0, s, x, (bf16_bits *)y, n); break;
+        default: set_error("cast_from_f32: unknown dtype %d", dtype); return MPHIP_EINVAL;
+    }
+    return check_launch("cast_from_f32");
+}
 }  // namespace mphip
 
 extern "C" int mphip_absmax_range(const float *x, size_t n, float *range, void *stream) {
     MPHIP_REQUIRE(x && range && n > 0, "absmax_range: null pointer or empty tensor");
     MPHIP_REQUIRE(((uintptr_t)x & 15) == 0 && ((uintptr_t)range & 3) == 0, "absmax_range: x must be 16-byte aligned");
     return mphip::absmax_range_launch(x, n, range, (hipStream_t)stream);
+}
+
+extern "C" int mphip_cast_to_f32_range(const void *x, int dtype, size_t n, float *y, float *range, void *stream) {
+    MPHIP_REQUIRE(x && n > 0 && (y || range), "cast_to_f32_range: null pointer or empty tensor");
+    MPHIP_REQUIRE(((uintptr_t)range & 3) == 0, "cast_to_f32_range: range must be 4-byte aligned");
+    return mphip::cast_range_launch(x, dtype, n, y, range, (hipStream_t)stream);
+}
+
+extern "C" int mphip_cast_from_f32(const float *x, void *y, int dtype, size_t n, void *stream) {
+    MPHIP_REQUIRE(x && y && n > 0, "cast_from_f32: null pointer or empty tensor");
+    return mphip::cast_from_f32_launch(x, y, dtype, n, (hipStream_t)stream);
 }

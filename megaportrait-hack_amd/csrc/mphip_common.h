@@ -144,6 +144,34 @@ __device__ __forceinline__ void range_scale_block(const float *__restrict__ rang
 
 // max|x| of a tensor of unknown origin -> descriptor (one streaming pass, one launch).  Defined in api.hip.
 int absmax_range_launch(const float *x, size_t n, float *range, hipStream_t s);
+// (model dtypes, include/mphip.h) the range descriptor of a typed tensor, widened to fp32 on the fly; y != nullptr also stores the widened
+// values (one pass: mphip_cast_to_f32_range)
+int cast_range_launch(const void *x, int dtype, size_t n, float *y, float *range, hipStream_t s);
+int cast_from_f32_launch(const float *x, void *y, int dtype, size_t n, hipStream_t s);
+
+// ---- typed boundary tensors (MPHIP_DTYPE_*): widened to fp32 on load (exact), rounded once at the store like torch's .to(dtype)
+struct bf16_bits {
+    unsigned short u;
+};
+template <int DT> struct dtype_of;
+template <> struct dtype_of<MPHIP_DTYPE_F32> { using T = float; };
+template <> struct dtype_of<MPHIP_DTYPE_F16> { using T = _Float16; };
+template <> struct dtype_of<MPHIP_DTYPE_BF16> { using T = bf16_bits; };
+template <int DT> using dtype_t = typename dtype_of<DT>::T;
+
+__device__ __forceinline__ float widen(float v) { return v; }
+__device__ __forceinline__ float widen(_Float16 v) { return (float)v; }
+__device__ __forceinline__ float widen(bf16_bits v) { return __uint_as_float((unsigned)v.u << 16); }
+template <int DT> __device__ __forceinline__ dtype_t<DT> narrow(float v);
+template <> __device__ __forceinline__ float narrow<MPHIP_DTYPE_F32>(float v) { return v; }
+template <> __device__ __forceinline__ _Float16 narrow<MPHIP_DTYPE_F16>(float v) { return (_Float16)v; }   // v_cvt_f16_f32: RNE, Inf/NaN kept
+template <> __device__ __forceinline__ bf16_bits narrow<MPHIP_DTYPE_BF16>(float v) {
+    // c10::BFloat16's round_to_nearest_even: NaN -> 0x7FC0, else round the low 16 bits to even
+    const unsigned u = __float_as_uint(v);
+    bf16_bits r;
+    r.u = v != v ? (unsigned short)0x7FC0u : (unsigned short)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
+    return r;
+}
 
 // value of a split-K tensor element: slab[0][o] + slab[1][o] + ... (z ascending, the reduce kernel's order).
 // The loads of 8 slabs are issued together (independent addresses) and only the adds are sequential, so a

@@ -661,8 +661,10 @@ T5 g3d(Ctx &c, T5 &x, bool external_out, float *out, Hook hook, Tail tail) {
 }
 
 // _HotSliceRunner._run for <= 64 frames (model.py:1151-1171)
-int run_slice(Plan *p, const float *vs, const float *es, const float *Rs, const float *ts, const float *zs, const float *Rd, const float *td,
-              const float *zd, float *out, int B, void *workspace, size_t workspace_bytes, hipStream_t s, bool dry, size_t *need) {
+// vs_dt / out_dt (model dtypes, ABI 15): K2 reads a typed vs, K3 writes a typed projection; nothing else depends on them
+int run_slice(Plan *p, const void *vs, const float *es, const float *Rs, const float *ts, const float *zs, const float *Rd, const float *td,
+              const float *zd, void *out, int B, void *workspace, size_t workspace_bytes, hipStream_t s, bool dry, size_t *need,
+              int vs_dt = MPHIP_DTYPE_F32, int out_dt = MPHIP_DTYPE_F32) {
     const bool overlap = p->overlap && !dry;
     // the side stream's arena sits behind the main one: sizes from the dry pass
     size_t side_bytes = 0, main_bytes = 0;
@@ -706,7 +708,10 @@ int run_slice(Plan *p, const float *vs, const float *es, const float *Rs, const 
     // full tail the old order stands: critical path first, the C2D generator's ~25 launches behind G3d's first conv.
     // K2's corner image (warp.hip): vs is an input, so the copy runs here, beside the generators' latency-bound chains, not in front of K2
     Buf cimg = take(cm, mphip_warp_corner_image_bytes(B, p->C));
-    RUN(cm, mphip_warp_corner_image(vs, cimg.p, mphip_warp_corner_image_bytes(B, p->C), B, p->C, p->D, p->H, p->W, s));
+    if (vs_dt == MPHIP_DTYPE_F32)
+        RUN(cm, mphip_warp_corner_image((const float *)vs, cimg.p, mphip_warp_corner_image_bytes(B, p->C), B, p->C, p->D, p->H, p->W, s));
+    else
+        RUN(cm, mphip_warp_corner_image_typed(vs, vs_dt, cimg.p, mphip_warp_corner_image_bytes(B, p->C), B, p->C, p->D, p->H, p->W, s));
     Buf coords, box, c_s2c;
     bool c2d_issued = false;
     auto finish_c2d = [&] {   // the per-frame box of voxels K3 will read (demand-driven final_conv)
@@ -752,7 +757,10 @@ int run_slice(Plan *p, const float *vs, const float *es, const float *Rs, const 
     {
         const size_t wsb = mphip_warp_workspace_bytes(B, p->D, p->H, p->W);   // (covers the per-tile marks of the gather passes)
         Buf ws = take(cm, wsb);
-        RUN(cm, mphip_warp_volume_coords_img(vs, c_s2c.p, vc.data.p, vc.range.p, B, p->C, p->D, p->H, p->W, ws.p, wsb, cimg.p, s));
+        if (vs_dt == MPHIP_DTYPE_F32)
+            RUN(cm, mphip_warp_volume_coords_img((const float *)vs, c_s2c.p, vc.data.p, vc.range.p, B, p->C, p->D, p->H, p->W, ws.p, wsb, cimg.p, s));
+        else
+            RUN(cm, mphip_warp_volume_coords_img_typed(vs, vs_dt, c_s2c.p, vc.data.p, vc.range.p, B, p->C, p->D, p->H, p->W, ws.p, wsb, cimg.p, s));
         give(cm, ws);
     }
     give(cm, c_s2c);
@@ -772,7 +780,10 @@ int run_slice(Plan *p, const float *vs, const float *es, const float *Rs, const 
     if (cs.rc != MPHIP_OK && cm.rc == MPHIP_OK) cm.rc = cs.rc;
     if (join_rc != MPHIP_OK) return join_rc;
     // apply_warping_field + torch.sum(dim=2) (model.py:1167-1171) in one kernel (K3), on the coordinates computed above
-    RUN(cm, mphip_warp_volume_dsum_coords(vc2d.data.p, coords.p, out, B, p->C, p->D, p->H, p->W, 0, s));
+    if (out_dt == MPHIP_DTYPE_F32)
+        RUN(cm, mphip_warp_volume_dsum_coords(vc2d.data.p, coords.p, (float *)out, B, p->C, p->D, p->H, p->W, 0, s));
+    else
+        RUN(cm, mphip_warp_volume_dsum_coords_typed(vc2d.data.p, coords.p, out, out_dt, B, p->C, p->D, p->H, p->W, 0, s));
     give(cs, coords);
     give(cs, box);
     give(cm, vc2d);
@@ -780,10 +791,12 @@ int run_slice(Plan *p, const float *vs, const float *es, const float *Rs, const 
     return cm.rc;
 }
 
-int run_g3d(Plan *p, const float *x, const float *x_range, bool have_range, float *y, int B, void *workspace, size_t workspace_bytes, hipStream_t s,
-            bool dry) {
+// x_dt / y_dt (model dtypes, ABI 15): a typed x is widened with its range descriptor into the arena (one pass); a typed y is the fp32 result
+// rounded once (one pass)
+int run_g3d(Plan *p, const void *x, const float *x_range, bool have_range, void *y, int B, void *workspace, size_t workspace_bytes, hipStream_t s,
+            bool dry, int x_dt = MPHIP_DTYPE_F32, int y_dt = MPHIP_DTYPE_F32) {
     if (!dry) {
-        run_g3d(p, nullptr, nullptr, have_range, nullptr, B, nullptr, 0, nullptr, true);
+        run_g3d(p, nullptr, nullptr, have_range, nullptr, B, nullptr, 0, nullptr, true, x_dt, y_dt);
         if (workspace_bytes < p->main_arena.peak || !workspace) {
             set_error("g3d_forward: workspace %zu bytes < required %zu", workspace_bytes, p->main_arena.peak);
             return MPHIP_EWORKSPACE;
@@ -793,13 +806,22 @@ int run_g3d(Plan *p, const float *x, const float *x_range, bool have_range, floa
     p->main_arena.reset(workspace, cap, dry);
     Ctx cm{p, &p->main_arena, s, dry};
     T5 xt;
-    xt.n = B; xt.c = p->C; xt.d = p->D; xt.h = p->H; xt.w = p->W;
-    xt.data.p = const_cast<float *>(x);
-    xt.range.p = const_cast<float *>(x_range);
-    xt.has_range = have_range;   // else range_for() measures x (one extra pass) into an arena descriptor
-    // the caller's tensors are not arena blocks: give() ignores them (off == SIZE_MAX)
-    T5 out = g3d(cm, xt, true, y, [] {}, [] { return Roi(); });
-    (void)out;
+    if (x_dt == MPHIP_DTYPE_F32) {
+        xt.n = B; xt.c = p->C; xt.d = p->D; xt.h = p->H; xt.w = p->W;
+        xt.data.p = const_cast<float *>((const float *)x);
+        xt.range.p = const_cast<float *>(x_range);
+        xt.has_range = have_range;   // else range_for() measures x (one extra pass) into an arena descriptor
+        // the caller's tensors are not arena blocks: give() ignores them (off == SIZE_MAX)
+    } else {
+        xt = new_t5(cm, B, p->C, p->D, p->H, p->W, true);
+        RUN(cm, mphip_cast_to_f32_range(x, x_dt, xt.numel(), xt.data.p, xt.range.p, s));
+    }
+    T5 out = g3d(cm, xt, y_dt == MPHIP_DTYPE_F32, (float *)y, [] {}, [] { return Roi(); });
+    if (y_dt != MPHIP_DTYPE_F32) {
+        RUN(cm, mphip_cast_from_f32(out.data.p, y, y_dt, out.numel(), s));
+        give(cm, out);
+    }
+    give(cm, xt);
     return cm.rc;
 }
 
@@ -1037,24 +1059,40 @@ extern "C" size_t mphip_hot_slice_workspace_bytes(mphip_hot_slice_plan *p, int B
     return need;
 }
 
-extern "C" int mphip_hot_slice_forward(mphip_hot_slice_plan *p, const float *vs, const float *es, const float *Rs, const float *ts,
-                                       const float *zs, const float *Rd, const float *td, const float *zd, float *out, int B, void *workspace,
-                                       size_t workspace_bytes, void *stream) {
+static int hot_slice_forward(mphip_hot_slice_plan *p, const void *vs, int vs_dt, const float *es, const float *Rs, const float *ts,
+                             const float *zs, const float *Rd, const float *td, const float *zd, void *out, int out_dt, int B, void *workspace,
+                             size_t workspace_bytes, void *stream) {
     MPHIP_REQUIRE(p && p->have_generators, "hot_slice_forward: null plan (or a G3d-only plan)");
     MPHIP_REQUIRE(vs && es && Rs && ts && zs && Rd && td && zd && out, "hot_slice_forward: null pointer");
     MPHIP_REQUIRE(B > 0, "hot_slice_forward: B=%d", B);
+    MPHIP_REQUIRE(vs_dt >= MPHIP_DTYPE_F32 && vs_dt <= MPHIP_DTYPE_BF16 && out_dt >= MPHIP_DTYPE_F32 && out_dt <= MPHIP_DTYPE_BF16,
+                  "hot_slice_forward: unknown dtype (vs %d, out %d)", vs_dt, out_dt);
     MPHIP_REQUIRE(p->lin_d && p->lin_h && p->lin_w && p->aff_base,
                   "hot_slice_forward: no torch.linspace table for a %dx%dx%d volume is built in (16 and 64 are): call mphip_hot_slice_plan_set_tables",
                   p->D, p->H, p->W);
     const size_t vol = (size_t)p->C * p->D * p->H * p->W, plane = (size_t)p->C * p->H * p->W;
+    const size_t vs_elt = vs_dt == MPHIP_DTYPE_F32 ? 4 : 2, out_elt = out_dt == MPHIP_DTYPE_F32 ? 4 : 2;
     // (the conv kernels address their input through one 2 GiB buffer resource: larger batches run as consecutive passes)
     for (int b0 = 0; b0 < B; b0 += MPHIP_PLAN_MAX_FRAMES_PER_PASS) {
         const int nb = B - b0 < MPHIP_PLAN_MAX_FRAMES_PER_PASS ? B - b0 : MPHIP_PLAN_MAX_FRAMES_PER_PASS;
-        int rc = run_slice(p, vs + b0 * vol, es + (size_t)b0 * 512, Rs + b0 * 3, ts + b0 * 3, zs + (size_t)b0 * 512, Rd + b0 * 3, td + b0 * 3,
-                           zd + (size_t)b0 * 512, out + b0 * plane, nb, workspace, workspace_bytes, (hipStream_t)stream, false, nullptr);
+        int rc = run_slice(p, (const char *)vs + b0 * vol * vs_elt, es + (size_t)b0 * 512, Rs + b0 * 3, ts + b0 * 3, zs + (size_t)b0 * 512, Rd + b0 * 3,
+                           td + b0 * 3, zd + (size_t)b0 * 512, (char *)out + b0 * plane * out_elt, nb, workspace, workspace_bytes, (hipStream_t)stream,
+                           false, nullptr, vs_dt, out_dt);
         if (rc) return rc;
     }
     return MPHIP_OK;
+}
+
+extern "C" int mphip_hot_slice_forward(mphip_hot_slice_plan *p, const float *vs, const float *es, const float *Rs, const float *ts,
+                                       const float *zs, const float *Rd, const float *td, const float *zd, float *out, int B, void *workspace,
+                                       size_t workspace_bytes, void *stream) {
+    return hot_slice_forward(p, vs, MPHIP_DTYPE_F32, es, Rs, ts, zs, Rd, td, zd, out, MPHIP_DTYPE_F32, B, workspace, workspace_bytes, stream);
+}
+
+extern "C" int mphip_hot_slice_forward_typed(mphip_hot_slice_plan *p, const void *vs, int vs_dtype, const float *es, const float *Rs,
+                                             const float *ts, const float *zs, const float *Rd, const float *td, const float *zd, void *out,
+                                             int out_dtype, int B, void *workspace, size_t workspace_bytes, void *stream) {
+    return hot_slice_forward(p, vs, vs_dtype, es, Rs, ts, zs, Rd, td, zd, out, out_dtype, B, workspace, workspace_bytes, stream);
 }
 
 extern "C" size_t mphip_g3d_workspace_bytes(mphip_hot_slice_plan *p, int B) {
@@ -1068,6 +1106,22 @@ extern "C" int mphip_g3d_forward(mphip_hot_slice_plan *p, const float *x, const 
     MPHIP_REQUIRE(p && x && y, "g3d_forward: null pointer");
     MPHIP_REQUIRE(B > 0 && B <= MPHIP_PLAN_MAX_FRAMES_PER_PASS, "g3d_forward: 1 <= B <= %d frames per call, got %d", MPHIP_PLAN_MAX_FRAMES_PER_PASS, B);
     return run_g3d(p, x, x_range, x_range != nullptr, y, B, workspace, workspace_bytes, (hipStream_t)stream, false);
+}
+
+extern "C" size_t mphip_g3d_workspace_bytes_typed(mphip_hot_slice_plan *p, int B, int x_dtype, int y_dtype) {
+    if (!p || B <= 0 || x_dtype < MPHIP_DTYPE_F32 || x_dtype > MPHIP_DTYPE_BF16 || y_dtype < MPHIP_DTYPE_F32 || y_dtype > MPHIP_DTYPE_BF16) return 0;
+    run_g3d(p, nullptr, nullptr, false, nullptr, B, nullptr, 0, nullptr, true, x_dtype, y_dtype);
+    return p->main_arena.peak;
+}
+
+extern "C" int mphip_g3d_forward_typed(mphip_hot_slice_plan *p, const void *x, int x_dtype, const float *x_range, void *y, int y_dtype, int B,
+                                       void *workspace, size_t workspace_bytes, void *stream) {
+    MPHIP_REQUIRE(p && x && y, "g3d_forward_typed: null pointer");
+    MPHIP_REQUIRE(B > 0 && B <= MPHIP_PLAN_MAX_FRAMES_PER_PASS, "g3d_forward_typed: 1 <= B <= %d frames per call, got %d", MPHIP_PLAN_MAX_FRAMES_PER_PASS, B);
+    MPHIP_REQUIRE(x_dtype >= MPHIP_DTYPE_F32 && x_dtype <= MPHIP_DTYPE_BF16 && y_dtype >= MPHIP_DTYPE_F32 && y_dtype <= MPHIP_DTYPE_BF16,
+                  "g3d_forward_typed: unknown dtype (x %d, y %d)", x_dtype, y_dtype);
+    const bool have = x_dtype == MPHIP_DTYPE_F32 && x_range != nullptr;
+    return run_g3d(p, x, have ? x_range : nullptr, have, y, B, workspace, workspace_bytes, (hipStream_t)stream, false, x_dtype, y_dtype);
 }
 
 extern "C" void mphip_hot_slice_plan_destroy(mphip_hot_slice_plan *p) {

@@ -189,6 +189,25 @@ __device__ __forceinline__ float gather8_pairs(const float *__restrict__ vol, co
     return acc;
 }
 
+// Typed source volumes (model dtypes, include/mphip.h): the same 8 taps and accumulation order on values widened to fp32 on load —
+// bitwise gather8 on the fp32 volume.  The pair form's 8-byte load has no 2-byte counterpart worth having: both read the taps one by one.
+template <typename T>
+__device__ __forceinline__ float gather8(const T *__restrict__ vol, const Taps &t) {
+    const T *p = vol + t.base;
+    float acc = 0.0f;
+    acc += widen(p[0]) * t.w[0];
+    acc += widen(p[t.dx]) * t.w[1];
+    acc += widen(p[t.dy]) * t.w[2];
+    acc += widen(p[t.dy + t.dx]) * t.w[3];
+    acc += widen(p[t.dz]) * t.w[4];
+    acc += widen(p[t.dz + t.dx]) * t.w[5];
+    acc += widen(p[t.dz + t.dy]) * t.w[6];
+    acc += widen(p[t.dz + t.dy + t.dx]) * t.w[7];
+    return acc;
+}
+template <typename T>
+__device__ __forceinline__ float gather8_pairs(const T *__restrict__ vol, const Taps &t) { return gather8(vol, t); }
+
 // ---- coordinate pass -------------------------------------------------------------------------
 // One thread per output voxel: coords[B,D,H,W,3] = clipped (x,y,z) sample coordinates (and the
 // floor indices for the tests).  12 B per voxel (0.79 MB per 512^2 frame, 3 % of K2's traffic);
@@ -475,6 +494,22 @@ warp_corner_image_kernel(const float *__restrict__ v, float *__restrict__ img, i
         img[((size_t)b * groups + g) * blk + (size_t)cell * cgp + cl] = real ? v[((size_t)b * C + ch) * vol + ((size_t)z * H + y) * W + x] : 0.0f;
     }
 }
+// model dtypes: the same image (fp32) from a typed volume, widened on load.  A typed K2 always has the image: warp_gather_typed_kernel
+// reads the corner from it and nowhere else.
+template <int DT>
+__global__ void __launch_bounds__(128)
+warp_corner_image_typed_kernel(const dtype_t<DT> *__restrict__ v, float *__restrict__ img, int C, int D, int H, int W, int cg, int groups) {
+    const int cell = blockIdx.x, b = blockIdx.y;
+    const int z = cell / (K2_CORNER_E * K2_CORNER_E), y = (cell / K2_CORNER_E) % K2_CORNER_E, x = cell % K2_CORNER_E;
+    const bool inside = z < D && y < H && x < W;
+    const size_t vol = (size_t)D * H * W, blk = k2_block_floats(cg);
+    const int cgp = k2_pitch(cg);
+    for (int c = threadIdx.x; c < groups * cgp; c += 128) {
+        const int g = c / cgp, cl = c - g * cgp, ch = g * cg + cl;
+        const bool real = inside && cl < cg && ch < C;
+        img[((size_t)b * groups + g) * blk + (size_t)cell * cgp + cl] = real ? widen(v[((size_t)b * C + ch) * vol + ((size_t)z * H + y) * W + x]) : 0.0f;
+    }
+}
 // one block of the corner image -> LDS, as LDS-DMA (16 bytes per lane, 1 KiB per wave and instruction, no registers); issued by hand:
 // the compiler would wait for each transfer before the next LDS access.  The caller waits (vmcnt(0)) before its barrier.
 __device__ __forceinline__ void k2_dma_image(const float *__restrict__ blk, float *lds, int floats) {
@@ -528,143 +563,31 @@ warp_gather_kernel(const float *__restrict__ v, const float *__restrict__ coords
                    float *__restrict__ out_range /* optional range descriptor of `out`: G3d's first conv reads it */,
                    int *__restrict__ todo, int B, int C, int D, int H, int W,
                    const float *__restrict__ img /* optional corner image (warp_corner_image_kernel, same cg) */, int cg /* channels per blockIdx.y */) {
-    __shared__ __attribute__((aligned(16))) float lds[K2_LDS_FLOATS];
-    __shared__ int red[(K2_THREADS / 64) * 6];
-    K2_STAMP(0)
-    const int HW = H * W;
-    const int tiles_w = (W + K2_TW - 1) / K2_TW, tiles_h = (H + K2_TH - 1) / K2_TH;
-    // XCD-aware order: consecutive logical ids (d fastest, then tile, then frame) run on the same XCD
-    const unsigned bid = xcd_remap(blockIdx.x, gridDim.x);
-    const int d = (int)(bid % (unsigned)D);
-    const int tile = (int)((bid / (unsigned)D) % (unsigned)(tiles_w * tiles_h));
-    const int b = (int)(bid / ((unsigned)D * (unsigned)(tiles_w * tiles_h)));
-    const int cg0 = (int)blockIdx.y * cg, Cg = min(C - cg0, cg), cgp = k2_pitch(cg);
-    const int h = (tile / tiles_w) * K2_TH + (int)(threadIdx.x / (K2_TW / 2));
-    const int w = (tile % tiles_w) * K2_TW + (int)(threadIdx.x % (K2_TW / 2)) * 2;
-    const bool active = h < H && w < W;  // W % 4 == 0 -> a thread's 2 positions share validity
-    const int p0 = h * W + w;
-    const size_t vol = (size_t)D * HW;
+#define K2_MAYBE(cond) cond
+#include "warp_k2_corner_body.h"
+#undef K2_MAYBE
+}
 
-    Taps taps[2];
-    int x0[2], y0[2], z0[2];
-    int lx = INT_MAX, ly = INT_MAX, lz = INT_MAX, hx = 0, hy = 0, hz = 0;
-    float cf[6] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
-    if (active) {   // (issued BEFORE the scalar test below is waited for: one round trip for both)
-        const float *cp = coords + (((size_t)b * D + d) * HW + p0) * 3;   // (p0 even: 8-byte aligned)
-#pragma unroll
-        for (int q = 0; q < 3; ++q) {
-            const float2 t2 = *reinterpret_cast<const float2 *>(cp + q * 2);
-            cf[q * 2] = t2.x; cf[q * 2 + 1] = t2.y;
-        }
-    }
-    // The image is fetched only if the tile's FIRST sample lies in the corner (one scalar load): a field that travels through the volume
-    // (not the reference's) would otherwise pay for the transfers for nothing.
-    const float *c0p = coords + (((size_t)b * D + d) * HW + (size_t)(tile / tiles_w) * K2_TH * W + (tile % tiles_w) * K2_TW) * 3;
-    const float fx = c0p[0], fy = c0p[1], fz = c0p[2];
-    const bool maybe = fx >= 0.0f && fx < (float)(K2_CORNER_E - 1) && fy >= 0.0f && fy < (float)(K2_CORNER_E - 1) && fz >= 0.0f && fz < (float)(K2_CORNER_E - 1);
-    const bool dma = maybe && img != nullptr;
-#ifndef MPHIP_K2_ABL_NOSTAGE   /* dev ablations (timing only, wrong results): tools/k2_ablate.sh */
-    if (dma) k2_dma_image(img + ((size_t)b * gridDim.y + blockIdx.y) * k2_block_floats(cg), lds, (int)k2_block_floats(cg));
-#endif
-    if (active) {
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            Coord3 c{cf[i * 3], cf[i * 3 + 1], cf[i * 3 + 2]};
-            taps[i] = make_taps(c, D, H, W);
-            x0[i] = (int)floorf(c.x); y0[i] = (int)floorf(c.y); z0[i] = (int)floorf(c.z);
-            lx = min(lx, x0[i]); ly = min(ly, y0[i]); lz = min(lz, z0[i]);
-            hx = max(hx, x0[i]); hy = max(hy, y0[i]); hz = max(hz, z0[i]);
-        }
-    }
-    const Box bx = block_box_n<K2_THREADS / 64>(lx, ly, lz, hx, hy, hz, D, H, W, red);
-    K2_STAMP(1)
-    // block-uniform: every sample of the tile (all eight corners of each) inside the corner the image holds
-    const bool in_corner = bx.ox + bx.ex <= K2_CORNER_E && bx.oy + bx.ey <= K2_CORNER_E && bx.oz + bx.ez <= K2_CORNER_E;
-    // 0: done here; 1: a box of moderate size = a smooth field that travels -> warp_gather_columns_body (plane reuse down the
-    // slices); 2: no locality to exploit (a box like the whole volume) -> warp_gather_direct_body (most loads in flight)
-    if (threadIdx.x == 0 && blockIdx.y == 0) todo[bid] = in_corner ? 0 : (bx.ex * bx.ey * bx.ez <= K2_COLUMNS_MAX_BOX ? 1 : 2);
-    unsigned mbits = 0;
-    if (dma) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's pieces of the image have landed
-    if (in_corner) {
-        float *ob = out + (size_t)b * C * vol + (size_t)d * HW + p0;
-#ifndef MPHIP_K2_ABL_NOSTAGE
-        if (!dma) k2_stage_corner(v + (size_t)b * C * vol, lds, cg0, Cg, cgp, D, H, W);
-#endif
-        __syncthreads();
-        K2_STAMP(2)
-        if (active) {
-            int tb[2][8];   // tap addresses in the image (floats, premultiplied by the pitch)
-            const Box cbx{0, 0, 0, K2_CORNER_E, K2_CORNER_E, K2_CORNER_E};
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                const TapOff o = rebase(taps[i], x0[i], y0[i], z0[i], cbx, cgp);
-                tb[i][0] = o.base; tb[i][1] = o.base + o.dx; tb[i][2] = o.base + o.dy; tb[i][3] = o.base + o.dy + o.dx;
-                tb[i][4] = o.base + o.dz; tb[i][5] = o.base + o.dz + o.dx; tb[i][6] = o.base + o.dz + o.dy;
-                tb[i][7] = o.base + o.dz + o.dy + o.dx;
-            }
-            k2_f2 wp[2][4];   // the taps' weights in pairs
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int j = 0; j < 4; ++j) wp[i][j] = k2_f2{taps[i].w[2 * j], taps[i].w[2 * j + 1]};
-            auto two_channels = [&](const float *src, int c) {
-                k2_f2 pv[2][8];
-#pragma unroll
-                for (int i = 0; i < 2; ++i)
-#pragma unroll
-                    for (int k = 0; k < 8; ++k) pv[i][k] = *reinterpret_cast<const k2_f2 *>(src + tb[i][k]);   // (even pitch, even channel: 8-byte aligned)
-                k2_f2 acc[2];
-#pragma unroll
-                for (int i = 0; i < 2; ++i) {
-                    acc[i] = k2_f2{0.0f, 0.0f};
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        acc[i] = k2_pk_add(acc[i], k2_pk_mul<0>(pv[i][2 * j], wp[i][j]));
-                        acc[i] = k2_pk_add(acc[i], k2_pk_mul<1>(pv[i][2 * j + 1], wp[i][j]));
-                    }
-                }
-#ifdef MPHIP_K2_ABL_NOSTORE
-                if (acc[0][0] == 1.2345e30f)
-#endif
-                {
-                    *reinterpret_cast<float2 *>(ob + (size_t)(cg0 + c) * vol) = make_float2(acc[0][0], acc[1][0]);
-                    *reinterpret_cast<float2 *>(ob + (size_t)(cg0 + c + 1) * vol) = make_float2(acc[0][1], acc[1][1]);
-                }
-                mbits = max(max(mbits, range_bits(acc[0][0])), max(range_bits(acc[0][1]), max(range_bits(acc[1][0]), range_bits(acc[1][1]))));
-                __builtin_amdgcn_sched_barrier(0);   // one channel pair at a time (hoisting the next pairs' reads spills)
-            };
-            int c = 0;
-#ifndef MPHIP_K2_ABL_NOLOOP
-            for (; c + 8 <= Cg; c += 8) {   // (eight channels per trip: their offsets are immediates of the tap reads)
-                const float *src = lds + c;
-#pragma unroll
-                for (int u = 0; u < 8; u += 2) two_channels(src + u, c + u);
-            }
-            for (; c + 2 <= Cg; c += 2) two_channels(lds + c, c);
-            if (c < Cg) {   // odd tail
-                float r[2];
-#pragma unroll
-                for (int i = 0; i < 2; ++i) {
-                    r[i] = 0.0f;
-#pragma unroll
-                    for (int k = 0; k < 8; ++k) r[i] += lds[c + tb[i][k]] * taps[i].w[k];
-                }
-                *reinterpret_cast<float2 *>(ob + (size_t)(cg0 + c) * vol) = make_float2(r[0], r[1]);
-                mbits = max(mbits, max(range_bits(r[0]), range_bits(r[1])));
-            }
-#endif
-        }
-    }
-    // (slot = group * tiles + tile: the follow-up kernels fold into group 0's slots)
-    if (out_range) range_note_block(mbits, out_range, blockIdx.y * gridDim.x + blockIdx.x, gridDim.x * gridDim.y);
-    K2_STAMP(3)
+// Model dtypes: the same corner gather for a typed source volume.  It never reads the volume: the fp32 image of the corner (built from
+// the typed volume by warp_corner_image_typed_kernel) is required and brought in for EVERY tile, so a tile whose clamped box lies in the
+// corner although its first sample does not (an axis of 6 voxels whose samples clip to its far border) finds its data in LDS too.
+template <int DT>
+__global__ void __launch_bounds__(K2_THREADS)
+warp_gather_typed_kernel(const float *__restrict__ coords, float *__restrict__ out, float *__restrict__ out_range, int *__restrict__ todo,
+                         int B, int C, int D, int H, int W, const float *__restrict__ img, int cg) {
+    if (img == nullptr) return;   // (the host refuses a typed K2 without the image)
+    const float *v = nullptr;     // (never read: with the image, `dma` below always holds)
+#define K2_MAYBE(cond) ((cond) || true)
+#include "warp_k2_corner_body.h"
+#undef K2_MAYBE
 }
 
 // The tiles warp_gather_kernel marked: one position per lane, lanes running along w, so for a smooth field every tap load of
 // a wave covers one or two contiguous row segments (the per-CU L1 serves the overlap between taps and rows) and the stores
 // are contiguous 128-byte rows; the x-neighbour taps come in pairs (gather8_pairs).  Workgroups of unmarked tiles exit.
+template <typename TV>
 __device__ __forceinline__ void
-warp_gather_direct_body(const float *__restrict__ v, const float *__restrict__ coords, float *__restrict__ out,
+warp_gather_direct_body(const TV *__restrict__ v, const float *__restrict__ coords, float *__restrict__ out,
                         float *__restrict__ out_range, const int *__restrict__ todo, int B, int C, int D, int H, int W,
                         unsigned blk_x, unsigned grid_x, unsigned blk_y, unsigned grid_y) {
     unsigned mbits = 0;
@@ -694,14 +617,14 @@ warp_gather_direct_body(const float *__restrict__ v, const float *__restrict__ c
                 t[i] = make_taps(Coord3{cq[0], cq[1], cq[2]}, D, H, W);
             }
         }
-        const float *vb = v + (size_t)b * C * vol;
+        const TV *vb = v + (size_t)b * C * vol;
         float *ob = out + (size_t)b * C * vol + (size_t)d * HW + hb * W + w;
         // channels are split over grid_y workgroups: this path is latency-bound (L2-hit gathers), it needs every wave slot
         const int cpg = (C + (int)grid_y - 1) / (int)grid_y;
         const int c_end = min(C, ((int)blk_y + 1) * cpg);
 #pragma unroll 2
         for (int c = (int)blk_y * cpg; c < c_end; ++c) {
-            const float *src = vb + (size_t)c * vol;
+            const TV *src = vb + (size_t)c * vol;
 #pragma unroll
             for (int i = 0; i < NP; ++i) {
                 if (act[i]) {
@@ -728,8 +651,9 @@ warp_gather_direct_body(const float *__restrict__ v, const float *__restrict__ c
 #define MPHIP_K2C_CPB 16
 #endif
 constexpr int K2C_CPB = MPHIP_K2C_CPB;
+template <typename TV>
 __device__ __forceinline__ void
-warp_gather_columns_body(const float *__restrict__ v, const float *__restrict__ coords, float *__restrict__ out,
+warp_gather_columns_body(const TV *__restrict__ v, const float *__restrict__ coords, float *__restrict__ out,
                          float *__restrict__ out_range, const int *__restrict__ todo, int B, int C, int D, int H, int W,
                          unsigned blk, unsigned nblk) {
     const int HW = H * W;
@@ -748,7 +672,7 @@ warp_gather_columns_body(const float *__restrict__ v, const float *__restrict__ 
     // the 16 x 16 tile lies inside one 32 x 32 tile of warp_gather_kernel: its marks, one per slice (block-uniform)
     const int t32 = ((tile / tiles_w) * 16 / K2_TH) * tiles32_w + (tile % tiles_w) * 16 / K2_TW;
     const int *marks = todo + ((size_t)b * ntile32 + t32) * D;
-    const float *vb = v + ((size_t)b * C + c0) * vol;
+    const TV *vb = v + ((size_t)b * C + c0) * vol;
     float *ob = out + ((size_t)b * C + c0) * vol + p;
     unsigned mbits = 0;
     // nothing marked for this column (every launch on the reference's own fields): leave after ONE round of loads
@@ -785,6 +709,18 @@ warp_gather_direct_kernel(const float *__restrict__ v, const float *__restrict__
                           float *__restrict__ out_range, const int *__restrict__ todo, int B, int C, int D, int H, int W) {
     warp_gather_direct_body(v, coords, out, out_range, todo, B, C, D, H, W, blockIdx.x, gridDim.x, blockIdx.y, gridDim.y);
 }
+template <int DT>
+__global__ void __launch_bounds__(256)
+warp_gather_columns_typed_kernel(const dtype_t<DT> *__restrict__ v, const float *__restrict__ coords, float *__restrict__ out,
+                                 float *__restrict__ out_range, const int *__restrict__ todo, int B, int C, int D, int H, int W) {
+    warp_gather_columns_body(v, coords, out, out_range, todo, B, C, D, H, W, blockIdx.x, gridDim.x);
+}
+template <int DT>
+__global__ void __launch_bounds__(256)
+warp_gather_direct_typed_kernel(const dtype_t<DT> *__restrict__ v, const float *__restrict__ coords, float *__restrict__ out,
+                                float *__restrict__ out_range, const int *__restrict__ todo, int B, int C, int D, int H, int W) {
+    warp_gather_direct_body(v, coords, out, out_range, todo, B, C, D, H, W, blockIdx.x, gridDim.x, blockIdx.y, gridDim.y);
+}
 
 // K3: a workgroup owns a compact 16 x 16 tile of (h,w) positions of one frame and CPB channels; every thread walks the D
 // output slices of its position accumulating the depth projection in registers (d ascending, like torch.sum(dim=2) on
@@ -799,88 +735,24 @@ template <int CPB>
 __global__ void __launch_bounds__(256)
 warp_gather_dsum_kernel(const float *__restrict__ v, const float *__restrict__ coords, float *__restrict__ out,
                         int B, int C, int D, int H, int W, size_t v_frame_stride /* floats; 0 = one shared source volume */) {
-    __shared__ __attribute__((aligned(16))) float lds[STAGE_FLOATS];
-    __shared__ int red[24];
-    const int HW = H * W;
-    const int tiles_w = (W + K3_TW - 1) / K3_TW, tiles_h = (H + K3_TH - 1) / K3_TH, ntile = tiles_w * tiles_h;
-    // XCD-aware order: the tiles of one (frame, channel slice) are consecutive logical ids, i.e. they run on ONE XCD at about the
-    // same time — w-neighbours share every 128-byte line of a source row, h-neighbours the halo rows, and with the hardware's
-    // round-robin (tile t -> XCD t % 8) each of those lines was fetched into up to four different L2s (travelling fields: 5x the
-    // algorithmic bytes crossed the fabric, at 6.9 TB/s — the kernel's limit)
-    unsigned bid = xcd_remap(blockIdx.x, gridDim.x);
-    const int tile = (int)(bid % ntile); bid /= ntile;
-    const int slices = (C + CPB - 1) / CPB;
-    const int slice = (int)(bid % slices), b = (int)(bid / slices);
-    static_assert(K3_TH * K3_TW == 256, "one thread per position of the tile");
-    const int h = (tile / tiles_w) * K3_TH + (int)(threadIdx.x / K3_TW);
-    const int w = (tile % tiles_w) * K3_TW + (int)(threadIdx.x % K3_TW);
-    const bool active = h < H && w < W;
-    const int p = h * W + w;
-    const size_t vol = (size_t)D * HW;
-    const int c0 = slice * CPB;
-    const int cs = min(CPB, C - c0);
-    const int cs_pad = lds_pitch_for(cs);
-    const float *cp = coords + ((size_t)b * D * HW + (active ? p : 0)) * 3;
-    const float *vb = v + (size_t)b * v_frame_stride;
-
-    float acc[CPB];
-#pragma unroll
-    for (int c = 0; c < CPB; ++c) acc[c] = 0.0f;
-
-    int lx = INT_MAX, ly = INT_MAX, lz = INT_MAX, hx = 0, hy = 0, hz = 0;
-    if (active) {
-        for (int d = 0; d < D; ++d) {
-            const float *q = cp + (size_t)d * HW * 3;
-            int x = (int)floorf(q[0]), y = (int)floorf(q[1]), z = (int)floorf(q[2]);
-            lx = min(lx, x); ly = min(ly, y); lz = min(lz, z);
-            hx = max(hx, x); hy = max(hy, y); hz = max(hz, z);
-        }
-    }
-    const Box all = block_box(lx, ly, lz, hx, hy, hz, D, H, W, red);
-    if (all.ex * all.ey * all.ez * cs_pad <= STAGE_FLOATS) {  // block-uniform: everything in one [voxel][channel] image
-        stage_box(vb, lds, all, c0, cs, cs_pad, H, W, vol);
-        __syncthreads();
-        if (active) {
-            for (int d = 0; d < D; ++d) {
-                const float *q = cp + (size_t)d * HW * 3;
-                Coord3 cc{q[0], q[1], q[2]};
-                Taps t = make_taps(cc, D, H, W);
-                const TapOff lt = rebase(t, (int)floorf(cc.x), (int)floorf(cc.y), (int)floorf(cc.z), all, cs_pad);
-#pragma unroll
-                for (int c = 0; c < CPB; c += 4) {
-                    if (c + 4 <= cs) {
-                        float tmp[4];
-                        gather8x4(lds + c, lt, t.w, tmp);
-#pragma unroll
-                        for (int k = 0; k < 4; ++k) acc[c + k] += tmp[k];
-                    } else {
-#pragma unroll
-                        for (int k = 0; k < 4; ++k)
-                            if (c + k < cs) acc[c + k] += gather8_lds(lds + c + k, lt, t.w);
-                    }
-                }
-            }
-        }
-    } else if (active) {
-        // a field that travels through the volume: gather from global memory; lanes run along w (coalesced row segments for
-        // a smooth field, the per-CU L1 serves the overlap between taps), x-neighbour taps in pairs
-        for (int d = 0; d < D; ++d) {
-            const float *q = cp + (size_t)d * HW * 3;
-            const Taps t = make_taps(Coord3{q[0], q[1], q[2]}, D, H, W);
-#pragma unroll
-            for (int c = 0; c < CPB; ++c)
-                if (c < cs) acc[c] += W >= 2 ? gather8_pairs(vb + (size_t)(c0 + c) * vol, t) : gather8(vb + (size_t)(c0 + c) * vol, t);
-        }
-    }
-    if (!active) return;
-#pragma unroll
-    for (int c = 0; c < CPB; ++c)
-        if (c < cs) out[((size_t)b * C + c0 + c) * HW + p] = acc[c];
+#define K3_STORE(x) x
+#include "warp_k3_body.h"
+#undef K3_STORE
+}
+// model dtypes: fp32 accumulation exactly as above, the projection rounded once at the store
+template <int CPB, int DTO>
+__global__ void __launch_bounds__(256)
+warp_gather_dsum_typed_kernel(const float *__restrict__ v, const float *__restrict__ coords, dtype_t<DTO> *__restrict__ out,
+                              int B, int C, int D, int H, int W, size_t v_frame_stride) {
+#define K3_STORE(x) narrow<DTO>(x)
+#include "warp_k3_body.h"
+#undef K3_STORE
 }
 
 // Fallback for W % 4 != 0 (never the case on the hot path): one thread per output voxel and channel slice.
-__global__ void __launch_bounds__(256)
-warp_gather_scalar_kernel(const float *__restrict__ v, const float *__restrict__ coords, float *__restrict__ out,
+template <typename TV>
+__device__ __forceinline__ void
+warp_gather_scalar_body(const TV *v, const float *coords, float *out,
                           int B, int C, int D, int H, int W, int cpb) {
     const size_t vol = (size_t)D * H * W;
     size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -892,6 +764,17 @@ warp_gather_scalar_kernel(const float *__restrict__ v, const float *__restrict__
     const int c_begin = blockIdx.y * cpb, c_end = min(C, c_begin + cpb);
     for (int ch = c_begin; ch < c_end; ++ch)
         out[((size_t)b * C + ch) * vol + r] = gather8(v + ((size_t)b * C + ch) * vol, taps);
+}
+__global__ void __launch_bounds__(256)
+warp_gather_scalar_kernel(const float *__restrict__ v, const float *__restrict__ coords, float *__restrict__ out,
+                          int B, int C, int D, int H, int W, int cpb) {
+    warp_gather_scalar_body(v, coords, out, B, C, D, H, W, cpb);
+}
+template <int DT>
+__global__ void __launch_bounds__(256)
+warp_gather_scalar_typed_kernel(const dtype_t<DT> *__restrict__ v, const float *__restrict__ coords, float *__restrict__ out,
+                                int B, int C, int D, int H, int W, int cpb) {
+    warp_gather_scalar_body(v, coords, out, B, C, D, H, W, cpb);
 }
 
 }  // namespace mphip
@@ -952,6 +835,8 @@ static int launch_coords(const float *field, const float *lin_d, const float *li
 
 static int warp_volume_gather(const float *v, const float *coords, float *out, float *out_range, int *todo, float *corner_img, bool img_ready,
                               int B, int C, int D, int H, int W, hipStream_t s);
+static int warp_volume_gather_dt(const void *v, int dtype, const float *coords, float *out, float *out_range, int *todo, float *corner_img,
+                                 bool img_ready, int B, int C, int D, int H, int W, hipStream_t s);
 
 extern "C" int mphip_warp_volume(const float *v, const float *field, const float *lin_d, const float *lin_h,
                                  const float *lin_w, float *out, float *coords_out, int32_t *idx_out, float *out_range, int B,
@@ -974,10 +859,38 @@ extern "C" int mphip_warp_volume(const float *v, const float *field, const float
     return warp_volume_gather(v, coords, out, out_range, todo, corner_img, false, B, C, D, H, W, s);
 }
 
-// the gather pass(es) of K2 on given coordinates; todo: one int per tile; corner_img: optional mphip_warp_corner_image_bytes(B, C) bytes
-static int warp_volume_gather(const float *v, const float *coords, float *out, float *out_range, int *todo, float *corner_img, bool img_ready,
-                              int B, int C, int D, int H, int W, hipStream_t s) {
+extern "C" int mphip_warp_volume_typed(const void *v, int v_dtype, const float *field, const float *lin_d, const float *lin_h, const float *lin_w,
+                                       float *out, float *coords_out, int32_t *idx_out, float *out_range, int B, int C, int D, int H, int W,
+                                       int fD, int fH, int fW, void *workspace, size_t workspace_bytes, void *stream) {
+    int rc = check_warp_args("warp_volume_typed", v, field, lin_d, lin_h, lin_w, out, B, C, D, H, W, fD, fH, fW);
+    if (rc) return rc;
+    MPHIP_REQUIRE(!idx_out || coords_out, "warp_volume_typed: idx_out requires coords_out");
+    const size_t need = mphip_warp_workspace_bytes(B, D, H, W), coord_bytes = (size_t)B * D * H * W * 3 * sizeof(float);
+    if (!workspace || workspace_bytes < need) {
+        set_error("warp_volume_typed: workspace %zu bytes < required %zu", workspace_bytes, need);
+        return MPHIP_EWORKSPACE;
+    }
+    float *coords = coords_out ? coords_out : (float *)workspace;
+    int *todo = (int *)((char *)workspace + coord_bytes);
+    float *corner_img = workspace_bytes >= need + mphip_warp_corner_image_bytes(B, C) ? (float *)((char *)workspace + need) : nullptr;
+    hipStream_t s = (hipStream_t)stream;
+    rc = launch_coords(field, lin_d, lin_h, lin_w, coords, idx_out, B, D, H, W, fD, fH, fW, s);
+    if (rc) return rc;
+    return warp_volume_gather_dt(v, v_dtype, coords, out, out_range, todo, corner_img, false, B, C, D, H, W, s);
+}
+
+// the gather pass(es) of K2 on given coordinates; todo: one int per tile; corner_img: optional mphip_warp_corner_image_bytes(B, C) bytes.
+// DT: the source volume's dtype (model dtypes); the fp32 instantiation launches the original kernels.
+template <int DT>
+static int warp_volume_gather_t(const void *v_, const float *coords, float *out, float *out_range, int *todo, float *corner_img, bool img_ready,
+                                int B, int C, int D, int H, int W, hipStream_t s) {
+    using TV = dtype_t<DT>;
+    const TV *v = (const TV *)v_;
     int rc;
+    if (DT != MPHIP_DTYPE_F32 && W % 4 == 0 && !corner_img) {
+        set_error("warp_volume (typed source): the workspace must include mphip_warp_corner_image_bytes(B, C) for the corner image");
+        return MPHIP_EWORKSPACE;
+    }
     const size_t nblocks = k2_tiles(B, D, H, W);
     // channel groups of the corner gather (its range slots: one per workgroup)
     const int cg = k2_group_channels(nblocks, C);
@@ -985,32 +898,87 @@ static int warp_volume_gather(const float *v, const float *coords, float *out, f
     if (out_range && (W % 4 != 0 || nblocks * groups > RANGE_MAX_PARTS)) {
         // (scalar fallback kernel / more workgroups than partial slots) the warp is a convex combination of v's voxels:
         // max|out| <= max|v|, so v's own range serves
-        rc = absmax_range_launch(v, (size_t)B * C * D * H * W, out_range, s);
+        rc = cast_range_launch(v, DT, (size_t)B * C * D * H * W, nullptr, out_range, s);
         if (rc) return rc;
         out_range = nullptr;
     }
     if (W % 4 == 0) {
         const unsigned ncol = (unsigned)((size_t)B * ((H + 15) / 16) * ((W + 15) / 16) * cdiv(C, K2C_CPB));
-        if (corner_img && !img_ready)
-            hipLaunchKernelGGL(warp_corner_image_kernel, dim3(K2_CORNER_CELLS, (unsigned)B), dim3(128), 0, s, v, corner_img, C, D, H, W, cg, (int)groups);
-        hipLaunchKernelGGL(warp_gather_kernel, dim3((unsigned)nblocks, groups), dim3(K2_THREADS), 0, s, v, coords, out, out_range, todo, B, C, D, H, W,
-                           (const float *)corner_img, cg);
-        // the tiles it marked: smooth travelling fields -> column walk, incoherent ones -> direct gather (workgroups of the other
-        // kind, and all of them on the reference's own fields, exit after one load)
-        hipLaunchKernelGGL(warp_gather_columns_kernel, dim3(ncol), dim3(256), 0, s, v, (const float *)coords, out, out_range,
-                           (const int *)todo, B, C, D, H, W);
-        hipLaunchKernelGGL(warp_gather_direct_kernel, dim3((unsigned)nblocks, K2_DIRECT_SPLIT * (K2_TH / (4 * (256 / K2_TW)))), dim3(256), 0, s, v, (const float *)coords,
-                           out, out_range, (const int *)todo, B, C, D, H, W);
+        const dim3 gdirect((unsigned)nblocks, K2_DIRECT_SPLIT * (K2_TH / (4 * (256 / K2_TW))));
+        if constexpr (DT == MPHIP_DTYPE_F32) {
+            if (corner_img && !img_ready)
+                hipLaunchKernelGGL(warp_corner_image_kernel, dim3(K2_CORNER_CELLS, (unsigned)B), dim3(128), 0, s, v, corner_img, C, D, H, W, cg, (int)groups);
+            hipLaunchKernelGGL(warp_gather_kernel, dim3((unsigned)nblocks, groups), dim3(K2_THREADS), 0, s, v, coords, out, out_range, todo, B, C, D, H, W,
+                               (const float *)corner_img, cg);
+            // the tiles it marked: smooth travelling fields -> column walk, incoherent ones -> direct gather (workgroups of the other
+            // kind, and all of them on the reference's own fields, exit after one load)
+            hipLaunchKernelGGL(warp_gather_columns_kernel, dim3(ncol), dim3(256), 0, s, v, (const float *)coords, out, out_range,
+                               (const int *)todo, B, C, D, H, W);
+            hipLaunchKernelGGL(warp_gather_direct_kernel, gdirect, dim3(256), 0, s, v, (const float *)coords,
+                               out, out_range, (const int *)todo, B, C, D, H, W);
+        } else {
+            if (corner_img && !img_ready)
+                hipLaunchKernelGGL(warp_corner_image_typed_kernel<DT>, dim3(K2_CORNER_CELLS, (unsigned)B), dim3(128), 0, s, v, corner_img, C, D, H, W, cg,
+                                   (int)groups);
+            hipLaunchKernelGGL(warp_gather_typed_kernel<DT>, dim3((unsigned)nblocks, groups), dim3(K2_THREADS), 0, s, coords, out, out_range, todo,
+                               B, C, D, H, W, (const float *)corner_img, cg);
+            hipLaunchKernelGGL(warp_gather_columns_typed_kernel<DT>, dim3(ncol), dim3(256), 0, s, v, (const float *)coords, out, out_range,
+                               (const int *)todo, B, C, D, H, W);
+            hipLaunchKernelGGL(warp_gather_direct_typed_kernel<DT>, gdirect, dim3(256), 0, s, v, (const float *)coords,
+                               out, out_range, (const int *)todo, B, C, D, H, W);
+        }
     } else {
         const int cpb = C >= 48 ? 12 : C;
-        hipLaunchKernelGGL(warp_gather_scalar_kernel, dim3(cdiv((size_t)B * D * H * W, 256), cdiv(C, cpb)), dim3(256), 0, s,
-                           v, coords, out, B, C, D, H, W, cpb);
+        const dim3 grid(cdiv((size_t)B * D * H * W, 256), cdiv(C, cpb));
+        if constexpr (DT == MPHIP_DTYPE_F32)
+            hipLaunchKernelGGL(warp_gather_scalar_kernel, grid, dim3(256), 0, s, v, coords, out, B, C, D, H, W, cpb);
+        else
+            hipLaunchKernelGGL(warp_gather_scalar_typed_kernel<DT>, grid, dim3(256), 0, s, v, coords, out, B, C, D, H, W, cpb);
     }
     return check_launch("warp_volume");
 }
 
+static int warp_volume_gather_dt(const void *v, int dtype, const float *coords, float *out, float *out_range, int *todo, float *corner_img,
+                                 bool img_ready, int B, int C, int D, int H, int W, hipStream_t s) {
+    switch (dtype) {
+        case MPHIP_DTYPE_F32: return warp_volume_gather_t<MPHIP_DTYPE_F32>(v, coords, out, out_range, todo, corner_img, img_ready, B, C, D, H, W, s);
+        case MPHIP_DTYPE_F16: return warp_volume_gather_t<MPHIP_DTYPE_F16>(v, coords, out, out_range, todo, corner_img, img_ready, B, C, D, H, W, s);
+        case MPHIP_DTYPE_BF16: return warp_volume_gather_t<MPHIP_DTYPE_BF16>(v, coords, out, out_range, todo, corner_img, img_ready, B, C, D, H, W, s);
+    }
+    set_error("warp_volume: unknown source dtype %d", dtype);
+    return MPHIP_EINVAL;
+}
+
+static int warp_volume_gather(const float *v, const float *coords, float *out, float *out_range, int *todo, float *corner_img, bool img_ready,
+                              int B, int C, int D, int H, int W, hipStream_t s) {
+    return warp_volume_gather_t<MPHIP_DTYPE_F32>(v, coords, out, out_range, todo, corner_img, img_ready, B, C, D, H, W, s);
+}
+
+// K3's gather pass on given coordinates, the projection stored in out_dtype
+static int launch_dsum(const float *v, const float *coords, void *out, int out_dtype, int B, int C, int D, int H, int W, size_t v_frame_stride,
+                       hipStream_t s) {
+    constexpr int CPB = 16;
+    const int tiles = ((H + K3_TH - 1) / K3_TH) * ((W + K3_TW - 1) / K3_TW);
+    const dim3 grid((unsigned)((size_t)B * tiles * cdiv(C, CPB)));
+    switch (out_dtype) {
+        case MPHIP_DTYPE_F32:
+            hipLaunchKernelGGL(warp_gather_dsum_kernel<CPB>, grid, dim3(256), 0, s, v, coords, (float *)out, B, C, D, H, W, v_frame_stride);
+            break;
+        case MPHIP_DTYPE_F16:
+            hipLaunchKernelGGL((warp_gather_dsum_typed_kernel<CPB, MPHIP_DTYPE_F16>), grid, dim3(256), 0, s, v, coords, (_Float16 *)out, B, C, D, H, W,
+                               v_frame_stride);
+            break;
+        case MPHIP_DTYPE_BF16:
+            hipLaunchKernelGGL((warp_gather_dsum_typed_kernel<CPB, MPHIP_DTYPE_BF16>), grid, dim3(256), 0, s, v, coords, (bf16_bits *)out, B, C, D, H,
+                               W, v_frame_stride);
+            break;
+        default: set_error("warp_volume_dsum: unknown output dtype %d", out_dtype); return MPHIP_EINVAL;
+    }
+    return MPHIP_OK;
+}
+
 static int warp_volume_dsum_impl(const char *name, const float *v, size_t v_frame_stride, const float *field,
-                                 const float *lin_d, const float *lin_h, const float *lin_w, float *out, int B, int C, int D,
+                                 const float *lin_d, const float *lin_h, const float *lin_w, void *out, int out_dtype, int B, int C, int D,
                                  int H, int W, int fD, int fH, int fW, void *workspace, size_t workspace_bytes, void *stream) {
     int rc = check_warp_args(name, v, field, lin_d, lin_h, lin_w, out, B, C, D, H, W, fD, fH, fW);
     if (rc) return rc;
@@ -1023,10 +991,8 @@ static int warp_volume_dsum_impl(const char *name, const float *v, size_t v_fram
     float *coords = (float *)workspace;
     rc = launch_coords(field, lin_d, lin_h, lin_w, coords, nullptr, B, D, H, W, fD, fH, fW, s);
     if (rc) return rc;
-    constexpr int CPB = 16;
-    const int tiles = ((H + K3_TH - 1) / K3_TH) * ((W + K3_TW - 1) / K3_TW);
-    hipLaunchKernelGGL(warp_gather_dsum_kernel<CPB>, dim3((unsigned)((size_t)B * tiles * cdiv(C, CPB))), dim3(256), 0, s, v,
-                       coords, out, B, C, D, H, W, v_frame_stride);
+    rc = launch_dsum(v, coords, out, out_dtype, B, C, D, H, W, v_frame_stride, s);
+    if (rc) return rc;
     return check_launch(name);
 }
 
@@ -1073,6 +1039,26 @@ extern "C" int mphip_warp_corner_image(const float *v, void *img, size_t img_byt
                        cg, cdiv(C, cg));
     return check_launch("warp_corner_image");
 }
+extern "C" int mphip_warp_corner_image_typed(const void *v, int v_dtype, void *img, size_t img_bytes, int B, int C, int D, int H, int W, void *stream) {
+    if (v_dtype == MPHIP_DTYPE_F32) return mphip_warp_corner_image((const float *)v, img, img_bytes, B, C, D, H, W, stream);
+    MPHIP_REQUIRE(v && img, "warp_corner_image_typed: null pointer");
+    MPHIP_REQUIRE(B > 0 && C > 0 && D > 0 && H > 0 && W > 0, "warp_corner_image_typed: bad dims");
+    MPHIP_REQUIRE(((uintptr_t)img & 15) == 0, "warp_corner_image_typed: img must be 16-byte aligned");
+    MPHIP_REQUIRE(v_dtype == MPHIP_DTYPE_F16 || v_dtype == MPHIP_DTYPE_BF16, "warp_corner_image_typed: unknown dtype %d", v_dtype);
+    if (img_bytes < mphip_warp_corner_image_bytes(B, C)) {
+        set_error("warp_corner_image_typed: buffer %zu bytes < required %zu", img_bytes, mphip_warp_corner_image_bytes(B, C));
+        return MPHIP_EWORKSPACE;
+    }
+    const int cg = k2_group_channels(k2_tiles(B, D, H, W), C);
+    const dim3 grid(K2_CORNER_CELLS, (unsigned)B);
+    if (v_dtype == MPHIP_DTYPE_F16)
+        hipLaunchKernelGGL(warp_corner_image_typed_kernel<MPHIP_DTYPE_F16>, grid, dim3(128), 0, (hipStream_t)stream, (const _Float16 *)v, (float *)img,
+                           C, D, H, W, cg, cdiv(C, cg));
+    else
+        hipLaunchKernelGGL(warp_corner_image_typed_kernel<MPHIP_DTYPE_BF16>, grid, dim3(128), 0, (hipStream_t)stream, (const bf16_bits *)v,
+                           (float *)img, C, D, H, W, cg, cdiv(C, cg));
+    return check_launch("warp_corner_image_typed");
+}
 extern "C" int mphip_warp_volume_coords_img(const float *v, const float *coords, float *out, float *out_range, int B, int C, int D, int H, int W,
                                             void *workspace, size_t workspace_bytes, const void *img, void *stream) {
     MPHIP_REQUIRE(v && coords && out && img, "warp_volume_coords_img: null pointer");
@@ -1086,6 +1072,19 @@ extern "C" int mphip_warp_volume_coords_img(const float *v, const float *coords,
     }
     return warp_volume_gather(v, coords, out, out_range, (int *)workspace, (float *)img, true, B, C, D, H, W, (hipStream_t)stream);
 }
+extern "C" int mphip_warp_volume_coords_img_typed(const void *v, int v_dtype, const float *coords, float *out, float *out_range, int B, int C, int D,
+                                                  int H, int W, void *workspace, size_t workspace_bytes, const void *img, void *stream) {
+    MPHIP_REQUIRE(v && coords && out && img, "warp_volume_coords_img_typed: null pointer");
+    MPHIP_REQUIRE(B > 0 && C > 0 && D > 0 && H > 0 && W > 0, "warp_volume_coords_img_typed: bad dims");
+    MPHIP_REQUIRE((size_t)D * H * W < (1u << 30), "warp_volume_coords_img_typed: volume too large for 32-bit tap offsets");
+    MPHIP_REQUIRE(((uintptr_t)img & 15) == 0, "warp_volume_coords_img_typed: img must be 16-byte aligned");
+    const size_t need = k2_todo_bytes(B, D, H, W);
+    if (!workspace || workspace_bytes < need) {
+        set_error("warp_volume_coords_img_typed: workspace %zu bytes < required %zu", workspace_bytes, need);
+        return MPHIP_EWORKSPACE;
+    }
+    return warp_volume_gather_dt(v, v_dtype, coords, out, out_range, (int *)workspace, (float *)img, true, B, C, D, H, W, (hipStream_t)stream);
+}
 
 // K3 with the coordinate pass already done (mphip_warp_coords): lets a caller look at the sample positions BEFORE the volume is
 // produced (mphip_warp_sample_box -> mphip_conv3d_fwd_roi).  shared != 0: v is ONE volume [1,C,D,H,W] for all B coordinate sets.
@@ -1093,25 +1092,39 @@ extern "C" int mphip_warp_volume_dsum_coords(const float *v, const float *coords
                                              void *stream) {
     MPHIP_REQUIRE(v && coords && out, "warp_volume_dsum_coords: null pointer");
     MPHIP_REQUIRE(B > 0 && C > 0 && D > 0 && H > 0 && W > 0, "warp_volume_dsum_coords: bad dims");
-    constexpr int CPB = 16;
-    const int tiles = ((H + K3_TH - 1) / K3_TH) * ((W + K3_TW - 1) / K3_TW);
-    hipLaunchKernelGGL(warp_gather_dsum_kernel<CPB>, dim3((unsigned)((size_t)B * tiles * cdiv(C, CPB))), dim3(256), 0, (hipStream_t)stream, v,
-                       coords, out, B, C, D, H, W, shared ? (size_t)0 : (size_t)C * D * H * W);
+    const int rc = launch_dsum(v, coords, out, MPHIP_DTYPE_F32, B, C, D, H, W, shared ? (size_t)0 : (size_t)C * D * H * W, (hipStream_t)stream);
+    if (rc) return rc;
     return check_launch("warp_volume_dsum_coords");
+}
+
+extern "C" int mphip_warp_volume_dsum_coords_typed(const float *v, const float *coords, void *out, int out_dtype, int B, int C, int D, int H, int W,
+                                                   int shared, void *stream) {
+    MPHIP_REQUIRE(v && coords && out, "warp_volume_dsum_coords_typed: null pointer");
+    MPHIP_REQUIRE(B > 0 && C > 0 && D > 0 && H > 0 && W > 0, "warp_volume_dsum_coords_typed: bad dims");
+    const int rc = launch_dsum(v, coords, out, out_dtype, B, C, D, H, W, shared ? (size_t)0 : (size_t)C * D * H * W, (hipStream_t)stream);
+    if (rc) return rc;
+    return check_launch("warp_volume_dsum_coords_typed");
 }
 
 extern "C" int mphip_warp_volume_dsum(const float *v, const float *field, const float *lin_d, const float *lin_h,
                                       const float *lin_w, float *out, int B, int C, int D, int H, int W, int fD,
                                       int fH, int fW, void *workspace, size_t workspace_bytes, void *stream) {
-    return warp_volume_dsum_impl("warp_volume_dsum", v, (size_t)C * D * H * W, field, lin_d, lin_h, lin_w, out, B, C, D, H, W, fD,
-                                 fH, fW, workspace, workspace_bytes, stream);
+    return warp_volume_dsum_impl("warp_volume_dsum", v, (size_t)C * D * H * W, field, lin_d, lin_h, lin_w, out, MPHIP_DTYPE_F32, B, C, D, H, W,
+                                 fD, fH, fW, workspace, workspace_bytes, stream);
 }
 
 extern "C" int mphip_warp_volume_dsum_shared(const float *v, const float *field, const float *lin_d, const float *lin_h,
                                              const float *lin_w, float *out, int B, int C, int D, int H, int W, int fD,
                                              int fH, int fW, void *workspace, size_t workspace_bytes, void *stream) {
-    return warp_volume_dsum_impl("warp_volume_dsum_shared", v, 0, field, lin_d, lin_h, lin_w, out, B, C, D, H, W, fD, fH, fW,
+    return warp_volume_dsum_impl("warp_volume_dsum_shared", v, 0, field, lin_d, lin_h, lin_w, out, MPHIP_DTYPE_F32, B, C, D, H, W, fD, fH, fW,
                                  workspace, workspace_bytes, stream);
+}
+
+extern "C" int mphip_warp_volume_dsum_typed(const float *v, int shared, const float *field, const float *lin_d, const float *lin_h,
+                                            const float *lin_w, void *out, int out_dtype, int B, int C, int D, int H, int W, int fD, int fH, int fW,
+                                            void *workspace, size_t workspace_bytes, void *stream) {
+    return warp_volume_dsum_impl("warp_volume_dsum_typed", v, shared ? (size_t)0 : (size_t)C * D * H * W, field, lin_d, lin_h, lin_w, out, out_dtype,
+                                 B, C, D, H, W, fD, fH, fW, workspace, workspace_bytes, stream);
 }
 
 // =====================================================================================================

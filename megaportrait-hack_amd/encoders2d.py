@@ -145,8 +145,7 @@ class Eapp(nn.Module):
     def forward(self, x):
         out = self.trunk2d(x)
         vs = out.view(out.size(0), 96, 16, *out.shape[2:])       # model.py:271 — channel c*16+d is voxel (c, d)
-        for name in M.Eapp3DTail._ORDER:                          # model.py:276-290, HIP kernels
-            vs = getattr(self, name)(vs)
+        vs = M.eapp_tail(self, vs)                                # model.py:276-290, HIP kernels (in the blocks' model dtype)
         return vs, self.descriptor(x)
 
 

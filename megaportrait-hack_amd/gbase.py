@@ -93,15 +93,23 @@ class Gbase(M._HotSliceRunner, nn.Module):
 
         if xs.shape[0] != 1:
             raise ValueError("reenact expects a single source image [1,3,H,W]")
-        with torch.autocast(device_type="cuda", dtype=torch.float16, enabled=bool(fp16)):
+        import contextlib
+
+        # a half model (model.model_dtype): the hot slice runs on its fp32 twin with typed boundaries, exactly as forward() does it
+        dt = M.model_dtype(self)
+        hot = self if dt == torch.float32 else M._twin(self, self._hot_twin)
+        policy = ops.half_products(True) if dt != torch.float32 else contextlib.nullcontext()
+        with torch.autocast(device_type="cuda", dtype=torch.float16, enabled=bool(fp16)), policy:
             vs, es = self.appearanceEncoder(xs)
             Rs, ts, zs = self.motionEncoder(self._nhwc(xs))
-            vc2d = self.G3d(M.apply_warping_field(vs, self.warp_generator_s2c(Rs, ts, zs, es)))
+            w_s2c = hot.warp_generator_s2c(Rs, ts, zs, es)
+            vc2d = hot.G3d(ops.warp_volume(vs, w_s2c) if dt != torch.float32 else M.apply_warping_field(vs, w_s2c))
             b, e = dp.shard_range(xd.shape[0], rank, world)
             outs = []
             for i in range(b, e, chunk):
                 j = min(e, i + chunk)
                 Rd, td, zd = self.motionEncoder(self._nhwc(xd[i:j]))
-                w_c2d = self.warp_generator_c2d(Rd, td, zd, es.float().expand(j - i, -1).contiguous())
-                outs.append(self.G2d(self._nhwc(ops.warp_volume_dsum(vc2d, w_c2d))).float().contiguous())
+                w_c2d = hot.warp_generator_c2d(Rd, td, zd, es.float().expand(j - i, -1).contiguous())
+                proj = ops.warp_volume_dsum(vc2d, w_c2d) if dt == torch.float32 else ops.warp_volume_dsum(vc2d, w_c2d, out_dtype=dt)
+                outs.append(self.G2d(self._nhwc(proj)).float().contiguous())
         return torch.cat(outs, dim=0) if outs else xs.new_zeros((0,) + tuple(xs.shape[1:]))

@@ -51,6 +51,143 @@ def _autocast_policy(fn):
     return wrapped
 
 
+# ------------------------------------------------------------------ model dtypes (INTEGRATION.md "Model dtypes")
+# A hot module's model dtype is the dtype of its floating-point parameters.  A .half() / .bfloat16() module runs as its "fp32 twin": a
+# copy whose parameters are fp32 shadows of the half ones (exact), under the single-product conv policy (ops.half_products), with the
+# boundary tensors typed — inputs are read in their own dtype (K2, ops.cast_to_f32_range), outputs written in the model dtype (K3,
+# ops.cast_from_f32).  Activations between kernels stay fp32.  The output is therefore bitwise the twin's fp32 output rounded once.
+_HALF = (torch.float16, torch.bfloat16)
+_dtype_generation = 0   # bumped by every dtype / device conversion of a hot module (_ModelDtype._apply): invalidates cached model dtypes
+_TRAIN_HALF_MSG = ("{}: training a module whose parameters are {} is not supported — keep fp32 parameters and use torch.autocast "
+                   "(the HIP path then runs the same single-product convs)")
+
+
+class _ModelDtype:
+    """Mixin of the hot modules: `.half()`, `.bfloat16()`, `.float()`, `.to()` reach every submodule's `_apply`; each call invalidates
+    the cached model dtypes (recomputed on the next forward: the per-call check costs one dict lookup) and drops the fp32 twins of the
+    converted modules (a module converted back to fp32 holds no dead copy; a half one builds its twin again on its next forward)."""
+
+    def _apply(self, fn, *args, **kwargs):
+        global _dtype_generation
+        _dtype_generation += 1
+        out = super()._apply(fn, *args, **kwargs)
+        for m in self.modules():
+            for k in _TWIN_SLOTS:
+                m.__dict__.pop(k, None)
+        return out
+
+
+def model_dtype(module: nn.Module) -> torch.dtype:
+    """The dtype of the module's floating-point parameters: float32, float16 or bfloat16.  Mixed dtypes raise RuntimeError."""
+    hit = module.__dict__.get("_mphip_dtype")
+    if hit is not None and hit[0] == _dtype_generation:
+        return hit[1]
+    dts = {p.dtype for p in module.parameters() if p.is_floating_point()}
+    if len(dts) > 1:
+        raise RuntimeError(f"{type(module).__name__}: parameters mix dtypes ({', '.join(sorted(str(d) for d in dts))}); a hot module runs in "
+                           "ONE model dtype — convert it as a whole with .float(), .half() or .bfloat16()")
+    dt = dts.pop() if dts else torch.float32
+    if dt not in (torch.float32,) + _HALF:
+        raise RuntimeError(f"{type(module).__name__}: parameters are {dt}; the HIP path runs float32, float16 or bfloat16 models")
+    module.__dict__["_mphip_dtype"] = (_dtype_generation, dt)
+    return dt
+
+
+# per-module caches (packs, derived weights, plans, streams, ...): a twin starts without them
+_TWIN_SLOTS = ("_mphip_twin", "_mphip_tail_twin")
+_CACHE_ATTRS = ("_mphip_pack", "_mphip_bwd_pack", "_w_kn", "_w_head", "_fused", "_plans", "_side_streams", "_mphip_dtype") + _TWIN_SLOTS
+
+
+def _fp32_copy(module: nn.Module) -> nn.Module:
+    """Deep copy with every floating-point parameter / buffer as an fp32 tensor (no gradient) and the caches left behind."""
+    import copy
+
+    memo = {}
+    for m in module.modules():
+        for k in _CACHE_ATTRS:
+            v = m.__dict__.get(k)
+            if v is not None:
+                memo[id(v)] = {} if isinstance(v, dict) else None
+        for p in m._parameters.values():
+            if p is not None:
+                memo[id(p)] = nn.Parameter(p.detach().float() if p.is_floating_point() else p.detach().clone(), requires_grad=False)
+        for b in m._buffers.values():
+            if b is not None:
+                memo[id(b)] = b.detach().float() if b.is_floating_point() else b.detach().clone()
+    return copy.deepcopy(module, memo)
+
+
+def _twin_key(pairs):
+    return (ops.weight_epoch(),) + tuple((p.data_ptr(), p._version) for p, _ in pairs)
+
+
+def _twin(module: nn.Module, build=None, slot: str = "_mphip_twin") -> nn.Module:
+    """The module's fp32 twin, kept in step with the half parameters: a parameter that changed (in-place update, load_state_dict) is
+    copied into its shadow, whose new version makes every cache of the twin (packs, plans) rebuild as it would for an fp32 module.
+    The twin is built anew when there is none (a conversion of the module drops it: _ModelDtype._apply), after ops.invalidate_packs()
+    (a Parameter object may have been replaced) and when a parameter changed device.  Whenever a twin is built or a parameter moved,
+    the model dtype is checked afresh, uncached: a sub-module converted on its own (`.G3d.final_conv.float()`) never runs mixed."""
+    src = module.__dict__.get(slot)
+    if src is not None:
+        twin, pairs, key = src
+        now = _twin_key(pairs)
+        if now == key:
+            return twin
+        module.__dict__.pop("_mphip_dtype", None)
+        model_dtype(module)
+        if now[0] == key[0] and all(p.device == q.device for p, q in pairs):
+            with torch.no_grad():
+                for (p, q), k_old, k_new in zip(pairs, key[1:], now[1:]):
+                    if k_old != k_new:
+                        q.copy_(p)
+            module.__dict__[slot] = (twin, pairs, now)
+            return twin
+    module.__dict__.pop(slot, None)
+    module.__dict__.pop("_mphip_dtype", None)
+    model_dtype(module)
+    if build is not None:
+        twin, pairs = build()   # (twin, [(half parameter, its fp32 shadow), ...])
+    else:
+        twin = _fp32_copy(module)
+        pairs = list(zip(module.parameters(), twin.parameters()))
+    module.__dict__[slot] = (twin, pairs, _twin_key(pairs))
+    return twin
+
+
+def _refuse_half_training(module, dt, *tensors):
+    if ag.needs_grad(module, *tensors):
+        raise RuntimeError(_TRAIN_HALF_MSG.format(type(module).__name__, dt))
+
+
+def _model_dtype_forward(cast_input: bool = False, volume_input: bool = False):
+    """Decorator of a hot module's public forward: fp32 modules run it unchanged; a half module runs its fp32 twin's (see above) and
+    returns the model dtype.  cast_input: the first argument feeds an f16x3 conv stack — a half input is widened together with its range
+    descriptor in one pass (ops.cast_to_f32_range).  volume_input: a 4-D first argument is Eapp's [B,1536,H,W] map, viewed as the
+    [B,96,16,H,W] volume before the cast (the descriptor rides on the tensor the stack reads)."""
+    import functools
+
+    def deco(fn):
+        @functools.wraps(fn)
+        def wrapped(self, *args, **kwargs):
+            dt = model_dtype(self)
+            if dt == torch.float32:
+                return fn(self, *args, **kwargs)
+            _refuse_half_training(self, dt, *args, *kwargs.values())
+            twin = _twin(self, getattr(self, "_twin_build", None))
+            if cast_input and args and isinstance(args[0], torch.Tensor) and args[0].dtype in _HALF:
+                x = args[0]
+                if volume_input and x.dim() == 4:
+                    x = x.reshape(x.size(0), 96, 16, *x.shape[2:])
+                args = (ops.cast_to_f32_range(x),) + args[1:]
+            with ops.half_products(True):
+                y = fn(twin, *args, **kwargs)   # (this class's forward on the twin, also when a subclass calls it: encoders2d.G2d)
+            return ops.cast_from_f32(y, dt)
+
+        return wrapped
+
+    return deco
+
+
 class _PackCache:
     """Packed conv weights, rebuilt when the parameter changes (in-place update, load_state_dict or .to()).
     The pack lives ON the conv module (not in a global table keyed by id()), so it dies with the module and
@@ -187,7 +324,7 @@ class ResBlock3D_Adaptive(nn.Module):
                                    b2=n2.bias, residual=res, relu=True, up=_up)
 
 
-class FlowField(nn.Module):
+class FlowField(_ModelDtype, nn.Module):
     """model.py:415-471: [B,512,1,1] -> [B,3,16,16,16] in [0,1)."""
 
     _UPS = ((2, 2, 2), (2, 2, 2), (1, 2, 2), (1, 2, 2))
@@ -230,6 +367,7 @@ class FlowField(nn.Module):
             self.__dict__["_w_head"] = hit
         return hit[1]
 
+    @_model_dtype_forward()
     def forward_from_codes(self, z, e, gamma):
         """Inference entry used by the warp generators: FlowField((z+e) @ Gamma) with the two dense products merged."""
         z, e = _f32(z, e)
@@ -237,6 +375,7 @@ class FlowField(nn.Module):
         x = ops.add_matmul(z.reshape(b, 512), e.reshape(b, 512), self._head_kn(gamma), self.conv1x1.bias)
         return self._tail(x.view(b, 512, 4, 1, 1), False)
 
+    @_model_dtype_forward()
     def forward(self, zs, adaptive_gamma=0, adaptive_beta=0):  # last two ignored, as in the reference
         zs = _f32(zs)
         train = ag.needs_grad(self, zs)
@@ -268,7 +407,7 @@ class FlowField(nn.Module):
         return x
 
 
-class _WarpGenerator(nn.Module):
+class _WarpGenerator(_ModelDtype, nn.Module):
     _INVERT = False
 
     def __init__(self, num_channels):
@@ -280,6 +419,7 @@ class _WarpGenerator(nn.Module):
         self.adaptive_matrix_gamma = nn.Parameter(torch.randn(self.num_channels, self.num_channels))
         self.adaptive_matrix_beta = nn.Parameter(torch.randn(self.num_channels, self.num_channels))
 
+    @_model_dtype_forward()
     def forward(self, R, t, z, e):
         assert R.shape == (z.shape[0], 3), f"Expected R shape (batch_size, 3), got {R.shape}"
         assert t.shape == (z.shape[0], 3), f"Expected t shape (batch_size, 3), got {t.shape}"
@@ -361,7 +501,7 @@ class ResBlock3D(nn.Module):
                                    pool2=_pool_after)
 
 
-class G3d(nn.Module):
+class G3d(_ModelDtype, nn.Module):
     """model.py:571-597.  nn.Sequential indices give the reference's state-dict names."""
 
     def __init__(self, in_channels):
@@ -379,6 +519,7 @@ class G3d(nn.Module):
         )
         self.final_conv = nn.Conv3d(96, 96, kernel_size=3, padding=1)
 
+    @_model_dtype_forward(cast_input=True)
     @_autocast_policy
     def forward(self, x, _after_first_conv=None, _final_roi=None):
         """`_final_roi`: sample boxes of the warp that is the ONLY reader of the result (GbaseHotSlice under autograd): final_conv
@@ -400,7 +541,7 @@ class G3d(nn.Module):
         return ops.conv3d(x, _packs.get(self.final_conv))
 
 
-class Eapp3DTail(nn.Module):
+class Eapp3DTail(_ModelDtype, nn.Module):
     """Scope row f1: the 3D tail of Eapp, model.py:217-226 + 271-290.  Attribute names are
     the reference Eapp's, so `appearanceEncoder.resblock3D_*` checkpoint keys load into this module directly.
     The reference assigns `resblock3D_96_2` twice (model.py:218,225): five blocks exist, one is applied twice."""
@@ -417,6 +558,7 @@ class Eapp3DTail(nn.Module):
         self.resblock3D_96_2 = ResBlock3D_Adaptive(in_channels=96, out_channels=96)
         self.resblock3D_96_2_2 = ResBlock3D_Adaptive(in_channels=96, out_channels=96)
 
+    @_model_dtype_forward(cast_input=True, volume_input=True)
     @_autocast_policy
     def forward(self, out):
         """out: Eapp's conv_1 output [B,1536,H,W] (model.py:268) or the reshaped volume [B,96,16,H,W]."""
@@ -431,7 +573,40 @@ class Eapp3DTail(nn.Module):
         return vs
 
 
-class G2dHead(nn.Module):
+def eapp_tail(owner: nn.Module, vs):
+    """Eapp3DTail's block sequence on the `resblock3D_*` blocks of `owner` (an Eapp that holds them itself, encoders2d.Eapp), in their
+    model dtype: fp32 blocks run as they are; fp16 / bf16 blocks run as an fp32 twin, the input widened with its range descriptor in one
+    pass and the output rounded once — what Eapp3DTail does for a half module."""
+    blocks = {name: getattr(owner, name) for name in Eapp3DTail._ORDER}
+    dts = {p.dtype for b in blocks.values() for p in b.parameters()}
+    if dts == {torch.float32}:
+        owner.__dict__.pop("_mphip_tail_twin", None)   # (converted back to fp32 by a parent that is not a hot module)
+        for name in Eapp3DTail._ORDER:
+            vs = blocks[name](vs)
+        return vs
+    if len(dts) > 1:
+        raise RuntimeError(f"{type(owner).__name__}: the 3-D tail's parameters mix dtypes ({', '.join(sorted(str(d) for d in dts))}); convert "
+                           "the module as a whole with .float(), .half() or .bfloat16()")
+    dt = dts.pop()
+    _refuse_half_training(nn.ModuleList(blocks.values()), dt, vs)
+
+    def build():
+        twin = Eapp3DTail.__new__(Eapp3DTail)
+        nn.Module.__init__(twin)
+        pairs = []
+        for name in dict.fromkeys(Eapp3DTail._ORDER):
+            setattr(twin, name, _fp32_copy(blocks[name]))
+            pairs += list(zip(blocks[name].parameters(), getattr(twin, name).parameters()))
+        return twin, pairs
+
+    twin = _twin(owner, build, "_mphip_tail_twin")
+    x = ops.cast_to_f32_range(vs) if vs.dtype in _HALF else vs
+    with ops.half_products(True):
+        y = twin(x)
+    return ops.cast_from_f32(y, dt)
+
+
+class G2dHead(_ModelDtype, nn.Module):
     """Scope row f3: the entry of G2d, model.py:718-719 + 756-757 — `reshape` Conv2d(96,1536,1)
     followed directly by `conv1x1` Conv2d(1536,512,1).  There is no nonlinearity between them, so at inference the two
     collapse into ONE 96->512 product (W = W2 @ W1, b = W2 @ b1 + b2): 19x fewer FLOPs and the 25 MB/frame 1536-channel
@@ -442,6 +617,16 @@ class G2dHead(nn.Module):
         super().__init__()
         self.reshape = nn.Conv2d(96, 1536, kernel_size=1)
         self.conv1x1 = nn.Conv2d(1536, 512, kernel_size=1)
+
+    def _twin_build(self):
+        """The fp32 twin of the head alone (a subclass such as encoders2d.G2d carries a PyTorch body the head never runs)."""
+        twin = G2dHead.__new__(G2dHead)
+        nn.Module.__init__(twin)
+        pairs = []
+        for name in ("reshape", "conv1x1"):
+            setattr(twin, name, _fp32_copy(getattr(self, name)))
+            pairs += list(zip(getattr(self, name).parameters(), getattr(twin, name).parameters()))
+        return twin, pairs
 
     def _fused_pack(self) -> ops.PackedConv:
         ps = (self.reshape.weight, self.reshape.bias, self.conv1x1.weight, self.conv1x1.bias)
@@ -455,6 +640,7 @@ class G2dHead(nn.Module):
             self.__dict__["_fused"] = hit
         return hit[1]
 
+    @_model_dtype_forward(cast_input=True)
     def forward(self, x):
         """x: the hot slice's output [B,96,H,W] (model.py:1171) -> [B,512,H,W], the input of G2d's ResBlock2D stack."""
         x = _f32(x)
@@ -468,7 +654,7 @@ class G2dHead(nn.Module):
         return y.reshape(b, 512, h, w)
 
 
-class _HotSliceRunner:
+class _HotSliceRunner(_ModelDtype):
     """model.py:1151-1171 over `self.warp_generator_s2c`, `self.warp_generator_c2d`, `self.G3d` — shared by
     GbaseHotSlice (the slice alone) and gbase.Gbase (the orchestrator)."""
 
@@ -526,22 +712,59 @@ class _HotSliceRunner:
 
     _MAX_PLANS = 6
 
-    @_autocast_policy
+    _HOT_CHILDREN = ("warp_generator_s2c", "warp_generator_c2d", "G3d")
+    _TWIN_FLAGS = ("use_c_plan", "overlap_generators", "full_final_conv", "max_frames_per_pass")
+
     def _run(self, vs, es, Rs, ts, zs, Rd, td, zd, check_shape: bool):
-        vs, es, Rs, ts, zs, Rd, td, zd = _f32(vs, es, Rs, ts, zs, Rd, td, zd)
+        dt = model_dtype(self)
+        if dt != torch.float32:
+            return self._run_typed(dt, vs, es, Rs, ts, zs, Rd, td, zd, check_shape)
+        return self._run_f32(vs, es, Rs, ts, zs, Rd, td, zd, check_shape)
+
+    def _hot_twin(self):
+        """fp32 twin of the hot slice alone (gbase.Gbase's 2-D modules are not copied): a bare GbaseHotSlice over fp32 copies."""
+        twin = GbaseHotSlice.__new__(GbaseHotSlice)
+        nn.Module.__init__(twin)
+        pairs = []
+        for name in self._HOT_CHILDREN:
+            src = getattr(self, name)
+            setattr(twin, name, _fp32_copy(src))
+            pairs += list(zip(src.parameters(), getattr(twin, name).parameters()))
+        return twin, pairs
+
+    def _run_typed(self, dt, vs, es, Rs, ts, zs, Rd, td, zd, check_shape: bool):
+        """A half model (see model_dtype): the fp32 twin under the single-product conv policy; K2 reads vs in its own dtype, K3 writes the
+        projection in the model dtype."""
+        _refuse_half_training(self, dt, vs, es, Rs, ts, zs, Rd, td, zd)
+        twin = _twin(self, self._hot_twin)
+        for k in self._TWIN_FLAGS:
+            twin.__dict__[k] = getattr(self, k)
+        with ops.half_products(True):
+            return twin._run_f32(vs, es, Rs, ts, zs, Rd, td, zd, check_shape, out_dtype=dt)
+
+    @_autocast_policy
+    def _run_f32(self, vs, es, Rs, ts, zs, Rd, td, zd, check_shape: bool, out_dtype=None):
+        """out_dtype (a half model's twin): vs may stay fp16/bf16 — K2 reads it directly — and the result is written in out_dtype."""
+        typed = out_dtype is not None and isinstance(vs, torch.Tensor) and vs.dtype in _HALF
+        es, Rs, ts, zs, Rd, td, zd = _f32(es, Rs, ts, zs, Rd, td, zd)
+        vs = vs if typed else _f32(vs)
         if (self.use_c_plan and vs.shape[0] > 0 and vs.dim() == 5 and vs.shape[1] == 96 and ops._conv_hook is None
                 and ops._GNIN_ENABLED and ops._GN_SMALL_ENABLED and ops._RANGES_ENABLED   # (dev A/B switches act on the per-op path)
                 and not ag.needs_grad(self, vs, es, Rs, ts, zs, Rd, td, zd)
                 and all(v % 8 == 0 for v in vs.shape[2:])):
             if check_shape:
                 assert vs.shape[1:] == (96, 16, 64, 64), f"Expected vc shape (_, 96, 16, 64, 64), got {vs.shape}"
+            if out_dtype is not None:
+                return self._plan_for(vs).forward(vs, es, Rs, ts, zs, Rd, td, zd, out_dtype=out_dtype)
             return self._plan_for(vs).forward(vs, es, Rs, ts, zs, Rd, td, zd)
-        return self._run_python(vs, es, Rs, ts, zs, Rd, td, zd, check_shape)
+        return self._run_python(vs, es, Rs, ts, zs, Rd, td, zd, check_shape, out_dtype)
 
-    def _run_python(self, vs, es, Rs, ts, zs, Rd, td, zd, check_shape: bool):
-        vs, es, Rs, ts, zs, Rd, td, zd = _f32(vs, es, Rs, ts, zs, Rd, td, zd)
+    def _run_python(self, vs, es, Rs, ts, zs, Rd, td, zd, check_shape: bool, out_dtype=None):
+        typed = out_dtype is not None and isinstance(vs, torch.Tensor) and vs.dtype in _HALF
+        es, Rs, ts, zs, Rd, td, zd = _f32(es, Rs, ts, zs, Rd, td, zd)
+        vs = vs if typed else _f32(vs)
         if vs.shape[0] == 0:  # an empty frame shard (dp.shard_inputs with more ranks than frames): nothing to launch
-            out = vs.new_zeros((0, vs.shape[1]) + tuple(vs.shape[3:]))
+            out = vs.new_zeros((0, vs.shape[1]) + tuple(vs.shape[3:]), dtype=out_dtype or torch.float32)
             if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
                 # training: stay connected to the parameters (zero gradients), so this rank's loss.backward() runs and it
                 # enters the gradient all-reduce with the others instead of leaving them blocked in the collective
@@ -552,7 +775,7 @@ class _HotSliceRunner:
         train = ag.needs_grad(self, vs, es, Rs, ts, zs, Rd, td, zd)
         if not train and vs.shape[0] > self.max_frames_per_pass:
             step = int(self.max_frames_per_pass)
-            return torch.cat([self._run_python(*(t[i:i + step] for t in (vs, es, Rs, ts, zs, Rd, td, zd)), check_shape)
+            return torch.cat([self._run_python(*(t[i:i + step] for t in (vs, es, Rs, ts, zs, Rd, td, zd)), check_shape, out_dtype)
                               for i in range(0, vs.shape[0], step)], dim=0)
         main = torch.cuda.current_stream(vs.device)
         # training: one stream (autograd replays each op's backward on its forward stream; the overlap is an inference trick)
@@ -573,7 +796,7 @@ class _HotSliceRunner:
         early = side is not None and _C2D_EARLY  # dev switch: the old issue order, for same-box A/B runs
         if early:
             issue_c2d()
-        vc = apply_warping_field(vs, w_s2c)
+        vc = ops.warp_volume(vs, w_s2c) if typed else apply_warping_field(vs, w_s2c)   # (typed: K2 reads the half volume)
         if check_shape:
             assert vc.shape[1:] == (96, 16, 64, 64), f"Expected vc shape (_, 96, 16, 64, 64), got {vc.shape}"
         roi = None
@@ -595,6 +818,8 @@ class _HotSliceRunner:
         # apply_warping_field + torch.sum(dim=2) (model.py:1167-1171) in one kernel (K3)
         if train:
             return ag.WarpVolumeFn.apply(vc2d, w_c2d, True)
+        if out_dtype is not None:
+            return ops.warp_volume_dsum(vc2d, w_c2d, out_dtype=out_dtype)
         return ops.warp_volume_dsum(vc2d, w_c2d)
 
 

@@ -2,7 +2,9 @@
 
 PyTorch is used here only for device memory (tensor allocation through its caching allocator,
 which is stream-ordered) and for the current HIP stream.  Every function requires float32,
-contiguous CUDA tensors and raises otherwise — there is no eager/CPU fallback.
+contiguous CUDA tensors and raises otherwise — there is no eager/CPU fallback.  The exceptions are the
+boundary entries of half models ("model dtypes" below: K2's source, K3's output, the two casts), which
+also take fp16 / bf16.
 """
 from __future__ import annotations
 
@@ -37,6 +39,52 @@ def _req(t: torch.Tensor, name: str, dtype=torch.float32) -> torch.Tensor:
         raise RuntimeError(f"{name}: tensor lives on {t.device} but the current device is cuda:{torch.cuda.current_device()}; "
                            "call torch.cuda.set_device(tensor.device) (or use `with torch.cuda.device(...)`) first")
     return t if t.is_contiguous() else t.contiguous()
+
+
+# ------------------------------------------------------------------ model dtypes (include/mphip.h "model dtypes")
+# Boundary tensors of a .half() / .bfloat16() hot module are read and written in the model's dtype by the kernels themselves; activations
+# between kernels stay fp32.
+DTYPE_CODES = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}   # MPHIP_DTYPE_F32 / _F16 / _BF16
+
+
+def dtype_code(dtype: torch.dtype) -> int:
+    code = DTYPE_CODES.get(dtype)
+    if code is None:
+        raise RuntimeError(f"expected float32, float16 or bfloat16, got {dtype}")
+    return code
+
+
+def _req_typed(t: torch.Tensor, name: str) -> torch.Tensor:
+    """_req for a boundary tensor: fp32, fp16 or bf16."""
+    if isinstance(t, torch.Tensor) and t.dtype in DTYPE_CODES:
+        return _req(t, name, t.dtype)
+    return _req(t, name)
+
+
+def cast_to_f32_range(x: torch.Tensor) -> torch.Tensor:
+    """fp16/bf16 tensor -> fp32 copy carrying its range descriptor, in ONE pass (mphip_cast_to_f32_range): the input of an f16x3 conv
+    stack then costs what the cast alone costs.  An fp32 tensor is returned as is."""
+    x = _req_typed(x, "x")
+    if x.dtype == torch.float32:
+        return x
+    y = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+    if x.numel() == 0:
+        return y
+    rng = new_range(x.device)
+    _lib.check(_lib.load().mphip_cast_to_f32_range(_ptr(x), dtype_code(x.dtype), x.numel(), _ptr(y), _ptr(rng), _stream()),
+               "mphip_cast_to_f32_range")
+    return tag_range(y, rng)
+
+
+def cast_from_f32(x: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
+    """fp32 -> fp16/bf16, rounded to nearest even like torch's .to(dtype) (mphip_cast_from_f32).  fp32 -> fp32 returns x."""
+    x = _req(x, "x")
+    if dtype == torch.float32:
+        return x
+    y = torch.empty(x.shape, dtype=dtype, device=x.device)
+    if x.numel():
+        _lib.check(_lib.load().mphip_cast_from_f32(_ptr(x), _ptr(y), dtype_code(dtype), x.numel(), _stream()), "mphip_cast_from_f32")
+    return y
 
 
 # ------------------------------------------------------------------ range descriptors (f16x3 operand scales)
@@ -191,12 +239,13 @@ def warp_field_compose(theta: torch.Tensor, em: torch.Tensor, grid_size: int = 6
 
 # ------------------------------------------------------------------ K2 / K3
 def warp_volume(v: torch.Tensor, field: torch.Tensor, return_coords: bool = False):
-    v = _req(v, "v")
+    """K2.  v: fp32, fp16 or bf16 (widened on load: the result is bitwise K2 on v.float()); the output stays fp32."""
+    v = _req_typed(v, "v")
     field = _req(field, "warp_field")
     if v.dim() != 5 or field.dim() != 5 or field.shape[0] != v.shape[0] or field.shape[1] != 3:
         raise RuntimeError(f"warp_volume: bad shapes v={tuple(v.shape)} field={tuple(field.shape)}")
     b, c, d, h, w = v.shape
-    out = torch.empty_like(v)
+    out = torch.empty(v.shape, dtype=torch.float32, device=v.device)
     rng = new_range(v.device) if _RANGES_ENABLED else None
     coords = idx = None
     if return_coords:
@@ -206,28 +255,41 @@ def warp_volume(v: torch.Tensor, field: torch.Tensor, return_coords: bool = Fals
     lib = _lib.load()
     ws_bytes = lib.mphip_warp_workspace_bytes(b, d, h, w) + lib.mphip_warp_corner_image_bytes(b, c)   # (+ K2's optional corner image)
     ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=dev)
-    _lib.check(lib.mphip_warp_volume(_ptr(v), _ptr(field), _ptr(linspace_table(d, dev)), _ptr(linspace_table(h, dev)),
-                                     _ptr(linspace_table(w, dev)), _ptr(out), _ptr(coords), _ptr(idx), _ptr(rng), b, c, d, h, w,
-                                     field.shape[2], field.shape[3], field.shape[4], _ptr(ws), ws_bytes, _stream()),
-               "mphip_warp_volume")
+    if v.dtype == torch.float32:
+        _lib.check(lib.mphip_warp_volume(_ptr(v), _ptr(field), _ptr(linspace_table(d, dev)), _ptr(linspace_table(h, dev)),
+                                         _ptr(linspace_table(w, dev)), _ptr(out), _ptr(coords), _ptr(idx), _ptr(rng), b, c, d, h, w,
+                                         field.shape[2], field.shape[3], field.shape[4], _ptr(ws), ws_bytes, _stream()),
+                   "mphip_warp_volume")
+    else:   # (the workspace above includes the corner image: a typed K2 requires it)
+        _lib.check(lib.mphip_warp_volume_typed(_ptr(v), dtype_code(v.dtype), _ptr(field), _ptr(linspace_table(d, dev)),
+                                               _ptr(linspace_table(h, dev)), _ptr(linspace_table(w, dev)), _ptr(out), _ptr(coords), _ptr(idx),
+                                               _ptr(rng), b, c, d, h, w, field.shape[2], field.shape[3], field.shape[4], _ptr(ws), ws_bytes,
+                                               _stream()), "mphip_warp_volume_typed")
     tag_range(out, rng)
     return (out, coords, idx) if return_coords else out
 
 
-def warp_volume_dsum(v: torch.Tensor, field: torch.Tensor) -> torch.Tensor:
+def warp_volume_dsum(v: torch.Tensor, field: torch.Tensor, out_dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """K3.  out_dtype fp16/bf16: fp32 accumulation as always, the projection rounded once at the store (= the fp32 result .to(out_dtype))."""
     v = _req(v, "v")
     field = _req(field, "warp_field")
     if v.dim() != 5 or field.dim() != 5 or (field.shape[0] != v.shape[0] and v.shape[0] != 1) or field.shape[1] != 3:
         raise RuntimeError(f"warp_volume_dsum: bad shapes v={tuple(v.shape)} field={tuple(field.shape)}")
     _, c, d, h, w = v.shape
     b = field.shape[0]
-    out = torch.empty((b, c, h, w), dtype=torch.float32, device=v.device)
+    out = torch.empty((b, c, h, w), dtype=out_dtype, device=v.device)
     dev = v.device
     lib = _lib.load()
     ws_bytes = lib.mphip_warp_workspace_bytes(b, d, h, w)
     ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=dev)
     # one source volume for B driver fields (dp.cross_reenact): the kernel reads it in place, no expanded copy
-    fn = lib.mphip_warp_volume_dsum_shared if (v.shape[0] == 1 and b > 1) else lib.mphip_warp_volume_dsum
+    shared = v.shape[0] == 1 and b > 1
+    if out_dtype != torch.float32:
+        _lib.check(lib.mphip_warp_volume_dsum_typed(_ptr(v), int(shared), _ptr(field), _ptr(linspace_table(d, dev)), _ptr(linspace_table(h, dev)),
+                                                    _ptr(linspace_table(w, dev)), _ptr(out), dtype_code(out_dtype), b, c, d, h, w, field.shape[2],
+                                                    field.shape[3], field.shape[4], _ptr(ws), ws_bytes, _stream()), "mphip_warp_volume_dsum_typed")
+        return out
+    fn = lib.mphip_warp_volume_dsum_shared if shared else lib.mphip_warp_volume_dsum
     _lib.check(fn(_ptr(v), _ptr(field), _ptr(linspace_table(d, dev)), _ptr(linspace_table(h, dev)),
                                           _ptr(linspace_table(w, dev)), _ptr(out), b, c, d, h, w, field.shape[2],
                                           field.shape[3], field.shape[4], _ptr(ws), ws_bytes, _stream()),
@@ -368,7 +430,11 @@ class PackedConv:
                  header_from: Optional["PackedConv"] = None):
         """transposed: this object is the bwd-data conv of the conv whose weight is `weight` (Co/Ci swapped, taps
         flipped); the packing kernels read the original layout directly."""
-        weight = _req(weight.detach(), "conv weight")
+        weight = weight.detach()
+        if isinstance(weight, torch.Tensor) and weight.dtype in (torch.float16, torch.bfloat16):
+            weight = weight.float()   # a half model's conv: packed from the fp32 shadow (exact), i.e. bit-identical to its fp32 twin's pack
+            bias = None if bias is None else bias.detach().float()
+        weight = _req(weight, "conv weight")
         self.transposed = bool(transposed)
         self.header_from = header_from  # (transposed packs) the forward PackedConv of the same weight: shares its f16x3 scale
         co, ci = (weight.shape[1], weight.shape[0]) if transposed else (weight.shape[0], weight.shape[1])

@@ -109,11 +109,15 @@ class HotSlicePlan:
             ws = self._ws[key] = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
         return ws
 
-    def forward(self, vs, es, Rs, ts, zs, Rd, td, zd) -> torch.Tensor:
+    def forward(self, vs, es, Rs, ts, zs, Rd, td, zd, out_dtype: Optional[torch.dtype] = None) -> torch.Tensor:
+        """out_dtype None: fp32 in and out (mphip_hot_slice_forward).  Otherwise (a half model's twin, model.py): vs may be fp32 / fp16 /
+        bf16 and is read as it is, the result comes back in out_dtype (mphip_hot_slice_forward_typed; the bound parameters are fp32)."""
         if self.g3d_only:
             raise RuntimeError("HotSlicePlan(g3d_only=True) has no generators: use g3d()")
         c, d, h, w = self.dims
-        ins = [ops._req(t, n) for t, n in ((vs, "vs"), (es, "es"), (Rs, "Rs"), (ts, "ts"), (zs, "zs"), (Rd, "Rd"), (td, "td"), (zd, "zd"))]
+        typed = out_dtype is not None
+        ins = [(ops._req_typed(vs, "vs") if typed else ops._req(vs, "vs"))]
+        ins += [ops._req(t, n) for t, n in ((es, "es"), (Rs, "Rs"), (ts, "ts"), (zs, "zs"), (Rd, "Rd"), (td, "td"), (zd, "zd"))]
         b = ins[0].shape[0]
         if tuple(ins[0].shape) != (b, c, d, h, w):
             raise RuntimeError(f"HotSlicePlan.forward: vs {tuple(ins[0].shape)} does not match the plan's volume {(c, d, h, w)}")
@@ -123,12 +127,36 @@ class HotSlicePlan:
         self._sync_weights()
         nbytes = self.lib.mphip_hot_slice_workspace_bytes(self._handle, b)
         ws = self._workspace("slice", b, nbytes)
+        if typed:
+            out = torch.empty((b, c, h, w), dtype=out_dtype, device=self.device)
+            _lib.check(self.lib.mphip_hot_slice_forward_typed(self._handle, _P(ins[0].data_ptr()), ops.dtype_code(ins[0].dtype),
+                                                              *(_P(t.data_ptr()) for t in ins[1:]), _P(out.data_ptr()), ops.dtype_code(out_dtype), b,
+                                                              _P(ws.data_ptr()), ws.numel(), ops._stream()), "mphip_hot_slice_forward_typed")
+            return out
         out = torch.empty((b, c, h, w), dtype=torch.float32, device=self.device)
         _lib.check(self.lib.mphip_hot_slice_forward(self._handle, *(_P(t.data_ptr()) for t in ins), _P(out.data_ptr()), b, _P(ws.data_ptr()),
                                                     ws.numel(), ops._stream()), "mphip_hot_slice_forward")
         return out
 
     __call__ = forward
+
+    def g3d_typed(self, x: torch.Tensor, out_dtype: torch.dtype) -> torch.Tensor:
+        """G3d of a half model's twin: x fp32 / fp16 / bf16 (a typed x is widened with its range descriptor in one pass), y in out_dtype
+        (mphip_g3d_forward_typed)."""
+        c, d, h, w = self.dims
+        x = ops._req_typed(x, "x")
+        b = x.shape[0]
+        if tuple(x.shape) != (b, c, d, h, w):
+            raise RuntimeError(f"HotSlicePlan.g3d_typed: x {tuple(x.shape)} does not match the plan's volume {(c, d, h, w)}")
+        self._sync_weights()
+        xc, yc = ops.dtype_code(x.dtype), ops.dtype_code(out_dtype)
+        rng = ops.tensor_range(x) if xc == 0 else None
+        nbytes = self.lib.mphip_g3d_workspace_bytes_typed(self._handle, b, xc, yc)
+        ws = self._workspace("g3d_typed", b, nbytes)
+        y = torch.empty(x.shape, dtype=out_dtype, device=x.device)
+        _lib.check(self.lib.mphip_g3d_forward_typed(self._handle, _P(x.data_ptr()), xc, None if rng is None else _P(rng.data_ptr()), _P(y.data_ptr()),
+                                                    yc, b, _P(ws.data_ptr()), ws.numel(), ops._stream()), "mphip_g3d_forward_typed")
+        return y
 
     def g3d(self, x: torch.Tensor, x_range: Optional[torch.Tensor] = None) -> torch.Tensor:
         c, d, h, w = self.dims

@@ -44,6 +44,9 @@ def parse(argv=None):
     ap.add_argument("--fp16", action="store_true",
                     help="run the PyTorch-ROCm 2D modules under torch.autocast(float16) (the reference's policy, train.py:188); "
                          "the HIP hot path stays fp32-class")
+    ap.add_argument("--dtype", choices=("fp32", "fp16", "bf16"), default="fp32",
+                    help="model dtype: convert the whole generator with .half() / .bfloat16() (INTEGRATION.md \"Model dtypes\"); "
+                         "fp32 (default) runs it as loaded")
     ap.add_argument("--any-size", action="store_true", help="skip the reference's 512x512-only assert (model.py:1157)")
     ap.add_argument("--random-init", action="store_true", help="no checkpoint: random weights (plumbing tests)")
     ap.add_argument("--dry-run", action="store_true", help="resolve inputs and the launch plan, print them as JSON, exit")
@@ -150,6 +153,9 @@ def run(job: dict, args, rank: int, world: int) -> List[str]:
         if missing or unexpected:
             print(f"reenact: checkpoint loaded with {len(missing)} missing / {len(unexpected)} unexpected keys", file=sys.stderr)
     g = g.to(dev).eval()
+    dtype = {"fp32": torch.float32, "fp16": torch.float16, "bf16": torch.bfloat16}[args.dtype]
+    if dtype != torch.float32:
+        g = g.to(dtype)
     if args.channels_last:
         torch.backends.cudnn.benchmark = True   # MIOpen find mode: the NHWC kernels only pay off with it (gbase.channels_last_2d)
         g.channels_last_2d()
@@ -163,7 +169,7 @@ def run(job: dict, args, rank: int, world: int) -> List[str]:
     if not args.any_size and tuple(xs.shape[2:]) != (512, 512):
         raise SystemExit(f"reenact: the reference's Gbase only runs 512x512 frames (model.py:1157); got {tuple(xs.shape[2:])} "
                          "(pass --any-size to run other sizes)")
-    frames = g.reenact(xs.to(dev), xd.to(dev), chunk=args.chunk, fp16=args.fp16)   # this rank's shard; no collective
+    frames = g.reenact(xs.to(dev, dtype), xd.to(dev, dtype), chunk=args.chunk, fp16=args.fp16)   # this rank's shard; no collective
     written = []
     if job["output_tensor"]:
         torch.save({"begin": b, "end": e, "frames": frames.cpu()}, outputs[0])
