@@ -39,7 +39,7 @@ extern "C" {
 
 /* ABI version of this header.  Bumped whenever an exported signature or a packed layout changes; mphip_version() returns the
  * value the LIBRARY was built with — compare the two after dlopen (the ctypes binding does, and refuses a mismatch). */
-#define MPHIP_ABI_VERSION 15
+#define MPHIP_ABI_VERSION 16
 int mphip_version(void);
 /* hipGraph hygiene (ABI 13).  On ROCm 7.x a MEMSET node of a captured hipGraph is not reliably ordered with its neighbouring kernel nodes
  * (observed twice: stale f16x3 pack headers, r03; a training step's loss that kept its previous value, r04-r05 — ATen's multi-block
@@ -541,8 +541,16 @@ int mphip_f16x3_saturation_count(unsigned long long *count, int reset);
 
 /* Which kernel a full launch of mphip_conv3d_fwd takes for this shape: 0 = exact fp32 kernels / the k = 1 GEMM, 1 = the direct
  * f16x3 kernel on (td,8,8) tiles (2 = its (4,8,16)-tile form, removed in r05: never returned), 5 = the f16x3 kernel in the 1-D Winograd F(2,3) domain (2/3 of the MFMAs;
- * conv3d_f16x3_wino.hip).  For measurements and tests: results do not depend on it beyond fp32 rounding.                     */
+ * conv3d_f16x3_wino*.hip).  For measurements and tests: results do not depend on it beyond fp32 rounding.                     */
 int mphip_conv3d_kernel_variant(int N, int Ci, int Co, int D, int H, int W, int k, int precision);
+
+/* (ABI 16) Tests only: the whole decision the library takes for a precision-1 3x3x3 launch of this shape (roi != 0: a demand-driven
+ * one, mphip_conv3d_fwd_roi) under the calling thread's half-products flag.  out = { kernel, tile d, tile h, tile w, GroupNorm-partial
+ * rows per tile (0 = the kernel leaves none), accepts a demand-driven tile list, largest Ci with a fused input GroupNorm, splits, chunks
+ * per split, logical grid x, y, z }; kernel: 0 / 1 = the direct kernel on a (2,8,8) / (4,8,8) tile, 2-5 = the F(2,3) kernel on the
+ * lockstep, role-split, big-tile, two-frame schedule (all four answer 5 to mphip_conv3d_kernel_variant).  Returns 1, or 0 with out zeroed
+ * when the shape takes no such launch.  Host only: no GPU is touched.                                                           */
+int mphip_debug_conv3d_plan(int N, int Ci, int Co, int D, int H, int W, int roi, int out[12]);
 
 /* Measurement only (tools/mfma_sol.py, bench.py `roofline.sustained_peak`): the f16x3 convs' MFMA stream and nothing else — three
  * v_mfma_f32_32x32x16_f16 per product on random hi/lo fragments, 3 x 2 accumulator tiles per wave, 8 waves per workgroup; mode 1 reads

@@ -131,6 +131,7 @@ SIGNATURES = {
     "mphip_hot_slice_plan_destroy": (None, [_p]),
     "mphip_debug_mfma_sol": (_i, [_p, _i, _i, _i, _p]),
     "mphip_conv3d_kernel_variant": (_i, [_i] * 8),
+    "mphip_debug_conv3d_plan": (_i, [_i] * 7 + [ctypes.POINTER(ctypes.c_int)]),   # (ABI 16)
     "mphip_build_flags": (_i, []),
     "mphip_graph_memsets_to_kernels": (_i, [_p, ctypes.POINTER(ctypes.c_int)]),
     "mphip_graph_memset_nodes_left": (_i, [_p, ctypes.POINTER(ctypes.c_int)]),
@@ -145,7 +146,7 @@ _lib = None
 # The ABI version the SIGNATURES table above mirrors.  Checked against the library at load time, and against include/mphip.h by
 # tests/test_host.py — NOT read from the header at run time: a relocated / installed package ships libmphip.so without the repository's
 # include/ directory.
-EXPECTED_ABI_VERSION = 15
+EXPECTED_ABI_VERSION = 16
 
 
 def header_abi_version() -> int:

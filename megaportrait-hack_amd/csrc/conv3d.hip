@@ -472,12 +472,22 @@ static size_t packed_elems_f32(int Co, int Ci, int k) {
     return (size_t)k * k * k * ((Ci + 1) / 2 * 2) * ((Co + 31) / 32 * 32);
 }
 
+static bool conv_supported(const F16x3Switches &sw, int N, int Ci, int Co, int D, int H, int W, int k, int precision) {
+    if (N <= 0 || Ci <= 0 || Co <= 0 || D <= 0 || H <= 0 || W <= 0 || (k != 1 && k != 3)) return false;
+    if ((size_t)N * Ci * D * H * W * 4 >= 0x80000000ull) return false;
+    if (precision == 0) return true;
+    return precision == 1 && f16x3_supported(sw, N, Ci, Co, D, H, W, k);
+}
 extern "C" int mphip_conv3d_supported(int N, int Ci, int Co, int D, int H, int W, int k, int precision) {
-    if (N <= 0 || Ci <= 0 || Co <= 0 || D <= 0 || H <= 0 || W <= 0 || (k != 1 && k != 3)) return 0;
-    if ((size_t)N * Ci * D * H * W * 4 >= 0x80000000ull) return 0;
-    if (precision == 0) return 1;
-    if (precision == 1) return f16x3_supported(N, Ci, Co, D, H, W, k) ? 1 : 0;
-    return 0;
+    return conv_supported(f16x3_switches(), N, Ci, Co, D, H, W, k, precision) ? 1 : 0;
+}
+
+// The plan of a precision-1 3x3x3 launch for the calling thread's arithmetic policy; false: the launch is not one (other kernels take it).
+// Every entry point below builds it once and hands it to the size arithmetic.
+static bool f16x3_plan_for(const F16x3Switches &sw, F16x3Plan &fp, int N, int Ci, int Co, int D, int H, int W, int k, int precision, bool roi) {
+    if (precision != 1 || k != 3 || !conv_supported(sw, N, Ci, Co, D, H, W, k, precision)) return false;
+    fp = f16x3_plan(sw, N, Ci, Co, D, H, W, roi, conv_half_products());
+    return true;
 }
 
 extern "C" size_t mphip_packed_weight_bytes(int Co, int Ci, int k, int precision) {
@@ -626,30 +636,28 @@ extern "C" int mphip_pack_table_destroy(void *table) {
 
 constexpr size_t RANGE_BYTES = ((MPHIP_RANGE_FLOATS * sizeof(float) + 255) / 256) * 256;  // descriptor + padding: keeps what follows aligned
 
-static size_t conv_ws_bytes(int N, int Ci, int Co, int D, int H, int W, int k, int precision, bool roi);
-// GroupNorm statistics from the f16x3 3x3x3 kernel's epilogue (unsplit launches): bytes of its per-(tile, wave, channel) partials, 0 = the
-// separate statistics pass is used
-static size_t gn_epilogue_bytes(int N, int Ci, int Co, int D, int H, int W, int k, int precision, F16x3Plan *plan_out = nullptr) {
-    static const bool off = getenv("MPHIP_GN_EPILOGUE") && getenv("MPHIP_GN_EPILOGUE")[0] == '0';   // dev: same-box A/B
-    if (off || precision != 1 || k != 3 || !mphip_conv3d_supported(N, Ci, Co, D, H, W, k, precision)) return 0;
-    const F16x3Plan fp = f16x3_plan(N, Ci, Co, D, H, W, false);
-    if (fp.splits != 1) return 0;
-    if (fp.variant == 4 && D == 2) return 0;   // (the F(2,3) kernel's two-frame mode leaves no partials: separate statistics pass)
-    if (plan_out) *plan_out = fp;
-    return (size_t)fp.grid.x * f16x3_tile_waves(fp) * Co * 2 * sizeof(float) + 256;   // (+ the accumulator unscale behind the partials)
+// GroupNorm statistics from the f16x3 3x3x3 kernel's epilogue (unsplit launches): bytes of its per-(tile, row, channel) partials, 0 = the
+// separate statistics pass is used.  fp: the launch's plan, NULL when it is no f16x3 3x3x3 launch
+static size_t gn_epilogue_bytes(const F16x3Switches &sw, const F16x3Plan *fp, int Co) {
+    if (sw.gn_epilogue_off || !fp || fp->splits != 1 || fp->gn_rows == 0) return 0;
+    return (size_t)fp->grid.x * fp->gn_rows * Co * 2 * sizeof(float) + 256;   // (+ the accumulator unscale behind the partials)
 }
-static size_t conv_gn_bytes(int N, int Ci, int Co, int D, int H, int W, int k, int precision, int gn_groups) {
-    const size_t a = groupnorm_ws_bytes(N, Co, D * H * W, gn_groups), b = gn_epilogue_bytes(N, Ci, Co, D, H, W, k, precision);
+static size_t conv_gn_bytes(const F16x3Switches &sw, const F16x3Plan *fp, int N, int Co, int S, int gn_groups) {
+    const size_t a = groupnorm_ws_bytes(N, Co, S, gn_groups), b = gn_epilogue_bytes(sw, fp, Co);
     return a > b ? a : b;
 }
-extern "C" size_t mphip_conv3d_workspace_bytes(int N, int Ci, int Co, int D, int H, int W, int k, int precision) {
-    return conv_ws_bytes(N, Ci, Co, D, H, W, k, precision, false);
-}
-static size_t conv_ws_bytes(int N, int Ci, int Co, int D, int H, int W, int k, int precision, bool roi) {
-    if (!mphip_conv3d_supported(N, Ci, Co, D, H, W, k, precision)) return 0;
-    int splits = precision == 1 ? (k == 1 ? 1 : f16x3_plan(N, Ci, Co, D, H, W, roi).splits) : plan_conv(N, Ci, Co, D, H, W, k).splits;
+// (the shape is supported; fp as above)
+static size_t conv_ws_bytes(const F16x3Plan *fp, int N, int Ci, int Co, int D, int H, int W, int k, int precision) {
+    const int splits = fp ? fp->splits : precision == 1 ? 1 : plan_conv(N, Ci, Co, D, H, W, k).splits;
     // precision 1: room in front for the range descriptor the library computes itself when the caller passes none
     return (precision == 1 ? RANGE_BYTES : 0) + (splits > 1 ? (size_t)splits * N * Co * D * H * W * sizeof(float) : 0);
+}
+extern "C" size_t mphip_conv3d_workspace_bytes(int N, int Ci, int Co, int D, int H, int W, int k, int precision) {
+    const F16x3Switches sw = f16x3_switches();
+    if (!conv_supported(sw, N, Ci, Co, D, H, W, k, precision)) return 0;
+    F16x3Plan fp;
+    const bool f16k3 = f16x3_plan_for(sw, fp, N, Ci, Co, D, H, W, k, precision, false);
+    return conv_ws_bytes(f16k3 ? &fp : nullptr, N, Ci, Co, D, H, W, k, precision);
 }
 
 template <int KS, int MT, int NT, int WCO, bool SKIP>
@@ -717,18 +725,20 @@ static int conv3d_run(const float *x, const float *in_affine, int in_relu, const
     const size_t x_bytes = (size_t)N * Ci * D * H * W * sizeof(float);
     MPHIP_REQUIRE(x_bytes < 0x80000000ull, "conv3d_fwd: input of %zu bytes exceeds the 2 GiB buffer-addressing limit",
                   x_bytes);
-    MPHIP_REQUIRE(mphip_conv3d_supported(N, Ci, Co, D, H, W, k, precision),
+    const F16x3Switches sw = f16x3_switches();
+    MPHIP_REQUIRE(conv_supported(sw, N, Ci, Co, D, H, W, k, precision),
                   "conv3d_fwd: precision %d not available for this shape (query mphip_conv3d_supported)", precision);
     MPHIP_REQUIRE(!in_affine || precision == 1, "conv3d_fwd: the fused input GroupNorm needs the f16x3 kernel (precision 1)");
     hipStream_t s = (hipStream_t)stream;
     ConvPlan p{};
     F16x3Plan fp{};
+    const bool f16k3 = f16x3_plan_for(sw, fp, N, Ci, Co, D, H, W, k, precision, roi != nullptr);   // the one plan of this call
+    const F16x3Plan *fpp = f16k3 ? &fp : nullptr;
     int splits;
     if (precision == 1 && k == 1) {
         MPHIP_REQUIRE(!in_affine, "conv3d_fwd: the fused input GroupNorm is for the 3x3x3 f16x3 kernel");
         splits = 1;   // the k=1 GEMM kernel (conv3d_f16x3.hip): no split-K
     } else if (precision == 1) {
-        fp = f16x3_plan(N, Ci, Co, D, H, W, roi != nullptr);
         splits = fp.splits;
     } else {
         p = plan_conv(N, Ci, Co, D, H, W, k);
@@ -753,8 +763,9 @@ static int conv3d_run(const float *x, const float *in_affine, int in_relu, const
     workspace = workspace ? (char *)workspace + range_bytes : nullptr;
     workspace_bytes = workspace_bytes > range_bytes ? workspace_bytes - range_bytes : 0;
     const size_t slab_bytes = (splits > 1 && !keep_split) ? (size_t)splits * n_out * sizeof(float) : 0;
-    const size_t gn_bytes = gn_stats ? conv_gn_bytes(N, Ci, Co, D, H, W, k, precision, gn_groups) : 0;
-    const bool gn_in_epilogue = gn_stats && !roi && !keep_split && gn_epilogue_bytes(N, Ci, Co, D, H, W, k, precision) > 0;
+    // (no entry point passes both gn_stats and roi: the plan of a statistics launch is the full launch's)
+    const size_t gn_bytes = gn_stats ? conv_gn_bytes(sw, fpp, N, Co, D * H * W, gn_groups) : 0;
+    const bool gn_in_epilogue = gn_stats && !roi && !keep_split && gn_epilogue_bytes(sw, fpp, Co) > 0;
     if (slab_bytes + gn_bytes > 0) {
         if (!workspace || workspace_bytes < slab_bytes + gn_bytes) {
             set_error("conv3d_fwd: workspace %zu bytes < required %zu", workspace_bytes, slab_bytes + gn_bytes);
@@ -771,7 +782,7 @@ static int conv3d_run(const float *x, const float *in_affine, int in_relu, const
     const bool stamp = te0 && te1 && precision == 1 && k == 3;   // the f16x3 3x3x3 kernels carry the events themselves (kernel begin / end)
     if (te0 && !stamp) (void)hipEventRecord(te0, s);
     if (precision == 1 && k == 1) {
-        rc = f16x3_launch_k1(x, w_packed, bias, dst, N, Ci, Co, D * H * W, x_range, s);
+        rc = f16x3_launch_k1(sw, x, w_packed, bias, dst, N, Ci, Co, D * H * W, x_range, s);
     } else if (precision == 1) {
         int *tile_list = nullptr;
         if (roi) {   // the tile list lives at the END of the caller's workspace (mphip_conv3d_roi_workspace_bytes)
@@ -784,7 +795,7 @@ static int conv3d_run(const float *x, const float *in_affine, int in_relu, const
             // larger workspace whose size is not a multiple of 4 would misalign the int list — ADVICE r3)
             tile_list = (int *)((char *)workspace + (slab_bytes + gn_bytes + 255) / 256 * 256);
         }
-        rc = f16x3_launch(fp, x, w_packed, bias, dst, N, Ci, Co, D, H, W, in_affine, in_relu, x_range, s, roi, roi_frames, tile_list, roi_dilate,
+        rc = f16x3_launch(sw, fp, x, w_packed, bias, dst, N, Ci, Co, D, H, W, in_affine, in_relu, x_range, s, roi, roi_frames, tile_list, roi_dilate,
                           gn_in_epilogue ? (float *)gn_ws : nullptr, stamp ? te0 : nullptr, stamp ? te1 : nullptr);
     } else {
         const float *wf = (const float *)w_packed;
@@ -810,7 +821,7 @@ static int conv3d_run(const float *x, const float *in_affine, int in_relu, const
         if (rc) return rc;
     }
     if (gn_stats && gn_in_epilogue)
-        rc = groupnorm_stats_from_tiles((const float *)gn_ws, bias, y, gn_stats, N, Co, S, gn_groups, gn_eps, (int)fp.grid.x / N, f16x3_tile_waves(fp), s, gn_table);
+        rc = groupnorm_stats_from_tiles((const float *)gn_ws, bias, y, gn_stats, N, Co, S, gn_groups, gn_eps, (int)fp.grid.x / N, fp.gn_rows, s, gn_table);
     else if (gn_stats)
         rc = groupnorm_stats_launch(y, gn_stats, N, Co, S, gn_groups, gn_eps, gn_ws, s, gn_table);
     return rc;
@@ -825,16 +836,17 @@ extern "C" int mphip_conv3d_fwd(const float *x, const float *x_range, const void
 
 // Demand-driven conv (include/mphip.h): only the output tiles that intersect the consumer's sample boxes are computed.
 extern "C" int mphip_conv3d_roi_granule(int N, int Ci, int Co, int D, int H, int W, int k, int precision, int *tile_dhw) {
-    if (!tile_dhw || precision != 1 || k != 3 || !mphip_conv3d_supported(N, Ci, Co, D, H, W, k, 1)) return 0;
-    f16x3_tile_dims(f16x3_plan(N, Ci, Co, D, H, W, true), tile_dhw);
+    F16x3Plan fp;
+    if (!tile_dhw || !f16x3_plan_for(f16x3_switches(), fp, N, Ci, Co, D, H, W, k, precision, true)) return 0;
+    for (int i = 0; i < 3; ++i) tile_dhw[i] = fp.tile[i];
     return 1;
 }
 
 extern "C" size_t mphip_conv3d_roi_workspace_bytes(int N, int Ci, int Co, int D, int H, int W, int k, int precision) {
-    int dims[3];
-    if (!mphip_conv3d_roi_granule(N, Ci, Co, D, H, W, k, precision, dims)) return mphip_conv3d_workspace_bytes(N, Ci, Co, D, H, W, k, precision);
-    const size_t base = conv_ws_bytes(N, Ci, Co, D, H, W, k, precision, true);
-    const size_t tiles = (size_t)N * (D / dims[0]) * (H / dims[1]) * (W / dims[2]);
+    F16x3Plan fp;
+    if (!f16x3_plan_for(f16x3_switches(), fp, N, Ci, Co, D, H, W, k, precision, true)) return mphip_conv3d_workspace_bytes(N, Ci, Co, D, H, W, k, precision);
+    const size_t base = conv_ws_bytes(&fp, N, Ci, Co, D, H, W, k, precision);
+    const size_t tiles = (size_t)N * (D / fp.tile[0]) * (H / fp.tile[1]) * (W / fp.tile[2]);
     return (base + 255) / 256 * 256 + ((tiles + 1) * sizeof(int) + 255) / 256 * 256;
 }
 
@@ -850,17 +862,34 @@ extern "C" int mphip_conv3d_fwd_roi(const float *x, const float *x_range, const 
                       workspace_bytes, stream, tiled ? roi : nullptr, tiled ? roi_frames : 0);
 }
 
-// which kernel a (full) conv launch of this shape takes: 0 = exact fp32 kernels / k = 1 GEMM, 1 / 2 = the direct f16x3 kernel on
-// (td,8,8) / (4,8,16) tiles, 5 = the 1-D Winograd F(2,3) f16x3 kernel.  Measurement / tests only.
+// which kernel a (full) conv launch of this shape takes: 0 = exact fp32 kernels / k = 1 GEMM, 1 = a direct f16x3 kernel, 5 = an F(2,3)
+// f16x3 kernel on any schedule (mphip_debug_conv3d_plan tells them apart).  Measurement / tests only.
 extern "C" int mphip_conv3d_kernel_variant(int N, int Ci, int Co, int D, int H, int W, int k, int precision) {
-    if (precision != 1 || k != 3 || !mphip_conv3d_supported(N, Ci, Co, D, H, W, k, precision)) return 0;
-    return f16x3_plan(N, Ci, Co, D, H, W).variant + 1;
+    F16x3Plan fp;
+    if (!f16x3_plan_for(f16x3_switches(), fp, N, Ci, Co, D, H, W, k, precision, false)) return 0;
+    return f16x3_is_wino(fp.kernel) ? 5 : 1;
+}
+
+// the whole F16x3Plan of a precision-1 3x3x3 launch (roi != 0: a demand-driven one) under the calling thread's half-products flag:
+// out = {F16x3Kernel, tile d, h, w, GroupNorm-partial rows per tile, accepts a tile list, largest Ci of a fused input GroupNorm, splits,
+// chunks per split, grid x, y, z}.  0 (and zeros) when the shape takes no such launch.  Tests only.
+extern "C" int mphip_debug_conv3d_plan(int N, int Ci, int Co, int D, int H, int W, int roi, int out[12]) {
+    if (!out) return 0;
+    for (int i = 0; i < 12; ++i) out[i] = 0;
+    F16x3Plan fp;
+    if (!f16x3_plan_for(f16x3_switches(), fp, N, Ci, Co, D, H, W, 3, 1, roi != 0)) return 0;
+    const int v[12] = {(int)fp.kernel, fp.tile[0], fp.tile[1], fp.tile[2], fp.gn_rows, fp.tile_list, fp.max_gn_ci, fp.splits,
+                       fp.chunks_per_split, (int)fp.grid.x, (int)fp.grid.y, (int)fp.grid.z};
+    for (int i = 0; i < 12; ++i) out[i] = v[i];
+    return 1;
 }
 
 extern "C" int mphip_conv3d_splits(int N, int Ci, int Co, int D, int H, int W, int k, int precision) {
-    if (!mphip_conv3d_supported(N, Ci, Co, D, H, W, k, precision)) return 0;
-    if (precision == 1 && k == 1) return 1;
-    return precision == 1 ? f16x3_plan(N, Ci, Co, D, H, W).splits : plan_conv(N, Ci, Co, D, H, W, k).splits;
+    const F16x3Switches sw = f16x3_switches();
+    if (!conv_supported(sw, N, Ci, Co, D, H, W, k, precision)) return 0;
+    F16x3Plan fp;
+    if (f16x3_plan_for(sw, fp, N, Ci, Co, D, H, W, k, precision, false)) return fp.splits;
+    return precision == 1 ? 1 : plan_conv(N, Ci, Co, D, H, W, k).splits;
 }
 
 extern "C" int mphip_conv3d_fwd_split(const float *x, const float *x_range, const void *w_packed, const float *bias, float *out,
@@ -874,7 +903,11 @@ extern "C" int mphip_conv3d_fwd_split(const float *x, const float *x_range, cons
 extern "C" size_t mphip_conv3d_gn_workspace_bytes(int N, int Ci, int Co, int D, int H, int W, int k, int precision,
                                                   int gn_groups) {
     if (gn_groups <= 0 || Co % gn_groups) return 0;
-    return mphip_conv3d_workspace_bytes(N, Ci, Co, D, H, W, k, precision) + conv_gn_bytes(N, Ci, Co, D, H, W, k, precision, gn_groups);
+    const F16x3Switches sw = f16x3_switches();
+    F16x3Plan fp;
+    const F16x3Plan *fpp = f16x3_plan_for(sw, fp, N, Ci, Co, D, H, W, k, precision, false) ? &fp : nullptr;
+    const size_t ws = conv_supported(sw, N, Ci, Co, D, H, W, k, precision) ? conv_ws_bytes(fpp, N, Ci, Co, D, H, W, k, precision) : 0;
+    return ws + conv_gn_bytes(sw, fpp, N, Co, D * H * W, gn_groups);
 }
 
 extern "C" int mphip_conv3d_gn_fwd(const float *x, const float *x_range, const void *w_packed, const float *bias, float *y, float *gn_stats,
@@ -929,10 +962,10 @@ extern "C" int mphip_conv3d_bwd_data_roi(const float *dy, const void *wt_packed,
                                          size_t workspace_bytes, void *stream) {
     MPHIP_REQUIRE(roi && dx, "conv3d_bwd_data_roi: null pointer");
     MPHIP_REQUIRE(precision == 0 || dy_scale, "conv3d_bwd_data_roi: the f16x3 kernel needs the gradient scale of mphip_grad_prep");
-    int dims[3];
     // (a split-K launch reduces its slabs over EVERY voxel — garbage outside the listed tiles, where dx must be zero: such
     //  shapes, small volumes only, take the full evaluation)
-    const bool tiled = mphip_conv3d_roi_granule(N, Ci, Co, D, H, W, k, precision, dims) != 0 && f16x3_plan(N, Ci, Co, D, H, W, true).splits == 1;
+    F16x3Plan fp;
+    const bool tiled = f16x3_plan_for(f16x3_switches(), fp, N, Ci, Co, D, H, W, k, precision, true) && fp.splits == 1;
     if (tiled) zero_fill(dx, (size_t)N * Co * D * H * W * sizeof(float), (hipStream_t)stream);   // (16-byte multiple: W % 8 == 0 on this path)
     return conv3d_run(dy, nullptr, 0, precision == 1 ? dy_scale : nullptr, wt_packed, nullptr, dx, nullptr, 0, 0.0f, false, N, Ci, Co, D, H, W, k,
                       precision, workspace, workspace_bytes, stream, tiled ? roi : nullptr, 0, 1);

@@ -32,11 +32,6 @@
 namespace mphip {
 
 constexpr float X_SCALE = 16.0f;          // legacy fixed activation scale: only when a caller passes no range descriptor
-constexpr int F16X3_KC = 16;              // input channels per chunk = K of one MFMA
-constexpr int F16X3_TG = 3;               // taps per packed weight slab
-constexpr int F16X3_NG = 27 / F16X3_TG;   // slabs per 16-channel chunk
-constexpr int F16X3_COT = 96;             // output channels per workgroup (3 MFMA row tiles)
-constexpr int SLAB_HALFS = 2 * F16X3_TG * 2 * F16X3_COT * 8;  // [part][tap][kg][co][8] = 9216 halfs = 18432 B
 
 // Range: every operand tensor carries a range descriptor (mphip_common.h) and is scaled by its own power of two before the
 // split, so max|x|*scale < 2^14 and no finite value can leave the f16 range.  Whatever still does — a non-finite input, or a
@@ -750,7 +745,6 @@ conv3d_k3_f16x3_third_kernel(const float *__restrict__ x, const _Float16 *__rest
 // channels of 2 voxels straight from NCDHW (8 coalesced 128-byte row loads per tile), splits them in registers, and reads the
 // 6 weight fragments (hi/lo x 3 row tiles, 16 B per lane) from the packed slab in L2.  The fp32 gather kernel these convs ran
 // on before managed 27 % of the fp32 MFMA rate (0.25 ms per step for 0.65 % of the FLOPs).
-constexpr int K1_SLAB_HALFS = 2 * 2 * F16X3_COT * 8;   // [part][kg][co][8] = 3072 halfs = 6 KB per (co tile, chunk)
 
 __device__ __forceinline__ void f16x3_pack_k1_body(const float *__restrict__ w, _Float16 *__restrict__ out, const unsigned *hdr_in,
                                                    float *__restrict__ hdr_out, int Co, int Ci, int transposed, unsigned bid, unsigned nblk) {
@@ -911,92 +905,12 @@ conv3d_k1_f16x3_kernel(const float *__restrict__ x, const _Float16 *__restrict__
 }
 
 // waves sharing a tile (1 = none): small launches split the channel loop 4 or 8 ways
-static int f16x3_k1_ksplit(int N, int Ci, int Co, int DHW) {
-    const char *force = getenv("MPHIP_F16X3_K1_KS");   // dev: same-box A/B
-    if (force && (atoi(force) == 1 || atoi(force) == 4 || atoi(force) == 8)) return atoi(force);
+static int f16x3_k1_ksplit(const F16x3Switches &sw, int N, int Ci, int Co, int DHW) {
+    if (sw.k1_ks == 1 || sw.k1_ks == 4 || sw.k1_ks == 8) return sw.k1_ks;   // dev: same-box A/B
     const long wave_tiles = (long)N * DHW / 64 * (Co / F16X3_COT);
     const int nchunks = Ci / F16X3_KC;
     if (wave_tiles >= 1024 || nchunks < 8) return 1;   // (measured at B=8: 192->96 @8x32x32, 1024 wave tiles: 26 us unsplit, 31 us split 4)
     return (wave_tiles <= 512 && nchunks >= 16) ? 8 : 4;
-}
-
-static long f16x3_k1_min_voxels() {
-    const char *e = getenv("MPHIP_F16X3_K1_MIN");   // dev: threshold A/B
-    return e ? atol(e) : 1024;
-}
-
-bool f16x3_supported(int N, int Ci, int Co, int D, int H, int W, int k) {
-    if (k == 1)   // the k=1 GEMM kernel: whole 64-voxel wave tiles inside one sample, and enough of them to beat the split-K
-                  // fp32 gather kernel (measured: 1024 voxels 29 vs 32 us at B=8, but slower below — B=1 went 1.93 -> 2.11 ms)
-        return Ci % F16X3_KC == 0 && Co % F16X3_COT == 0 && ((long)D * H * W) % 64 == 0 && (long)N * D * H * W >= f16x3_k1_min_voxels() &&
-               (size_t)N * Ci * D * H * W * 4 < 0x80000000ull;
-    return k == 3 && Ci % F16X3_KC == 0 && Co % F16X3_COT == 0 && H % 8 == 0 && W % 8 == 0 && D % 2 == 0 &&
-           (size_t)N * Ci * D * H * W * 4 < 0x80000000ull;
-}
-
-size_t f16x3_packed_bytes_k1(int Co, int Ci) {
-    return 16 + (size_t)(Co / F16X3_COT) * (Ci / F16X3_KC) * K1_SLAB_HALFS * sizeof(_Float16);
-}
-
-static size_t f16x3_direct_bytes(int Co, int Ci) {   // header + the direct kernel's slabs
-    return 16 + (size_t)(Co / F16X3_COT) * (Ci / F16X3_KC) * F16X3_NG * SLAB_HALFS * sizeof(_Float16);
-}
-
-size_t f16x3_packed_bytes(int Co, int Ci) {   // ... + the transformed-domain slabs of the layers that can take that kernel
-    return f16x3_direct_bytes(Co, Ci) + f16x3_wino_packed_bytes(Co, Ci);
-}
-
-F16x3Plan f16x3_plan(int N, int Ci, int Co, int D, int H, int W, bool roi) {
-    F16x3Plan p;
-    p.td = D % 4 == 0 ? 4 : 2;
-    // variant: 0 = the direct kernels ((td,8,8) tile, 256 / 128 voxels per workgroup); 4 = the F(2,3) kernel.  (Until r05 a variant 1 —
-    // a (4,8,16) tile, 512 voxels per workgroup, the r02-r03 kernel of the chip-filling launches — was kept as the fallback of
-    // MPHIP_WINOGRAD=0; it was the one hot instantiation with scratch (248-256 B) and every launch it could take is variant 4's: removed.)
-    const char *force = getenv("MPHIP_F16X3_TILE");   // dev knob, read per call: "0" = direct kernels only (tools/sweep_conv_plans.py)
-    const int cot = Co / F16X3_COT;
-    p.variant = 0;
-    (void)roi;
-    // variant 4: the 1-D Winograd F(2,3) kernel (conv3d_f16x3_wino.hip; (4,8,8) tile, 2/3 of the MFMAs) on launches that fill the chip
-    // (demand-driven launches follow the full launch's choice, so that the tiles they compute carry the same bits)
-    // (depth-2 volumes: the F(2,3) kernel's two-frame mode — not for demand-driven launches)
-    if (!force && !(roi && D == 2) && f16x3_wino_usable(N, Ci, Co, D, H, W)) p.variant = 4;
-    const long tiles = p.variant == 4 ? f16x3_wino_tiles(N, D, H, W) : (long)N * (D / p.td) * (H / 8) * (W / 8);
-    const int nchunks = Ci / F16X3_KC;
-    // split-K only when the launch cannot give every CU a workgroup (each split adds a slab write + a reduce pass): the largest
-    // whole-chunk split that still fits the chip in ONE round of resident workgroups (one per CU; two for the 4-wave (2,8,8) kernel).
-    // r03 sweep (tools/sweep_conv_plans.py): a second round costs more than it hides (B=8, 384->192 @4x16x16: 256 workgroups 98 us,
-    // 512 106 us), and below that one chunk per workgroup beats three (B=1, 768->384 @2x8x8: 16 splits 41 us, 48 splits 24 us — the
-    // launch is one workgroup's serial chain of chunks).
-    int sp = 1;
-    {
-        const long base = tiles * cot, slots = (p.variant == 0 && p.td == 2) ? 512 : 256;
-        static const char *old_rule = getenv("MPHIP_F16X3_OLD_SPLITS");   // dev: same-box A/B against the r02 rule
-        if (old_rule) {
-            if (base < 256)
-                while (base * sp < 512 && nchunks / (sp * 2) >= 3) sp *= 2;
-        } else if (base < slots) {
-            for (int dv = 2; dv <= nchunks; ++dv)
-                if (nchunks % dv == 0 && base * dv <= slots) sp = dv;
-        }
-    }
-    const char *force_sp = getenv("MPHIP_F16X3_SPLITS");   // dev: planner sweep (tools/sweep_conv_plans.py)
-    if (force_sp && atoi(force_sp) > 0 && nchunks % atoi(force_sp) == 0) sp = atoi(force_sp);   // (whole chunks per split only)
-    if (p.variant == 4) sp = f16x3_wino_splits(N, Ci, Co, D, H, W);
-    p.splits = sp;
-    p.chunks_per_split = (nchunks + sp - 1) / sp;
-    p.grid = dim3((unsigned)tiles, Co / F16X3_COT, sp);
-    return p;
-}
-
-int f16x3_tile_waves(const F16x3Plan &p) {   // GroupNorm-partial rows per tile of the kernel variant f16x3_launch picks (= its waves;
-                                              // the Winograd kernel leaves one row per plane pair)
-    return p.variant == 4 ? 2 : p.td == 4 ? 8 : 4;
-}
-
-void f16x3_tile_dims(const F16x3Plan &p, int dims[3]) {   // output tile (d,h,w) of the kernel variant f16x3_launch picks
-    dims[0] = p.variant == 4 ? 4 : p.td;
-    dims[1] = 8;
-    dims[2] = 8;
 }
 
 int f16x3_pack(const float *w, void *out, int Co, int Ci, int k, int transposed, const void *header_from, hipStream_t s) {
@@ -1080,17 +994,16 @@ int f16x3_pack_many(const PackJob *jobs, PackSel absmax, PackSel k3, PackSel k1,
     return check_launch("pack_conv_weights(f16x3)");
 }
 
-int f16x3_launch_k1(const float *x, const void *wpacked, const float *bias, float *dst, int N, int Ci, int Co, int DHW,
-                    const float *x_range, hipStream_t s) {
+int f16x3_launch_k1(const F16x3Switches &sw, const float *x, const void *wpacked, const float *bias, float *dst, int N, int Ci, int Co,
+                    int DHW, const float *x_range, hipStream_t s) {
     const float *hdr = (const float *)wpacked;
     const _Float16 *slabs = (const _Float16 *)((const char *)wpacked + 16);
     const unsigned xb = (unsigned)((size_t)N * Ci * DHW * 4);
     const long waves = (long)N * DHW / 64;
-    const int ks = f16x3_k1_ksplit(N, Ci, Co, DHW);
+    const int ks = f16x3_k1_ksplit(sw, N, Ci, Co, DHW);
     // a launch with ONE wave per SIMD (64-voxel wave tiles) runs 32-voxel tiles on twice the waves (192->96 @8x32x32, B=8: 29 -> 25 us; with two
     // waves per SIMD already — 96->192 — it is slower, 26 -> 31 us: the weight fragments are re-read per wave)
-    static const char *nt_env = getenv("MPHIP_F16X3_K1_NT");   // dev: same-box A/B (1 / 2 forces)
-    const bool nt1 = ks == 1 && (nt_env ? atoi(nt_env) == 1 : waves * (Co / F16X3_COT) <= 1024);
+    const bool nt1 = ks == 1 && (sw.k1_nt >= 0 ? sw.k1_nt == 1 : waves * (Co / F16X3_COT) <= 1024);   // (switch: same-box A/B, 1 / 2 forces)
     if (ks == 8)
         hipLaunchKernelGGL(conv3d_k1_f16x3_kernel<8>, dim3((unsigned)waves, Co / F16X3_COT), dim3(512), 0, s, x, slabs, hdr, bias, dst, N, Ci,
                            Co, DHW, xb, x_range);
@@ -1106,47 +1019,38 @@ int f16x3_launch_k1(const float *x, const void *wpacked, const float *bias, floa
     return check_launch("conv3d_fwd(f16x3, k=1)");
 }
 
-int f16x3_launch(const F16x3Plan &p, const float *x, const void *wpacked, const float *bias, float *dst, int N, int Ci,
+int f16x3_launch(const F16x3Switches &sw, const F16x3Plan &p, const float *x, const void *wpacked, const float *bias, float *dst, int N, int Ci,
                  int Co, int D, int H, int W, const float *in_affine, int in_relu, const float *x_scale, hipStream_t s, const int *roi,
                  int roi_frames, int *tile_list, int roi_dilate, float *gn_part, hipEvent_t t0, hipEvent_t t1) {
-    if (in_affine && Ci > 768) {
-        set_error("conv3d_fwd(f16x3): fused input GroupNorm supports Ci <= 768 (got %d)", Ci);
+    const bool wino = f16x3_is_wino(p.kernel);
+    if (in_affine && Ci > p.max_gn_ci) {
+        set_error("conv3d_fwd(f16x3%s): fused input GroupNorm supports Ci <= %d (got %d)", wino ? ", F(2,3)" : "", p.max_gn_ci, Ci);
+        return MPHIP_EINVAL;
+    }
+    if ((roi && !p.tile_list) || (gn_part && !p.gn_rows)) {
+        set_error("conv3d_fwd(f16x3, F(2,3), D = 2): no demand-driven tile list / GroupNorm partials in the two-frame mode");
         return MPHIP_EINVAL;
     }
     const float *hdr = (const float *)wpacked;
-    const _Float16 *slabs = (const _Float16 *)((const char *)wpacked + 16);
+    const _Float16 *slabs = (const _Float16 *)((const char *)wpacked + (wino ? f16x3_direct_bytes(Co, Ci) : 16));
     const unsigned xb = (unsigned)((size_t)N * Ci * D * H * W * 4);
     if (roi) {   // demand-driven: boxes -> the list of tiles they touch (1 + tiles ints of caller workspace); the kernel gets the LIST
-        int dims[3];
-        f16x3_tile_dims(p, dims);
         // (r03: extra workgroups of this launch pre-reading the packed weights into every XCD's L2 changed nothing — a demand-driven
         //  tile is one CU's MFMA work, 2592 K-steps x 9 MFMAs per wave, not a chain of L2 misses)
-        hipLaunchKernelGGL(roi_tile_list_kernel, dim3(1), dim3(1024), 0, s, roi, roi_frames, (int)p.grid.x, D, H, W, dims[0], dims[1], dims[2],
+        hipLaunchKernelGGL(roi_tile_list_kernel, dim3(1), dim3(1024), 0, s, roi, roi_frames, (int)p.grid.x, D, H, W, p.tile[0], p.tile[1], p.tile[2],
                            roi_dilate, tile_list);
         roi = tile_list;
     }
-    if (p.variant == 4) {   // the 1-D Winograd F(2,3) kernel (full launches and demand-driven ones alike: a listed tile carries the full launch's bits)
-        if (in_affine && Ci > 384 && D != 2) {
-            set_error("conv3d_fwd(f16x3, F(2,3)): fused input GroupNorm supports Ci <= 384 (got %d)", Ci);
-            return MPHIP_EINVAL;
-        }
-        return f16x3_wino_launch(x, (const char *)wpacked + f16x3_direct_bytes(Co, Ci), hdr, bias, dst, N, Ci, Co, D, H, W, p.splits,
-                                 in_affine, in_relu, x_scale, s, roi, gn_part, t0, t1);
-    }
-    // persistent grid: as many workgroups as the chip runs at once (LDS: one per CU for the two big variants, two for
-    // the (2,8,8) one), each walking its share of the tiles
+    // persistent grid: as many workgroups as the chip runs at once (p.wgs_per_cu per CU), each walking its share of the tiles.
+    // "thirds" (a third of a (4,8,8) tile's output channels per workgroup) is the one choice left to the launch: only it knows gn_part
     const int tiles_total = (int)p.grid.x;
-    const int per_cu = p.td == 4 ? 1 : 2;
-    static const bool thirds_off = getenv("MPHIP_ROI_THIRDS") && getenv("MPHIP_ROI_THIRDS")[0] == '0';   // dev: same-box A/B
-    const bool thirds = roi && p.variant == 0 && p.td == 4 && !gn_part && !thirds_off;
+    const bool thirds = roi && p.kernel == F16X3_DIRECT_4 && !gn_part && !sw.thirds_off;
     const long others = (long)p.grid.y * (thirds ? 3 : 1) * p.grid.z;
-    static const char *cus_s = getenv("MPHIP_CONV_CUS");   // dev: persistent grid size (leave CUs to another batch's small kernels)
-    const long cus = cus_s ? atol(cus_s) : 256;
-    long gx = (cus * per_cu + others - 1) / others;
+    long gx = (sw.conv_cus * p.wgs_per_cu + others - 1) / others;
     if (gx < 1) gx = 1;
-    if (gx > tiles_total || getenv("MPHIP_F16X3_NO_PERSIST")) gx = tiles_total;
-    dim3 grid((unsigned)gx, p.grid.y * (thirds ? 3 : 1), p.grid.z);
-    static const int xcd_on = !(getenv("MPHIP_F16X3_XCD") && getenv("MPHIP_F16X3_XCD")[0] == '0');  // dev switch for same-box A/B
+    if (gx > tiles_total || (sw.no_persist && !wino)) gx = tiles_total;
+    const dim3 grid((unsigned)gx, p.grid.y * (thirds ? 3 : 1), p.grid.z);
+    const int xcd_on = sw.xcd_on, cps = p.chunks_per_split;
     // (two-slab groups for the 512-voxel tile — 5 instead of 9 barriers per chunk, 147 KB of LDS — were tried: the
     //  compiler spills 188 registers in that instantiation and it runs 35 % slower)
     // (t0, t1: the measurement hook's events ride on the kernel command itself — hipExtLaunchKernelGGL stamps them with the kernel's own
@@ -1155,16 +1059,37 @@ int f16x3_launch(const F16x3Plan &p, const float *x, const void *wpacked, const 
     {                                                                                                                            \
         if (t0 && t1)                                                                                                            \
             hipExtLaunchKernelGGL(kern_, grid, dim3(block_), 0, s, t0, t1, 0, x, slabs, hdr, bias, dst, N, Ci, Co, D, H, W,      \
-                                  p.chunks_per_split, xb, in_affine, in_relu, x_scale, tiles_total, xcd_on, roi, roi_frames, gn_part); \
+                                  cps, xb, in_affine, in_relu, x_scale, tiles_total, xcd_on, roi, roi_frames, gn_part);          \
         else                                                                                                                     \
-            hipLaunchKernelGGL(kern_, grid, dim3(block_), 0, s, x, slabs, hdr, bias, dst, N, Ci, Co, D, H, W, p.chunks_per_split, xb, \
+            hipLaunchKernelGGL(kern_, grid, dim3(block_), 0, s, x, slabs, hdr, bias, dst, N, Ci, Co, D, H, W, cps, xb,           \
                                in_affine, in_relu, x_scale, tiles_total, xcd_on, roi, roi_frames, gn_part);                      \
     }
-    if (p.td == 4 && thirds) F16X3_LAUNCH((conv3d_k3_f16x3_third_kernel<4, 8, 8, 8, 3>), 512)
-    else if (p.td == 4) F16X3_LAUNCH((conv3d_k3_f16x3_kernel<4, 8, 8, 8, 3>), 512)
-    else F16X3_LAUNCH((conv3d_k3_f16x3_kernel<2, 8, 8, 4, 1>), 256)
+#define F16X3_WINO_ARGS grid, s, t0, t1, x, slabs, hdr, bias, dst, N, Ci, Co, D, H, W, cps, xb, in_affine, in_relu, x_scale, tiles_total, xcd_on, roi, gn_part
+    switch (p.kernel) {   // (full launches and demand-driven ones alike: a listed tile carries the full launch's bits)
+        case F16X3_DIRECT_4:
+            if (thirds) F16X3_LAUNCH((conv3d_k3_f16x3_third_kernel<4, 8, 8, 8, 3>), 512)
+            else F16X3_LAUNCH((conv3d_k3_f16x3_kernel<4, 8, 8, 8, 3>), 512)
+            return check_launch("conv3d_fwd(f16x3)");
+        case F16X3_DIRECT_2:
+            F16X3_LAUNCH((conv3d_k3_f16x3_kernel<2, 8, 8, 4, 1>), 256)
+            return check_launch("conv3d_fwd(f16x3)");
+        case F16X3_WINO_LOCKSTEP:
+            f16x3_wino_launch(F16X3_WINO_ARGS);
+            return check_launch("conv3d_fwd(f16x3, F(2,3))");
+        case F16X3_WINO_ROLE_SPLIT:   // same arithmetic, same packed weights, same tile
+            f16x3_wino_pp_launch(F16X3_WINO_ARGS, p.one_product);
+            return check_launch("conv3d_fwd(f16x3, F(2,3), role-split)");
+        case F16X3_WINO_BIG_TILE:
+            f16x3_wino_bt_launch(F16X3_WINO_ARGS, false);
+            return check_launch("conv3d_fwd(f16x3, F(2,3), big tile)");
+        case F16X3_WINO_TWO_FRAME:
+            f16x3_wino_bt_launch(F16X3_WINO_ARGS, true);
+            return check_launch("conv3d_fwd(f16x3, F(2,3), big tile, two frames)");
+    }
+#undef F16X3_WINO_ARGS
 #undef F16X3_LAUNCH
-    return check_launch("conv3d_fwd(f16x3)");
+    set_error("conv3d_fwd(f16x3): plan names no kernel");
+    return MPHIP_EINVAL;
 }
 
 }  // namespace mphip
@@ -1194,11 +1119,13 @@ extern "C" int mphip_f16x3_saturation_count(unsigned long long *count, int reset
             return MPHIP_ELAUNCH;
         }
     }
-    unsigned long long wn = 0;   // the transformed-domain kernel keeps its own counter (separate translation unit)
-    if (mphip::f16x3_wino_saturation(&wn, reset) != 0) {
-        mphip::set_error("f16x3_saturation_count: hipMemcpyFromSymbol failed");
-        return MPHIP_ELAUNCH;
+    for (auto other : {mphip::f16x3_wino_saturation, mphip::f16x3_wino_pp_saturation, mphip::f16x3_wino_bt_saturation}) {
+        unsigned long long wn = 0;   // the transformed-domain kernels keep their own counters (separate translation units)
+        if (other(&wn, reset) != 0) {
+            mphip::set_error("f16x3_saturation_count: hipMemcpyFromSymbol failed");
+            return MPHIP_ELAUNCH;
+        }
+        *count += wn;
     }
-    *count += wn;
     return MPHIP_OK;
 }

@@ -29,6 +29,10 @@
 //   * output transform: the four positions of a pair live in four waves.  After the last chunk every wave parks three quarters
 //     of its accumulators in the (now dead) X region, one 32-channel row tile per round, and finishes the quarter it keeps:
 //     y0/y1, bias, the GroupNorm statistics partials of its channels, 8-byte stores.
+//
+// This file holds the lockstep kernel (r04's schedule, today the MPHIP_WINO_PP=0 A/B reference) and its launcher, nothing else: which
+// kernel a launch takes, the split-K factor and the size of the slabs are decided in conv3d_f16x3_plan.hip; the layout constants the
+// packer and the planner share (WN_KC, WN_COT, WN_SLAB_HALFS, ...) are in mphip_conv.h.
 #include <stdlib.h>
 
 #include <hip/hip_ext.h>
@@ -39,20 +43,14 @@
 
 namespace mphip {
 
-constexpr int WN_KC = 16;                                  // input channels per chunk = K of one MFMA
-constexpr int WN_COT = 96;                                 // output channels per workgroup (3 MFMA row tiles)
-constexpr int WN_NG = 9;                                   // (kd,kh) slabs per chunk
 constexpr int WN_RING = 4;                                 // slabs resident in LDS
-constexpr int WN_SLAB_HALFS = 2 * 4 * 2 * WN_COT * 8;      // [part][position][kg][co][8] = 12288 halfs = 24576 B
 constexpr int WN_PART_HALFS = WN_SLAB_HALFS / 2;
-constexpr int WN_TD = 4, WN_TH = 8, WN_TW = 8;             // output tile
 constexpr int WN_HD = WN_TD + 2, WN_HH = WN_TH + 2;
 constexpr int WN_ROWS = WN_HD * WN_HH;                     // 60 halo rows
 constexpr int WN_XBLK = WN_ROWS * 4 * 8 + 16;              // halfs per (part, position, kg) block: 240 (row, pair) slots x 8 channels
                                                            // + 32 B so that the two k-groups of a staging write sit 8 banks apart
 constexpr int WN_XPART = 4 * 2 * WN_XBLK;                  // halfs per part (hi or lo)
 constexpr int WN_X_HALFS = 2 * WN_XPART;                   // 30976 halfs = 61952 B
-constexpr int WN_AFF_CI = 384;                             // fused input GroupNorm table: Ci <= 384 (LDS: 98304 + 61952 + 3072 B + the range fold's 68)
 constexpr int WN_XLOADS = 8;                               // vector-memory instructions of one halo prefetch (per wave)
 
 // Weight layout (written by f16x3_pack_kernel in conv3d_f16x3.hip, from the tile it stages for the direct slabs):
@@ -589,13 +587,8 @@ conv3d_k3_f16x3_wino_kernel(const float *__restrict__ x, const _Float16 *__restr
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------------
-int f16x3_wino_saturation(unsigned long long *count, int reset) {   // (mphip_f16x3_saturation_count adds it to the direct kernels' counter)
+int f16x3_wino_saturation(unsigned long long *count, int reset) {   // (mphip_f16x3_saturation_count adds it to the other kernels' counters)
     if (hipMemcpyFromSymbol(count, HIP_SYMBOL(g_f16x3_wino_saturated), sizeof(unsigned long long)) != hipSuccess) return -1;
-    unsigned long long pp = 0;   // (the role-split kernel keeps its own counter: separate translation unit)
-    if (f16x3_wino_pp_saturation(&pp, reset) != 0) return -1;
-    *count += pp;
-    if (f16x3_wino_bt_saturation(&pp, reset) != 0) return -1;
-    *count += pp;
     if (reset) {
         const unsigned long long z = 0;
         if (hipMemcpyToSymbol(HIP_SYMBOL(g_f16x3_wino_saturated), &z, sizeof(z)) != hipSuccess) return -1;
@@ -603,99 +596,16 @@ int f16x3_wino_saturation(unsigned long long *count, int reset) {   // (mphip_f1
     return 0;
 }
 
-static bool wino_enabled() {   // dev: same-box A/B against the direct kernel (read per call: tests flip it in-process; packs always carry the slabs)
-    const char *e = getenv("MPHIP_WINOGRAD");
-    return !(e && e[0] == '0');
-}
-
-// layers that can ever take the transformed-domain kernel get its slabs behind the direct pack (a weight tensor does not know the
-// volume it will meet): Ci <= 384 covers G3d's levels 0-2 and Eapp's 3-D tail, +133 % pack bytes on <= 16 MB tensors
-size_t f16x3_wino_packed_bytes(int Co, int Ci) {
-    static const bool nopack = getenv("MPHIP_WINOGRAD_PACK") && getenv("MPHIP_WINOGRAD_PACK")[0] == '0';   // dev: bisecting (process-wide: set before the first pack)
-    if (nopack) return 0;
-    // (Ci <= 768: G3d's 2x8x8 level — 384 / 768 channels — takes the two-frame mode of the big-tile kernel, r06; the LDS table of the fused
-    //  input GroupNorm limits the 4-plane kernels to Ci <= 384 only when the norm is fused, checked at launch)
-    if (Ci % WN_KC || Co % WN_COT || Ci > 2 * WN_AFF_CI) return 0;
-    return (size_t)(Co / WN_COT) * (Ci / WN_KC) * WN_NG * WN_SLAB_HALFS * sizeof(_Float16);
-}
-
-// split-K factor of a launch (whole chunks only): the largest divisor of the chunk count that keeps the launch inside ONE round of
-// resident workgroups (one per CU) — the direct kernel's r03 rule
-// tiles of a launch: 4 x 8 x 8 voxels of one frame, or — depth-2 volumes, conv3d_f16x3_wino_bt.hip's D2 mode — 2 x 8 x 8 voxels of TWO frames
-long f16x3_wino_tiles(int N, int D, int H, int W) {
-    return D == 2 ? (long)((N + 1) / 2) * (H / WN_TH) * (W / WN_TW) : (long)N * (D / WN_TD) * (H / WN_TH) * (W / WN_TW);
-}
-
-int f16x3_wino_splits(int N, int Ci, int Co, int D, int H, int W) {
-    const long base = f16x3_wino_tiles(N, D, H, W) * (Co / WN_COT);
-    const int nchunks = Ci / WN_KC;
-    int sp = 1;
-    if (base < 256)
-        for (int dv = 2; dv <= nchunks; ++dv)
-            if (nchunks % dv == 0 && base * dv <= 256) sp = dv;
-    return sp;
-}
-
-bool f16x3_wino_usable(int N, int Ci, int Co, int D, int H, int W) {
-    const char *d2_env = getenv("MPHIP_WINOGRAD_D2");   // dev: same-box A/B of the two-frame mode against the direct kernel (read per call: tests flip it in-process)
-    const bool d2_off = d2_env && d2_env[0] == '0';
-    if (!wino_enabled() || f16x3_wino_packed_bytes(Co, Ci) == 0 || (D % WN_TD && (D != 2 || d2_off)) || H % WN_TH || W % WN_TW) return false;
-    // (two frames per tile: a single frame leaves half of every tile empty — B = 1, 768 -> 768: 31.6 us against the direct kernel's 28.8;
-    //  from B = 4, the training shard, the mode wins: tools/d2_check.py)
-    if (D == 2 && N < 4 && !getenv("MPHIP_WINOGRAD_MIN_TILES")) return false;
-    if (D != 2 && Ci > WN_AFF_CI) return false;   // (the 4-plane kernels keep r05's range: their launches may fuse the input GroupNorm through the LDS table)
-    // one workgroup per CU, ~1 us per (kd,kh) slab: worth it when the launch (with its split-K factor) fills the chip and the direct
-    // kernel's advantage — a 512-voxel tile's weight economy, thirds of a tile per CU — does not apply (measured: tools/wino_check.py)
-    const long tiles = f16x3_wino_tiles(N, D, H, W);
-    const char *min_s = getenv("MPHIP_WINOGRAD_MIN_TILES");   // dev: threshold sweep
-    const long min_wgs = min_s ? atol(min_s) : 192;
-    return tiles * (Co / WN_COT) * f16x3_wino_splits(N, Ci, Co, D, H, W) >= min_wgs;
-}
-
-int f16x3_wino_launch(const float *x, const void *slabs, const float *hdr, const float *bias, float *dst, int N, int Ci, int Co, int D,
-                      int H, int W, int splits, const float *in_affine, int in_relu, const float *x_range, hipStream_t s, const int *tile_list,
-                      float *gn_part, hipEvent_t t0, hipEvent_t t1) {
-    const int tiles = (int)f16x3_wino_tiles(N, D, H, W), cots = Co / WN_COT;
-    static const char *cus_s = getenv("MPHIP_CONV_CUS");   // dev: persistent grid size (leave CUs to another batch's small kernels)
-    const long cus = cus_s ? atol(cus_s) : 256;
-    long gx = (cus + cots * splits - 1) / (cots * splits);   // persistent: one workgroup per CU
-    if (gx > tiles) gx = tiles;
-    const dim3 grid((unsigned)gx, (unsigned)cots, (unsigned)splits);
-    const int cps = (Ci / WN_KC + splits - 1) / splits;
-    const unsigned xb = (unsigned)((size_t)N * Ci * D * H * W * 4);
-    static const int xcd_on = !(getenv("MPHIP_F16X3_XCD") && getenv("MPHIP_F16X3_XCD")[0] == '0');
-    const char *pp_env = getenv("MPHIP_WINO_PP");   // dev: same-box A/B against the lockstep schedule (read per call: tools flip it in-process)
-    const bool pp_on = !(pp_env && pp_env[0] == '0');
-    // MPHIP_WINO_PP: 0 the lockstep kernel (r04), 1 the role-split kernel (r05), 2 the big-tile kernel (r06: one wave per SIMD; bit-identical
-    // to 1).  The one-product (autocast) arithmetic exists on the role-split schedule only.
-    if (D == 2) {   // the two-frame mode exists in the big-tile kernel only (three-product arithmetic; under the autocast policy as well:
-                    // this level is 4 % of the slice's multiplies)
-        if (tile_list || gn_part) {
-            set_error("conv3d_fwd(f16x3, F(2,3), D = 2): no demand-driven tile list / GroupNorm partials in the two-frame mode");
-            return MPHIP_EINVAL;
-        }
-        f16x3_wino_bt_launch(grid, s, t0, t1, x, (const _Float16 *)slabs, hdr, bias, dst, N, Ci, Co, D, H, W, cps, xb, in_affine, in_relu, x_range,
-                             tiles, xcd_on, tile_list, gn_part);
-        return check_launch("conv3d_fwd(f16x3, F(2,3), big tile, two frames)");
-    }
-    const bool bt_on = pp_env && pp_env[0] == '2' && !conv_half_products();
-    if (bt_on) {
-        f16x3_wino_bt_launch(grid, s, t0, t1, x, (const _Float16 *)slabs, hdr, bias, dst, N, Ci, Co, D, H, W, cps, xb, in_affine, in_relu, x_range,
-                             tiles, xcd_on, tile_list, gn_part);
-        return check_launch("conv3d_fwd(f16x3, F(2,3), big tile)");
-    }
-    if (pp_on) {   // the role-split schedule (conv3d_f16x3_wino_pp.hip): same arithmetic, same packed weights, same tile
-        f16x3_wino_pp_launch(grid, s, t0, t1, x, (const _Float16 *)slabs, hdr, bias, dst, N, Ci, Co, D, H, W, cps, xb, in_affine, in_relu, x_range,
-                             tiles, xcd_on, tile_list, gn_part, conv_half_products());
-        return check_launch("conv3d_fwd(f16x3, F(2,3), role-split)");
-    }
+void f16x3_wino_launch(dim3 grid, hipStream_t s, hipEvent_t t0, hipEvent_t t1, const float *x, const _Float16 *slabs, const float *hdr,
+                       const float *bias, float *dst, int N, int Ci, int Co, int D, int H, int W, int cps, unsigned xb,
+                       const float *in_affine, int in_relu, const float *x_range, int tiles, int xcd_on, const int *tile_list,
+                       float *gn_part) {
     if (t0 && t1)
-        hipExtLaunchKernelGGL(conv3d_k3_f16x3_wino_kernel, grid, dim3(512), 0, s, t0, t1, 0, x, (const _Float16 *)slabs, hdr, bias, dst, N, Ci,
-                              Co, D, H, W, cps, xb, in_affine, in_relu, x_range, tiles, xcd_on, tile_list, gn_part);
+        hipExtLaunchKernelGGL(conv3d_k3_f16x3_wino_kernel, grid, dim3(512), 0, s, t0, t1, 0, x, slabs, hdr, bias, dst, N, Ci, Co, D, H, W, cps,
+                              xb, in_affine, in_relu, x_range, tiles, xcd_on, tile_list, gn_part);
     else
-        hipLaunchKernelGGL(conv3d_k3_f16x3_wino_kernel, grid, dim3(512), 0, s, x, (const _Float16 *)slabs, hdr, bias, dst, N, Ci, Co, D, H, W,
-                           cps, xb, in_affine, in_relu, x_range, tiles, xcd_on, tile_list, gn_part);
-    return check_launch("conv3d_fwd(f16x3, F(2,3))");
+        hipLaunchKernelGGL(conv3d_k3_f16x3_wino_kernel, grid, dim3(512), 0, s, x, slabs, hdr, bias, dst, N, Ci, Co, D, H, W, cps, xb,
+                           in_affine, in_relu, x_range, tiles, xcd_on, tile_list, gn_part);
 }
 
 }  // namespace mphip

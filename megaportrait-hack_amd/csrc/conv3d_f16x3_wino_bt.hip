@@ -662,7 +662,7 @@ int f16x3_wino_bt_saturation(unsigned long long *count, int reset) {
 void f16x3_wino_bt_launch(dim3 grid, hipStream_t s, hipEvent_t t0, hipEvent_t t1, const float *x, const _Float16 *slabs, const float *hdr,
                           const float *bias, float *dst, int N, int Ci, int Co, int D, int H, int W, int cps, unsigned xb,
                           const float *in_affine, int in_relu, const float *x_range, int tiles, int xcd_on, const int *tile_list,
-                          float *gn_part) {
+                          float *gn_part, bool two_frame) {
 #define BT_LAUNCH(F_, D_)                                                                                                                      \
     {                                                                                                                                          \
         if (t0 && t1)                                                                                                                          \
@@ -672,7 +672,7 @@ void f16x3_wino_bt_launch(dim3 grid, hipStream_t s, hipEvent_t t0, hipEvent_t t1
             hipLaunchKernelGGL((conv3d_k3_f16x3_wino_bt_kernel<F_, D_>), grid, dim3(256), 0, s, x, slabs, hdr, bias, dst, N, Ci, Co, D, H, W, cps, xb,   \
                                in_affine, in_relu, x_range, tiles, xcd_on, tile_list, gn_part);                                                \
     }
-    if (D == 2) { if (in_affine) BT_LAUNCH(true, true) else BT_LAUNCH(false, true) }
+    if (two_frame) { if (in_affine) BT_LAUNCH(true, true) else BT_LAUNCH(false, true) }
     else if (in_affine) BT_LAUNCH(true, false) else BT_LAUNCH(false, false)
 #undef BT_LAUNCH
 }

@@ -16,17 +16,76 @@ __device__ __forceinline__ mphip_f32x4 buf_load_f4(__amdgpu_buffer_rsrc_t rsrc, 
     return __builtin_bit_cast(mphip_f32x4, (u32x4_)__builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)voff, (int)soff, 0));
 }
 
-struct F16x3Plan {
-    int td, variant, splits, chunks_per_split;
-    dim3 grid;
-};
+// Pack layout of the precision-1 weights: what the size helpers and the planner (conv3d_f16x3_plan.hip) share with the kernels.
+constexpr int F16X3_KC = 16;              // input channels per chunk = K of one MFMA
+constexpr int F16X3_TG = 3;               // taps per packed weight slab
+constexpr int F16X3_NG = 27 / F16X3_TG;   // slabs per 16-channel chunk
+constexpr int F16X3_COT = 96;             // output channels per workgroup (3 MFMA row tiles)
+constexpr int SLAB_HALFS = 2 * F16X3_TG * 2 * F16X3_COT * 8;  // [part][tap][kg][co][8] = 9216 halfs = 18432 B
+constexpr int K1_SLAB_HALFS = 2 * 2 * F16X3_COT * 8;   // [part][kg][co][8] = 3072 halfs = 6 KB per (co tile, chunk)
+constexpr int F16X3_AFF_CI = 768;         // fused input GroupNorm table of the direct and two-frame kernels (their AFF_MAX_CI)
+constexpr int WN_KC = 16;                                  // input channels per chunk = K of one MFMA
+constexpr int WN_COT = 96;                                 // output channels per workgroup (3 MFMA row tiles)
+constexpr int WN_NG = 9;                                   // (kd,kh) slabs per chunk
+constexpr int WN_SLAB_HALFS = 2 * 4 * 2 * WN_COT * 8;      // [part][position][kg][co][8] = 12288 halfs = 24576 B
+constexpr int WN_TD = 4, WN_TH = 8, WN_TW = 8;             // output tile
+constexpr int WN_AFF_CI = 384;                             // fused input GroupNorm table: Ci <= 384 (LDS: 98304 + 61952 + 3072 B + the range fold's 68)
 
-bool f16x3_supported(int N, int Ci, int Co, int D, int H, int W, int k);
+// ---- conv3d_f16x3_plan.hip: the one place that decides which kernel a precision-1 launch takes ------------------------------------
+// Dev switches of the choice and of the launch geometry, read by f16x3_switches() and nowhere else.  "per call": read from the
+// environment by every f16x3_switches() (tests and tools flip these in-process).  "fixed": read by the first f16x3_switches() of the
+// process and kept (set them before the first conv query or launch).
+struct F16x3Switches {
+    bool direct_only;      // per call  MPHIP_F16X3_TILE (set to anything): the direct kernels only
+    int force_splits;      // per call  MPHIP_F16X3_SPLITS=n: split-K factor of a DIRECT launch when n divides the chunk count (F(2,3) launches ignore it)
+    bool no_persist;       // per call  MPHIP_F16X3_NO_PERSIST (set): one workgroup per tile — direct launches only
+    bool wino_off;         // per call  MPHIP_WINOGRAD=0: no F(2,3) launches (packs keep the slabs)
+    bool d2_off;           // per call  MPHIP_WINOGRAD_D2=0: no two-frame launches
+    bool min_tiles_set;    // per call  MPHIP_WINOGRAD_MIN_TILES (set to anything): lifts the two-frame mode's N >= 4 rule ...
+    long min_tiles;        // per call  ... and its value is the workgroup count from which an F(2,3) kernel takes a launch (default 192)
+    int wino_pp;           // per call  MPHIP_WINO_PP: 0 lockstep, 2 big tile (without half products), anything else / unset 1 = role-split
+    int k1_ks;             // per call  MPHIP_F16X3_K1_KS=1|4|8: waves sharing a tile of the k = 1 kernel (0 = the rule)
+    long k1_min_voxels;    // per call  MPHIP_F16X3_K1_MIN: voxels from which the k = 1 kernel takes a launch (default 1024)
+    bool old_splits;       // fixed     MPHIP_F16X3_OLD_SPLITS (set): r02's split-K rule on direct launches
+    bool xcd_on;           // fixed     MPHIP_F16X3_XCD=0 clears it: the hardware's round-robin tile placement
+    bool wino_nopack;      // fixed     MPHIP_WINOGRAD_PACK=0: packs carry no F(2,3) slabs (so no launch takes those kernels)
+    bool thirds_off;       // fixed     MPHIP_ROI_THIRDS=0: demand-driven (4,8,8) launches run whole tiles
+    long conv_cus;         // fixed     MPHIP_CONV_CUS=n: CUs a persistent grid fills (default 256)
+    bool gn_epilogue_off;  // fixed     MPHIP_GN_EPILOGUE=0: GroupNorm statistics by a pass of their own
+    int k1_nt;             // fixed     MPHIP_F16X3_K1_NT=1|2: column tiles per wave of the k = 1 kernel (-1 = the rule)
+};
+F16x3Switches f16x3_switches();
+
+enum F16x3Kernel {
+    F16X3_DIRECT_2,         // conv3d_f16x3.hip, (2,8,8) tile, 4 waves, two workgroups per CU
+    F16X3_DIRECT_4,         // conv3d_f16x3.hip, (4,8,8) tile, 8 waves ("thirds" of it on demand-driven launches)
+    F16X3_WINO_LOCKSTEP,    // conv3d_f16x3_wino.hip: F(2,3), the r04 schedule (A/B reference)
+    F16X3_WINO_ROLE_SPLIT,  // conv3d_f16x3_wino_pp.hip: F(2,3), the default of depth % 4 == 0 volumes
+    F16X3_WINO_BIG_TILE,    // conv3d_f16x3_wino_bt.hip: F(2,3), one wave per SIMD (A/B; three-product arithmetic only)
+    F16X3_WINO_TWO_FRAME,   // conv3d_f16x3_wino_bt.hip: its mode for depth-2 volumes, a tile = 2 planes of two frames
+};
+inline bool f16x3_is_wino(F16x3Kernel k) { return k >= F16X3_WINO_LOCKSTEP; }
+
+// The whole decision for one 3x3x3 launch; every consumer (workspace sizes, launch, statistics) reads these fields.
+struct F16x3Plan {
+    F16x3Kernel kernel;
+    int tile[3];            // output tile (d,h,w) a tile index of grid.x stands for (two-frame: the granule of the 4-plane kernels)
+    int gn_rows;            // GroupNorm-partial rows the kernel leaves per tile, 0 = none (separate statistics pass)
+    bool tile_list;         // accepts a demand-driven tile list
+    bool one_product;       // the autocast arithmetic (one f16 product per multiply): the role-split kernel under the half-products flag
+    int max_gn_ci;          // largest Ci with a fused input GroupNorm
+    int wgs_per_cu;         // resident workgroups per CU (the persistent grid and the split-K rule count 256 CUs of them)
+    int splits, chunks_per_split;
+    dim3 grid;              // logical grid: tiles, output-channel tiles, splits
+};
+F16x3Plan f16x3_plan(const F16x3Switches &sw, int N, int Ci, int Co, int D, int H, int W, bool roi, bool half_products);
+
+bool f16x3_supported(const F16x3Switches &sw, int N, int Ci, int Co, int D, int H, int W, int k);
+size_t f16x3_direct_bytes(int Co, int Ci);   // header + the direct kernel's slabs: where the F(2,3) slabs begin
 size_t f16x3_packed_bytes(int Co, int Ci);
 size_t f16x3_packed_bytes_k1(int Co, int Ci);
-int f16x3_launch_k1(const float *x, const void *wpacked, const float *bias, float *dst, int N, int Ci, int Co, int DHW,
-                    const float *x_range, hipStream_t s);
-F16x3Plan f16x3_plan(int N, int Ci, int Co, int D, int H, int W, bool roi = false);
+int f16x3_launch_k1(const F16x3Switches &sw, const float *x, const void *wpacked, const float *bias, float *dst, int N, int Ci, int Co,
+                    int DHW, const float *x_range, hipStream_t s);
 int f16x3_pack(const float *w_oidhw, void *out, int Co, int Ci, int k, int transposed, const void *header_from, hipStream_t s);
 // Batched re-packing (mphip_pack_table_*): one launch per kernel kind for every weight of a module.  PackJob is the device-side job
 // (the public mphip_pack_job + what the host resolved); PackSel a launch's selection: indices into the job array and the first block
@@ -48,26 +107,23 @@ size_t f16x3_pack_wino_offset(int Co, int Ci);
 int f16x3_pack_many(const PackJob *jobs, PackSel absmax, PackSel k3, PackSel k1, hipStream_t s);
 // roi (optional): 8 ints per box {lx,ly,lz,ex,ey,ez,-,-}: only the output tiles a box touches are computed (roi_frames == 0: one box per
 // frame; > 0: the conv's frames... single frame serves that many boxes)
-int f16x3_launch(const F16x3Plan &p, const float *x, const void *wpacked, const float *bias, float *dst, int N, int Ci,
+int f16x3_launch(const F16x3Switches &sw, const F16x3Plan &p, const float *x, const void *wpacked, const float *bias, float *dst, int N, int Ci,
                  int Co, int D, int H, int W, const float *in_affine, int in_relu, const float *x_range, hipStream_t s,
                  const int *roi = nullptr, int roi_frames = 0, int *tile_list = nullptr /* 1 + plan.grid.x ints when roi */, int roi_dilate = 0,
-                 float *gn_part = nullptr /* [Co][plan.grid.x][f16x3_tile_waves][2]: per-wave (sum, sumsq) of the output, splits == 1 only */,
+                 float *gn_part = nullptr /* [Co][plan.grid.x][plan.gn_rows][2]: per-wave (sum, sumsq) of the output, splits == 1 only */,
                  hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr /* stamped with the conv kernel's own begin / end */);
-void f16x3_tile_dims(const F16x3Plan &p, int dims[3]);
-int f16x3_tile_waves(const F16x3Plan &p);
 
-// conv3d_f16x3_wino.hip: the same split-f16 arithmetic in the 1-D Winograd F(2,3) domain (2/3 of the MFMAs).  Its slabs live
-// behind the direct slabs of a precision-1 k=3 pack (0 bytes when the layer can never take the kernel); F16x3Plan.variant 4.
+// conv3d_f16x3_wino.hip: the same split-f16 arithmetic in the 1-D Winograd F(2,3) domain (2/3 of the MFMAs), lockstep schedule.  Its
+// slabs live behind the direct slabs of a precision-1 k=3 pack (0 bytes when the layer can never take an F(2,3) kernel).  The three F(2,3)
+// launchers share one contract; f16x3_launch picks among them by F16x3Plan.kernel.
 size_t f16x3_wino_packed_bytes(int Co, int Ci);
-bool f16x3_wino_usable(int N, int Ci, int Co, int D, int H, int W);
-int f16x3_wino_splits(int N, int Ci, int Co, int D, int H, int W);
-long f16x3_wino_tiles(int N, int D, int H, int W);   // tiles of a launch (a depth-2 volume: one tile = two frames)
+void f16x3_wino_launch(dim3 grid, hipStream_t s, hipEvent_t t0, hipEvent_t t1, const float *x, const _Float16 *slabs, const float *hdr,
+                       const float *bias, float *dst, int N, int Ci, int Co, int D, int H, int W, int cps, unsigned xb,
+                       const float *in_affine, int in_relu, const float *x_range, int tiles, int xcd_on,
+                       const int *tile_list /* demand-driven: {count, tile ids} or NULL */, float *gn_part);
 int f16x3_wino_saturation(unsigned long long *count, int reset);
-int f16x3_wino_launch(const float *x, const void *slabs, const float *hdr, const float *bias, float *dst, int N, int Ci, int Co, int D,
-                      int H, int W, int splits /* f16x3_wino_splits: dst = [splits] slabs when > 1 */, const float *in_affine, int in_relu,
-                      const float *x_range, hipStream_t s, const int *tile_list /* demand-driven: {count, tile ids} or NULL */, float *gn_part, hipEvent_t t0, hipEvent_t t1);
 
-// conv3d_f16x3_wino_pp.hip: the same kernel contract on the role-split ("ping-pong") schedule; f16x3_wino_launch picks it
+// conv3d_f16x3_wino_pp.hip: the same kernel contract on the role-split ("ping-pong") schedule
 void f16x3_wino_pp_launch(dim3 grid, hipStream_t s, hipEvent_t t0, hipEvent_t t1, const float *x, const _Float16 *slabs, const float *hdr,
                           const float *bias, float *dst, int N, int Ci, int Co, int D, int H, int W, int cps, unsigned xb,
                           const float *in_affine, int in_relu, const float *x_range, int tiles, int xcd_on, const int *tile_list,
@@ -78,7 +134,7 @@ int f16x3_wino_pp_saturation(unsigned long long *count, int reset);
 void f16x3_wino_bt_launch(dim3 grid, hipStream_t s, hipEvent_t t0, hipEvent_t t1, const float *x, const _Float16 *slabs, const float *hdr,
                           const float *bias, float *dst, int N, int Ci, int Co, int D, int H, int W, int cps, unsigned xb,
                           const float *in_affine, int in_relu, const float *x_range, int tiles, int xcd_on, const int *tile_list,
-                          float *gn_part);
+                          float *gn_part, bool two_frame);
 int f16x3_wino_bt_saturation(unsigned long long *count, int reset);
 
 // api.hip: the calling thread's conv arithmetic policy (mphip_conv3d_set_half_products): true inside torch.autocast(float16) regions

@@ -29,7 +29,7 @@ def test_typed_entry_points_are_exported(lib):
     raw = ctypes.CDLL(_lib.LIB_PATH)
     for name in NEW_SYMBOLS:
         assert hasattr(raw, name) and name in _lib.SIGNATURES, name
-    assert lib.mphip_version() == 15
+    assert lib.mphip_version() >= 15   # (the ABI that introduced them; later exports bump it)
     hdr = open(os.path.join(ROOT, "include", "mphip.h")).read()
     for code, name in enumerate(("F32", "F16", "BF16")):
         assert f"#define MPHIP_DTYPE_{name} {code}" in hdr
