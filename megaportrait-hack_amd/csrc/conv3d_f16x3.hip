@@ -22,7 +22,6 @@
 
 #include <algorithm>
 
-#include <hip/hip_ext.h>
 
 #include "mphip_ablate.h"
 #include "mphip_common.h"
@@ -1053,41 +1052,33 @@ int f16x3_launch(const F16x3Switches &sw, const F16x3Plan &p, const float *x, co
     const int xcd_on = sw.xcd_on, cps = p.chunks_per_split;
     // (two-slab groups for the 512-voxel tile — 5 instead of 9 barriers per chunk, 147 KB of LDS — were tried: the
     //  compiler spills 188 registers in that instantiation and it runs 35 % slower)
-    // (t0, t1: the measurement hook's events ride on the kernel command itself — hipExtLaunchKernelGGL stamps them with the kernel's own
-    //  begin / end, so what another stream's kernel makes this launch WAIT for CUs is not counted as its duration)
-#define F16X3_LAUNCH(kern_, block_)                                                                                              \
-    {                                                                                                                            \
-        if (t0 && t1)                                                                                                            \
-            hipExtLaunchKernelGGL(kern_, grid, dim3(block_), 0, s, t0, t1, 0, x, slabs, hdr, bias, dst, N, Ci, Co, D, H, W,      \
-                                  cps, xb, in_affine, in_relu, x_scale, tiles_total, xcd_on, roi, roi_frames, gn_part);          \
-        else                                                                                                                     \
-            hipLaunchKernelGGL(kern_, grid, dim3(block_), 0, s, x, slabs, hdr, bias, dst, N, Ci, Co, D, H, W, cps, xb,           \
-                               in_affine, in_relu, x_scale, tiles_total, xcd_on, roi, roi_frames, gn_part);                      \
-    }
-#define F16X3_WINO_ARGS grid, s, t0, t1, x, slabs, hdr, bias, dst, N, Ci, Co, D, H, W, cps, xb, in_affine, in_relu, x_scale, tiles_total, xcd_on, roi, gn_part
+    // (t0, t1: see launch_timed)
+    const F16x3ConvArgs a = {x, slabs, hdr, bias, dst, N, Ci, Co, D, H, W, cps, xb, in_affine, in_relu, x_scale, tiles_total, xcd_on, roi, gn_part};
+    auto direct = [&](auto kern, int block) {
+        launch_timed(kern, grid, dim3(block), s, t0, t1, a.x, a.slabs, a.hdr, a.bias, a.dst, N, Ci, Co, D, H, W, cps, xb, a.in_affine, in_relu,
+                     a.x_range, tiles_total, xcd_on, a.tile_list, roi_frames, gn_part);
+    };
     switch (p.kernel) {   // (full launches and demand-driven ones alike: a listed tile carries the full launch's bits)
         case F16X3_DIRECT_4:
-            if (thirds) F16X3_LAUNCH((conv3d_k3_f16x3_third_kernel<4, 8, 8, 8, 3>), 512)
-            else F16X3_LAUNCH((conv3d_k3_f16x3_kernel<4, 8, 8, 8, 3>), 512)
+            if (thirds) direct(conv3d_k3_f16x3_third_kernel<4, 8, 8, 8, 3>, 512);
+            else direct(conv3d_k3_f16x3_kernel<4, 8, 8, 8, 3>, 512);
             return check_launch("conv3d_fwd(f16x3)");
         case F16X3_DIRECT_2:
-            F16X3_LAUNCH((conv3d_k3_f16x3_kernel<2, 8, 8, 4, 1>), 256)
+            direct(conv3d_k3_f16x3_kernel<2, 8, 8, 4, 1>, 256);
             return check_launch("conv3d_fwd(f16x3)");
         case F16X3_WINO_LOCKSTEP:
-            f16x3_wino_launch(F16X3_WINO_ARGS);
+            f16x3_wino_launch(grid, s, t0, t1, a);
             return check_launch("conv3d_fwd(f16x3, F(2,3))");
         case F16X3_WINO_ROLE_SPLIT:   // same arithmetic, same packed weights, same tile
-            f16x3_wino_pp_launch(F16X3_WINO_ARGS, p.one_product);
+            f16x3_wino_pp_launch(grid, s, t0, t1, a, p.one_product);
             return check_launch("conv3d_fwd(f16x3, F(2,3), role-split)");
         case F16X3_WINO_BIG_TILE:
-            f16x3_wino_bt_launch(F16X3_WINO_ARGS, false);
+            f16x3_wino_bt_launch(grid, s, t0, t1, a, false);
             return check_launch("conv3d_fwd(f16x3, F(2,3), big tile)");
         case F16X3_WINO_TWO_FRAME:
-            f16x3_wino_bt_launch(F16X3_WINO_ARGS, true);
+            f16x3_wino_bt_launch(grid, s, t0, t1, a, true);
             return check_launch("conv3d_fwd(f16x3, F(2,3), big tile, two frames)");
     }
-#undef F16X3_WINO_ARGS
-#undef F16X3_LAUNCH
     set_error("conv3d_fwd(f16x3): plan names no kernel");
     return MPHIP_EINVAL;
 }
@@ -1108,21 +1099,14 @@ extern "C" int mphip_debug_f16x3_profile(unsigned long long *out8, int reset) {
 extern "C" int mphip_f16x3_saturation_count(unsigned long long *count, int reset) {
     // synchronous (copies from the device): a diagnostic, not part of the stream-ordered path
     MPHIP_REQUIRE(count, "f16x3_saturation_count: null pointer");
-    if (hipMemcpyFromSymbol(count, HIP_SYMBOL(mphip::g_f16x3_saturated), sizeof(unsigned long long)) != hipSuccess) {
-        mphip::set_error("f16x3_saturation_count: hipMemcpyFromSymbol failed");
+    if (mphip::f16x3_counter_read(&mphip::g_f16x3_saturated, count, reset) != 0) {
+        mphip::set_error("f16x3_saturation_count: reading the counter failed");
         return MPHIP_ELAUNCH;
-    }
-    if (reset) {
-        const unsigned long long z = 0;
-        if (hipMemcpyToSymbol(HIP_SYMBOL(mphip::g_f16x3_saturated), &z, sizeof(z)) != hipSuccess) {
-            mphip::set_error("f16x3_saturation_count: hipMemcpyToSymbol failed");
-            return MPHIP_ELAUNCH;
-        }
     }
     for (auto other : {mphip::f16x3_wino_saturation, mphip::f16x3_wino_pp_saturation, mphip::f16x3_wino_bt_saturation}) {
         unsigned long long wn = 0;   // the transformed-domain kernels keep their own counters (separate translation units)
         if (other(&wn, reset) != 0) {
-            mphip::set_error("f16x3_saturation_count: hipMemcpyFromSymbol failed");
+            mphip::set_error("f16x3_saturation_count: reading the counter failed");
             return MPHIP_ELAUNCH;
         }
         *count += wn;

@@ -28,18 +28,16 @@
 //     was published one barrier earlier), so the barrier only guards the ring slot that is overwritten next.
 //   * output transform: the four positions of a pair live in four waves.  After the last chunk every wave parks three quarters
 //     of its accumulators in the (now dead) X region, one 32-channel row tile per round, and finishes the quarter it keeps:
-//     y0/y1, bias, the GroupNorm statistics partials of its channels, 8-byte stores.
+//     y0/y1, bias, the GroupNorm statistics partials of its channels, 16-byte stores (mphip_wino_epilogue.h: one definition with the
+//     big-tile kernel).
 //
 // This file holds the lockstep kernel (r04's schedule, today the MPHIP_WINO_PP=0 A/B reference) and its launcher, nothing else: which
 // kernel a launch takes, the split-K factor and the size of the slabs are decided in conv3d_f16x3_plan.hip; the layout constants the
-// packer and the planner share (WN_KC, WN_COT, WN_SLAB_HALFS, ...) are in mphip_conv.h.
-#include <stdlib.h>
-
-#include <hip/hip_ext.h>
-
+// packer, the planner and the three kernels share (WN_KC, WN_COT, WN_SLAB_HALFS, ...) are in mphip_conv.h.
 #include "mphip_ablate.h"
 #include "mphip_conv.h"
 #include "mphip_f16x3.h"
+#include "mphip_wino_tile.h"
 
 namespace mphip {
 
@@ -89,7 +87,7 @@ conv3d_k3_f16x3_wino_kernel(const float *__restrict__ x, const _Float16 *__restr
     _Float16 *const Ws = smem;                                   // ring of 4 slabs
     _Float16 *const Xs = smem + WN_RING * WN_SLAB_HALFS;         // [part][position][kg][row*4 + pair][8]
     float *const aff = reinterpret_cast<float *>(Xs + WN_X_HALFS);   // [Ci][2]: (scale, shift) of the fused input GroupNorm
-    float *const Ex = reinterpret_cast<float *>(Xs);             // output-transform exchange: [wave][slot 0..5][lane][4] (48 KB)
+    float *const Ex = reinterpret_cast<float *>(Xs);             // output-transform exchange: [plane pair][position][slot 0..5][lane][4] (48 KB)
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -133,14 +131,13 @@ conv3d_k3_f16x3_wino_kernel(const float *__restrict__ x, const _Float16 *__restr
     // (threads 480..511 re-do row 59 — same loads, same values, same LDS addresses — so that the staging code is branch-free: it is
     //  issued into the shadow of a chunk's last MFMAs, and the scheduler interleaves only inside one basic block)
     const int cp = tid & 7, srow = min(tid >> 3, WN_ROWS - 1);
-    const bool stager = true;
     const int sdl = srow / WN_HH, shl = srow % WN_HH;
     const bool fuse_in = in_affine != nullptr;   // workgroup-uniform
     const float relu_floor = in_relu ? 0.0f : -3.0e38f;   // (the fused ReLU as a max against a uniform: no branch in the staging code)
     int aff_n = -1;
-    auto row_off = [&]() -> unsigned {   // byte offset of (n, channel 2cp of chunk 0, row, w0), or OOB (padding rows / idle threads)
+    auto row_off = [&]() -> unsigned {   // byte offset of (n, channel 2cp of chunk 0, row, w0), or OOB (padding rows)
         const int gd = d0 - 1 + sdl, gh = h0 - 1 + shl;
-        if (stager && (unsigned)gd < (unsigned)D && (unsigned)gh < (unsigned)H)
+        if ((unsigned)gd < (unsigned)D && (unsigned)gh < (unsigned)H)
             return (unsigned)((((long)n * Ci + 2 * cp) * DHW + (long)gd * HW + gh * W + w0) * 4);
         return OOB;
     };
@@ -164,13 +161,12 @@ conv3d_k3_f16x3_wino_kernel(const float *__restrict__ x, const _Float16 *__restr
     unsigned xmax_ = 0;   // max |scaled halo value| this thread staged, as bits (NaN sorts above Inf above finite): beyond 2^15 the
                           // transformed values can leave the f16 range
     // registers -> (fused GroupNorm + ReLU) -> scale -> F(2,3) input transform -> split -> LDS
-#define WN_STAGER_ON stager
     // All arithmetic on (channel 2cp, channel 2cp+1) PAIRS (f32x2): the pair is exactly the half2 a staging store writes, so scale,
     // transform and split run on v_pk_mul_f32 / v_pk_add_f32 / v_cvt_pk_f16_f32 — ~130 VALU instructions per thread and chunk instead of
     // ~560 with scalar conversions (the halo write was 21 % of a launch: profiles/r04_wino_ablations.txt).  Split: hi = rne(t), lo =
     // rne(t - hi); a non-finite t gives hi = Inf / NaN and lo = NaN, i.e. a non-finite product, like the reference's fp32 conv.
 #define WN_WRITE_X(chunk, FUSE)                                                                            \
-    if (WN_STAGER_ON) {                                                                                    \
+    {                                                                                                      \
         f32x2 v_[10] = {{xl0, xl1}, {xa0[0], xa1[0]}, {xa0[1], xa1[1]}, {xa0[2], xa1[2]}, {xa0[3], xa1[3]},  \
                         {xb0[0], xb1[0]}, {xb0[1], xb1[1]}, {xb0[2], xb1[2]}, {xb0[3], xb1[3]}, {xr0, xr1}}; \
         if (FUSE) {   /* compile-time.  Padding (rows / edge voxels outside the volume) must stay 0: its (scale, shift) pair is zeroed, */ \
@@ -263,16 +259,8 @@ conv3d_k3_f16x3_wino_kernel(const float *__restrict__ x, const _Float16 *__restr
     for (int tj = j_first; tj < ntiles; tj += (int)gridDim.x) {
         const int en = n, ed0 = d0, eh0 = h0, ew0 = w0, etile = tile_at(tj);   // this tile (the staging variables move on during its last chunk)
         const bool has_next = tj + (int)gridDim.x < ntiles;
-        int tz = 0;
-        asm volatile("" : "+v"(tz));  // opaque 0, new per tile: keeps the epilogue's per-channel address math / bias loads from being hoisted
-                                      // out of the tile loop into registers (where they were spilled to scratch)
         f32x16 acc[3][2];
-#pragma unroll
-        for (int m = 0; m < 3; ++m)
-#pragma unroll
-            for (int t = 0; t < 2; ++t)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[m][t][r] = 0.0f;
+        const int tz = wino_tile_begin(acc);
 
         for (int c = c_begin; c < c_end; ++c) {
             const bool more = c + 1 < c_end;
@@ -291,50 +279,6 @@ conv3d_k3_f16x3_wino_kernel(const float *__restrict__ x, const _Float16 *__restr
             //              barrier s: slab s+2 published, slot of slab s free
 #define WN_TOFF(G) ((((G) / 3) * WN_HH + (G) % 3) * 32)
 #define WN_MFMA(a_, b_, c_) __builtin_amdgcn_mfma_f32_32x32x16_f16(a_, b_, c_, 0, 0, 0)
-#ifdef MPHIP_WN_DMA_FIRST   /* dev: same-box A/B — r04's first order: DMA issue and fragment reads in front of the interval's first MFMAs */
-#define WN_INTERVAL(G)                                                                                                     \
-    {                                                                                                                      \
-        constexpr int cur_ = (G) & 1;                                                                                      \
-        if ((G) == 2 && do_load) { WN_LOAD_X(load_chunk); }   /* (before the DMA: hipcc's own vmcnt(k) waits on the   */ \
-        const int issued_ = dma_issue();                       /*  registers it reloads then only cover landed pieces) */ \
-        const _Float16 *wsb_ = Ws + (s & (WN_RING - 1)) * WN_SLAB_HALFS + a_base;                                          \
-        const _Float16 *wsn_ = Ws + ((s + 1) & (WN_RING - 1)) * WN_SLAB_HALFS + a_base + WN_PART_HALFS;                    \
-        _Pragma("unroll") for (int m = 0; m < 3; ++m) ah[m] = *reinterpret_cast<const half8 *>(wsb_ + m * 256);            \
-        _Pragma("unroll") for (int t = 0; t < 2; ++t)                                                                      \
-            bl[t] = *reinterpret_cast<const half8 *>(Xs + WN_XPART + b_base[t] + WN_TOFF(G));                              \
-        __builtin_amdgcn_sched_barrier(0);                                                                                 \
-        _Pragma("unroll") for (int m = 0; m < 3; ++m)                                                                      \
-            _Pragma("unroll") for (int t = 0; t < 2; ++t)                                                                  \
-                acc[m][t] = WN_MFMA(al[m], bh[cur_][t], acc[m][t]);                \
-        __builtin_amdgcn_sched_barrier(0);                                                                                 \
-        if (s + 1 < s_total) {                                                                                             \
-            _Pragma("unroll") for (int m = 0; m < 3; ++m) al[m] = *reinterpret_cast<const half8 *>(wsn_ + m * 256);        \
-        }                                                                                                                  \
-        if ((G) < 8) {                                                                                                     \
-            _Pragma("unroll") for (int t = 0; t < 2; ++t)                                                                  \
-                bh[cur_ ^ 1][t] = *reinterpret_cast<const half8 *>(Xs + b_base[t] + WN_TOFF(((G) < 8 ? (G) + 1 : 0)));     \
-        }                                                                                                                  \
-        __builtin_amdgcn_sched_barrier(0);                                                                                 \
-        _Pragma("unroll") for (int m = 0; m < 3; ++m)                                                                      \
-            _Pragma("unroll") for (int t = 0; t < 2; ++t)                                                                  \
-                acc[m][t] = WN_MFMA(ah[m], bh[cur_][t], acc[m][t]);                \
-        _Pragma("unroll") for (int m = 0; m < 3; ++m)                                                                      \
-            _Pragma("unroll") for (int t = 0; t < 2; ++t)                                                                  \
-                acc[m][t] = WN_MFMA(ah[m], bl[t], acc[m][t]);                      \
-        __builtin_amdgcn_sched_barrier(0);                                                                                 \
-        WPROF_ADD(1)                                                                                                       \
-        /* younger than this wave's pieces of slab s+2: interval 2's halo prefetch (8) and this interval's pieces (3) */   \
-        if ((G) == 2 && do_load) {                                                                                         \
-            if (issued_) lds_dma_wait<WN_XLOADS + 3>(); else lds_dma_wait<WN_XLOADS>();                                    \
-        } else {                                                                                                           \
-            if (issued_) lds_dma_wait<3>(); else lds_dma_wait<0>();                                                        \
-        }                                                                                                                  \
-        WPROF_ADD(2)                                                                                                       \
-        lds_barrier();                                                                                                     \
-        WPROF_ADD(3)                                                                                                       \
-        ++s;                                                                                                               \
-    }
-#else
             // The interval's first six MFMAs (Wlo(s) x Xhi: both fetched during the previous interval) are issued straight after the
             // barrier; the DMA pieces, the halo prefetch and all of the interval's fragment reads are issued into their shadow — an LDS-DMA
             // piece costs its wave 60-185 issue cycles (MI355X_MICROARCH.md), which the MFMA pipe sat out when they came first.
@@ -382,7 +326,6 @@ conv3d_k3_f16x3_wino_kernel(const float *__restrict__ x, const _Float16 *__restr
         WPROF_ADD(3)                                                                                                       \
         ++s;                                                                                                               \
     }
-#endif
             WN_INTERVAL(0)
             WN_INTERVAL(1)
             WN_INTERVAL(2)
@@ -391,17 +334,6 @@ conv3d_k3_f16x3_wino_kernel(const float *__restrict__ x, const _Float16 *__restr
             WN_INTERVAL(5)
             WN_INTERVAL(6)
             WN_INTERVAL(7)
-#ifdef MPHIP_WN_NO_OVERLAP8   /* dev: same-box A/B — the halo write in its own phase after the chunk's last interval */
-            WN_INTERVAL(8)
-            if (more) {
-                if (fuse_in) { WN_WRITE_X(c + 1, true) } else { WN_WRITE_X(c + 1, false) }   // every wave is past its last read of the X tile
-                WPROF_ADD(4)
-                lds_barrier();
-#pragma unroll
-                for (int t = 0; t < 2; ++t) bh[0][t] = *reinterpret_cast<const half8 *>(Xs + b_base[t]);
-                WPROF_ADD(5)
-            }
-#else
             {
                 // The chunk's last interval carries the NEXT chunk's halo write: once this interval's fragments are in registers nobody reads
                 // the X tile any more, so after one early barrier the tile may be rewritten while the interval's 18 MFMAs run.  The two
@@ -411,14 +343,12 @@ conv3d_k3_f16x3_wino_kernel(const float *__restrict__ x, const _Float16 *__restr
                 // hipcc 70-160 spilled registers, and so did interleaving both jobs in one instruction stream); only the staging code
                 // sits under the wave-uniform conditions.  A tile's last chunk (!more) has nothing to stage here: the next tile's halo is
                 // written after the output transform, which uses the X region.
-#ifndef MPHIP_WN_DMA_FIRST
                 __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int m = 0; m < 3; ++m)
 #pragma unroll
                     for (int t = 0; t < 2; ++t) acc[m][t] = WN_MFMA(al[m], bh[0][t], acc[m][t]);
                 __builtin_amdgcn_sched_barrier(0);
-#endif
                 const int issued_ = dma_issue();
                 const _Float16 *wsb_ = Ws + (s & (WN_RING - 1)) * WN_SLAB_HALFS + a_base;
                 const _Float16 *wsn_ = Ws + ((s + 1) & (WN_RING - 1)) * WN_SLAB_HALFS + a_base + WN_PART_HALFS;
@@ -434,13 +364,6 @@ conv3d_k3_f16x3_wino_kernel(const float *__restrict__ x, const _Float16 *__restr
                     }
                 }
                 __builtin_amdgcn_sched_barrier(0);
-#ifdef MPHIP_WN_DMA_FIRST
-#pragma unroll
-                for (int m = 0; m < 3; ++m)
-#pragma unroll
-                    for (int t = 0; t < 2; ++t) acc[m][t] = WN_MFMA(al[m], bh[0][t], acc[m][t]);
-                __builtin_amdgcn_sched_barrier(0);
-#endif
                 if (s + 1 < s_total) {
 #pragma unroll
                     for (int m = 0; m < 3; ++m) al[m] = *reinterpret_cast<const half8 *>(wsn_ + m * 256);
@@ -470,93 +393,33 @@ conv3d_k3_f16x3_wino_kernel(const float *__restrict__ x, const _Float16 *__restr
                 }
                 WPROF_ADD(5)
             }
-#endif
 #undef WN_INTERVAL
         }
 
         // ---- output transform + epilogue: three rounds (one 32-channel row tile each) through the dead X region ---------------------
         const int gn_rows = tiles_total * 2;   // channel-major [Co][tile * 2 + ch][2] (the finalize kernel reads rows of it)
-        if (gn_part && etile == 0 && tid == 0) gn_part[(size_t)gn_rows * Co * 2] = unscale;   // (behind the partials)
+        if (gn_part && etile == 0 && tid == 0) wino_gn_write_unscale(gn_part, gn_rows, Co, unscale);
         const bool odd = (lane & 1) != 0;
         // (row start of this lane's QUAD of voxels: lanes 2k / 2k+1 store the 4 voxels 4k..4k+3 of a row, for different channels)
         float *const dsto = (direct ? y : y + (size_t)blockIdx.z * N * Co * DHW) + (size_t)en * Co * DHW + (size_t)(ed0 + 2 * ch) * HW + (size_t)(eh0 + (j >> 2)) * W + ew0 + 2 * (j & 2);
 #pragma unroll
         for (int m = 0; m < 3; ++m) {
-            // park the units other waves finish: unit u = accumulator registers 4u..4u+3 of both column tiles; wave p keeps unit p
-#pragma unroll
-            for (int t = 0; t < 2; ++t)
-#pragma unroll
-                for (int u = 0; u < 4; ++u)
-                    if (u != p) {
-                        const int slot = t * 3 + (u - (u > p ? 1 : 0));
-                        const f32x4 v = {acc[m][t][4 * u], acc[m][t][4 * u + 1], acc[m][t][4 * u + 2], acc[m][t][4 * u + 3]};
-                        *reinterpret_cast<f32x4 *>(Ex + ((wave * 6 + slot) * 64 + lane) * 4) = v;
-                    }
+            wino_park_units(p, acc[m], Ex, 4 * ch, lane);
             lds_barrier();
             float ssum[4] = {0.0f, 0.0f, 0.0f, 0.0f}, qsum[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-            float bv[4];
+            f32x4 bv;
 #pragma unroll
             for (int i = 0; i < 4; ++i) bv[i] = (direct && bias) ? bias[co0 + m * 32 + 8 * p + 4 * kgl + i + tz] : 0.0f;
 #pragma unroll
             for (int t = 0; t < 2; ++t) {
-                f32x4 M[4];
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {
-                    if (q != p) {
-                        const int slot = t * 3 + (p - (p > q ? 1 : 0));
-                        M[q] = *reinterpret_cast<const f32x4 *>(Ex + (((ch * 4 + q) * 6 + slot) * 64 + lane) * 4);
-                    } else {
-#pragma unroll
-                        for (int i = 0; i < 4; ++i) M[q][i] = acc[m][t][4 * q + i];
-                    }
-                }
-                float y0[4], y1[4];
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    const float r0 = (M[0][i] + M[1][i]) + M[2][i];
-                    const float r1 = (M[1][i] - M[2][i]) - M[3][i];
-                    ssum[i] += r0 + r1;
-                    qsum[i] = __builtin_fmaf(r0, r0, qsum[i]);
-                    qsum[i] = __builtin_fmaf(r1, r1, qsum[i]);
-                    y0[i] = r0 * unscale + bv[i];
-                    y1[i] = r1 * unscale + bv[i];
-                }
-                // 16-byte stores: a lane holds one output pair (2 voxels) of 4 channels; lanes 2k / 2k+1 hold neighbouring pairs of a row.
-                // They trade halves (quad_perm [1,0,3,2]): the even lane ends up with 4 consecutive voxels of channels 0-1, the odd lane
-                // with those of channels 2-3 — two dwordx4 stores per lane instead of four dwordx2 (the epilogue is store-ISSUE bound:
-                // 8-byte stores of 32-byte row pieces ran at ~7 B/clk/CU, MI355X_MICROARCH.md "epilogue store tail").
-#define WN_SWAP(v_) __uint_as_float(__builtin_amdgcn_update_dpp(0, __float_as_uint(v_), 0xB1, 0xf, 0xf, false))
-                const float g0 = WN_SWAP(odd ? y0[0] : y0[2]), g1 = WN_SWAP(odd ? y1[0] : y1[2]);
-                const float g2 = WN_SWAP(odd ? y0[1] : y0[3]), g3 = WN_SWAP(odd ? y1[1] : y1[3]);
-#undef WN_SWAP
-                const f32x4 va = {odd ? g0 : y0[0], odd ? g1 : y1[0], odd ? y0[2] : g0, odd ? y1[2] : g1};
-                const f32x4 vb = {odd ? g2 : y0[1], odd ? g3 : y1[1], odd ? y0[3] : g2, odd ? y1[3] : g3};
+                f32x4 M[4], va, vb;
+                wino_gather_M(p, acc[m][t], Ex, 4 * ch, lane, t, M);
+                wino_out_pair(M, bv, unscale, odd, true, ssum, qsum, va, vb);
                 float *const dq = dsto + (size_t)(co0 + m * 32 + 8 * p + 4 * kgl + (odd ? 2 : 0) + tz) * DHW + (size_t)t * HW;
                 *reinterpret_cast<f32x4 *>(dq) = va;
                 *reinterpret_cast<f32x4 *>(dq + DHW) = vb;
             }
-            if (gn_part) {
-                // per-channel (sum, sum of squares) of the RAW transformed accumulators over this wave's 2 x 64 voxels of the channel:
-                // the 32 lanes of a half-wave hold one channel's columns (the finalize kernel applies unscale and the bias in double)
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-#define WN_ROW_ADD(v_, ctrl_) v_ += __uint_as_float(__builtin_amdgcn_update_dpp(0, __float_as_uint(v_), ctrl_, 0xf, 0xf, false));
-                    WN_ROW_ADD(ssum[i], 0x128) WN_ROW_ADD(qsum[i], 0x128)   // row_ror:8, :4, :2, :1 -> every lane of a 16-lane row: the row's sum
-                    WN_ROW_ADD(ssum[i], 0x124) WN_ROW_ADD(qsum[i], 0x124)
-                    WN_ROW_ADD(ssum[i], 0x122) WN_ROW_ADD(qsum[i], 0x122)
-                    WN_ROW_ADD(ssum[i], 0x121) WN_ROW_ADD(qsum[i], 0x121)
-#undef WN_ROW_ADD
-                    ssum[i] += __shfl_xor(ssum[i], 16, 64);
-                    qsum[i] += __shfl_xor(qsum[i], 16, 64);
-                }
-                if (j == 0) {
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) {
-                        const int co = co0 + m * 32 + 8 * p + 4 * kgl + i + tz;
-                        *reinterpret_cast<float2 *>(gn_part + ((size_t)co * gn_rows + (size_t)etile * 2 + ch) * 2) = make_float2(ssum[i], qsum[i]);
-                    }
-                }
-            }
+            if (gn_part) wino_gn_write(gn_part, gn_rows, co0 + m * 32 + 8 * p + 4 * kgl + tz, (size_t)etile * 2 + ch, j, ssum, qsum);
             lds_barrier();   // the region is rewritten by the next round / the next tile's halo
         }
 
@@ -574,38 +437,15 @@ conv3d_k3_f16x3_wino_kernel(const float *__restrict__ x, const _Float16 *__restr
 #undef WN_LOAD_X
 #undef WN_WRITE_X
 #undef WN_TOFF
-    // operands outside the f16 range (non-finite inputs, or finite ones beyond a wrong caller-supplied descriptor) are not clamped — they
-    // propagate as Inf / NaN — but they are counted: here per thread that saw any (the direct kernel counts elements)
-    const unsigned xlim_ = __float_as_uint(0.5f * F16_CLAMP);
-    if (__builtin_amdgcn_ballot_w64(xmax_ > xlim_) != 0) {  // never taken in normal operation
-        unsigned tot = xmax_ > xlim_;
-#pragma unroll
-        for (int sft = 32; sft >= 1; sft >>= 1) tot += __shfl_xor(tot, sft, 64);
-        if (lane == 0) atomicAdd(&g_f16x3_wino_saturated, (unsigned long long)tot);
-    }
+    wino_count_saturated(xmax_ > __float_as_uint(0.5f * F16_CLAMP), &g_f16x3_wino_saturated, lane);
     WPROF_FLUSH
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------------
-int f16x3_wino_saturation(unsigned long long *count, int reset) {   // (mphip_f16x3_saturation_count adds it to the other kernels' counters)
-    if (hipMemcpyFromSymbol(count, HIP_SYMBOL(g_f16x3_wino_saturated), sizeof(unsigned long long)) != hipSuccess) return -1;
-    if (reset) {
-        const unsigned long long z = 0;
-        if (hipMemcpyToSymbol(HIP_SYMBOL(g_f16x3_wino_saturated), &z, sizeof(z)) != hipSuccess) return -1;
-    }
-    return 0;
-}
+int f16x3_wino_saturation(unsigned long long *count, int reset) { return f16x3_counter_read(&g_f16x3_wino_saturated, count, reset); }
 
-void f16x3_wino_launch(dim3 grid, hipStream_t s, hipEvent_t t0, hipEvent_t t1, const float *x, const _Float16 *slabs, const float *hdr,
-                       const float *bias, float *dst, int N, int Ci, int Co, int D, int H, int W, int cps, unsigned xb,
-                       const float *in_affine, int in_relu, const float *x_range, int tiles, int xcd_on, const int *tile_list,
-                       float *gn_part) {
-    if (t0 && t1)
-        hipExtLaunchKernelGGL(conv3d_k3_f16x3_wino_kernel, grid, dim3(512), 0, s, t0, t1, 0, x, slabs, hdr, bias, dst, N, Ci, Co, D, H, W, cps,
-                              xb, in_affine, in_relu, x_range, tiles, xcd_on, tile_list, gn_part);
-    else
-        hipLaunchKernelGGL(conv3d_k3_f16x3_wino_kernel, grid, dim3(512), 0, s, x, slabs, hdr, bias, dst, N, Ci, Co, D, H, W, cps, xb,
-                           in_affine, in_relu, x_range, tiles, xcd_on, tile_list, gn_part);
+void f16x3_wino_launch(dim3 grid, hipStream_t s, hipEvent_t t0, hipEvent_t t1, const F16x3ConvArgs &a) {
+    f16x3_wino_launch_kernel(conv3d_k3_f16x3_wino_kernel, grid, dim3(512), s, t0, t1, a);
 }
 
 }  // namespace mphip

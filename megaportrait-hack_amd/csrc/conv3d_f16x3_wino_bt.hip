@@ -29,13 +29,10 @@
 // Every slice is cut into micro-operations of <= 7 instructions hung behind one MFMA each of P2 / P3 (pinned with sched_barrier: hipcc
 // clusters otherwise), nothing is conditional (a branch costs the single wave two issue slots), P1 carries the fragment reads only, so
 // that no LDS operation is young at the barrier.  The tile's epilogue goes through ONE exchange region (buffer 1 already holds the next
-// period's first pair): six rounds (row tile x plane pair).
-#include <stdlib.h>
-
+// period's first pair): six rounds (row tile x plane pair).  Tile geometry, LDS map, stream walk and staging helpers: mphip_wino_tile.h;
+// output transform, GroupNorm partials, store pattern: mphip_wino_epilogue.h (shared with the lockstep kernel).
 #include <type_traits>
 #include <utility>
-
-#include <hip/hip_ext.h>
 
 #include "mphip_ablate.h"
 #include "mphip_conv.h"
@@ -97,7 +94,6 @@ conv3d_k3_f16x3_wino_bt_kernel(const float *__restrict__ x, const _Float16 *__re
     const int j = lane & 31, kgl = lane >> 5;
     const int HW = H * W, DHW = D * HW;
     const int ntiles = tile_list ? tile_list[0] : tiles_total;
-    auto tile_at = [&](int jj) -> int { return tile_list ? tile_list[1 + jj] : jj; };
     const int j_first = (tile_list || !xcd_aware) ? (int)blockIdx.x : (int)xcd_remap(blockIdx.x, gridDim.x);
     if (j_first >= ntiles) return;   // (workgroup-uniform, before any barrier)
     float x_scale = 16.0f, x_unscale = 1.0f / 16.0f;
@@ -107,7 +103,6 @@ conv3d_k3_f16x3_wino_bt_kernel(const float *__restrict__ x, const _Float16 *__re
     unsigned long long prof_epi = 0;
 #endif
 
-    const int tiles_w = W / PP_TW, tiles_h = H / PP_TH, tiles_d = D / PP_TD;
     const int cot = blockIdx.y;
     const int nchunks = Ci / 16;
     const int c_begin = blockIdx.z * chunks_per_split, c_end = min(nchunks, c_begin + chunks_per_split);
@@ -115,29 +110,12 @@ conv3d_k3_f16x3_wino_bt_kernel(const float *__restrict__ x, const _Float16 *__re
     const int nper = c_end - c_begin;
     const int nmine = (ntiles - j_first + (int)gridDim.x - 1) / (int)gridDim.x;   // tiles this workgroup walks
     const int per_total = nmine * nper;                                           // 16-channel periods it walks
+    const WinoStream ws = {tile_list, W / PP_TW, H / PP_TH, D / PP_TD, c_begin, c_end, (int)gridDim.x,
+                           reinterpret_cast<const unsigned char *>(wslabs) + (size_t)cot * nchunks * 9 * PP_SLAB_B};
 
-    auto period_at = [&](int tj, int chunk) -> PpPeriod {
-        PpPeriod r;
-        int bid = tile_at(tj);
-        const int tw = bid % tiles_w; bid /= tiles_w;
-        const int th = bid % tiles_h; bid /= tiles_h;
-        if constexpr (D2) { r.n = 2 * bid; r.d0 = 0; }      // a tile = the frame pair (2 bid, 2 bid + 1)
-        else { r.n = bid / tiles_d; r.d0 = (bid % tiles_d) * PP_TD; }
-        r.h0 = th * PP_TH; r.w0 = tw * PP_TW;
-        r.chunk = chunk; r.tj = tj;
-        return r;
-    };
-    auto period_next = [&](const PpPeriod &a) -> PpPeriod {   // (only called when a successor exists)
-        if (a.chunk + 1 < c_end) { PpPeriod r = a; r.chunk = a.chunk + 1; return r; }
-        return period_at(a.tj + (int)gridDim.x, c_begin);
-    };
-
-    // raw buffer descriptor of x (base, stride 0, num_records = bytes, 32-bit float data format): out-of-range offsets read 0 = the padding
-    const unsigned long long xaddr = (unsigned long long)(uintptr_t)x;
-    const pp_u32x4 rsrc = {(unsigned)xaddr, (unsigned)(xaddr >> 32) & 0xffffu, x_bytes, 0x00020000u};
+    const pp_u32x4 rsrc = wino_rsrc(x, x_bytes);
     const unsigned chan_stride = (unsigned)DHW * 4u;
-    const unsigned long long aaddr = (unsigned long long)(uintptr_t)in_affine;
-    const pp_u32x4 rsrc_aff = {(unsigned)aaddr, (unsigned)(aaddr >> 32) & 0xffffu, (unsigned)((size_t)N * Ci * 2 * 4), 0x00020000u};
+    const pp_u32x4 rsrc_aff = wino_rsrc(in_affine, (unsigned)((size_t)N * Ci * 2 * 4));
 
     // ---- X staging: thread = (channel pair cp of an 8-channel half, halo row); 240 of the 256 threads (the other 16 re-do row 59:
     // same loads, same values, same LDS addresses — branch-free).  Role 0 = the even half (buffer 0), role 1 = the odd half (buffer 1):
@@ -188,10 +166,7 @@ conv3d_k3_f16x3_wino_bt_kernel(const float *__restrict__ x, const _Float16 *__re
             pp_buf_load_2x1(rsrc, lft ? ob - 4u : OOB, rgt ? ob + 32u : OOB, ld == 4 ? xl0[role] : xl1[role], ld == 4 ? xr0[role] : xr1[role]);
         }
     };
-    auto note = [&](float a, float b) {   // range diagnostic: one v_max3 (|a|, |b|, m) and one unordered compare per two values
-        xmaxf_ = __builtin_fmaxf(__builtin_fmaxf(__builtin_fabsf(a), __builtin_fabsf(b)), xmaxf_);
-        xnan_ |= __builtin_isunordered(a, b);
-    };
+    auto note = [&](float a, float b) { wino_note(a, b, xmaxf_, xnan_); };
     // PREP 0: read the row's (scale, shift) pairs; 1 / 2: fold the operand scale S (a power of two: (x m + a) S == x (m S) + a S and
     // max(., 0) S == max(. S, 0) bit for bit) and the padding masks into them
     auto halo_prep = [&](const PpPeriod &s, auto ROLEc, auto Kc) __attribute__((always_inline)) {
@@ -246,12 +221,8 @@ conv3d_k3_f16x3_wino_bt_kernel(const float *__restrict__ x, const _Float16 *__re
         constexpr int role = decltype(ROLEc)::value, q = decltype(Qc)::value, pp = decltype(Kc)::value / 3, st = decltype(Kc)::value % 3;
         if (BT_ABL & 1) { asm volatile("" :: "v"(xa0[role]), "v"(xb0[role]), "v"(xa1[role]), "v"(xb1[role]), "v"(xl0[role]), "v"(xr0[role]), "v"(xl1[role]), "v"(xr1[role])); return; }
         if constexpr (st == 0) {
-            auto v0 = [&](int i) -> float { return i == 0 ? xl0[role] : i <= 4 ? xa0[role][i - 1] : i <= 8 ? xb0[role][i - 5] : xr0[role]; };   // (i folds: q is a constant)
-            auto v1 = [&](int i) -> float { return i == 0 ? xl1[role] : i <= 4 ? xa1[role][i - 1] : i <= 8 ? xb1[role][i - 5] : xr1[role]; };
-            if constexpr (pp == 0) { wt0 = v0(2 * q) - v0(2 * q + 2); wt1 = v1(2 * q) - v1(2 * q + 2); }
-            else if constexpr (pp == 1) { wt0 = v0(2 * q + 1) + v0(2 * q + 2); wt1 = v1(2 * q + 1) + v1(2 * q + 2); }
-            else if constexpr (pp == 2) { wt0 = v0(2 * q + 2) - v0(2 * q + 1); wt1 = v1(2 * q + 2) - v1(2 * q + 1); }
-            else { wt0 = v0(2 * q + 1) - v0(2 * q + 3); wt1 = v1(2 * q + 1) - v1(2 * q + 3); }
+            wt0 = wino_in_transform(pp, q, xl0[role], xa0[role], xb0[role], xr0[role]);
+            wt1 = wino_in_transform(pp, q, xl1[role], xa1[role], xb1[role], xr1[role]);
         } else if constexpr (st == 1) {
             whv = pp_cvt_pk(wt0, wt1);
             wt0 = pp_sub_lo(whv, wt0);
@@ -263,39 +234,15 @@ conv3d_k3_f16x3_wino_bt_kernel(const float *__restrict__ x, const _Float16 *__re
             *reinterpret_cast<unsigned *>(xw + PP_XPART_B + pp * PP_XPOS_B + q * PP_XPAIR_B) = lv;
         }
     };
-    auto load_aff = [&](int n, int first, int stride) {
-        for (int i = first; i < Ci * 2; i += stride) aff[i] = in_affine[(size_t)n * Ci * 2 + i];
-    };
-    // the same table for another frame, as LDS-DMA (ONE wave, up to three pieces of 1 KiB; lanes beyond the table are masked off)
     const unsigned aff_lds = (unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char *)smem + PP_LDS_AFF;
-    auto dma_aff = [&](int n) __attribute__((always_inline)) {
-        const unsigned char *const src = reinterpret_cast<const unsigned char *>(in_affine + (size_t)n * Ci * 2);
-        const int bytes = Ci * 8;
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-            if (i * 1024 < bytes && lane * 16 + i * 1024 < bytes)
-                asm volatile("s_nop 4\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, %1" ::"v"((unsigned)(lane * 16 + i * 1024)), "s"(src), "s"(aff_lds + i * 1024) : "memory");
-    };
-
-    // ---- weight stream: piece i of a wave covers LDS bytes [(p + 4 i) KiB, +1 KiB) of the slab image (the role-split kernel's source
-    // mapping: a lane's 16 bytes lie in k-group block (part, position, kg) = o / 1536; k-group 1 reads item 2s+1 = one slab further in the
-    // pack, except at step 4 where item 9 is (tap 0, k-group 1))
+    // ---- weight stream: piece i of a wave covers LDS bytes [(p + 4 i) KiB, +1 KiB) of the slab image (source mapping: wino_dma_src)
     const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char *)smem;
     unsigned dsrc[BT_PIECES], dsrc4[BT_PIECES];
 #pragma unroll
-    for (int i = 0; i < BT_PIECES; ++i) {
-        const unsigned o = (unsigned)(p + 4 * i) * 1024u + (unsigned)lane * 16u;
-        const unsigned blk = o / PP_KGBLK_B;
-        const bool kg1 = (blk & 1u) != 0;
-        const unsigned in_slab = (blk >> 1) * (2u * PP_KGBLK_B) + (o - blk * PP_KGBLK_B);
-        dsrc[i] = in_slab + (kg1 ? (unsigned)PP_SLAB_B : 0u);
-        dsrc4[i] = in_slab + (kg1 ? (unsigned)PP_KGBLK_B : 8u * PP_SLAB_B);
-    }
-    const unsigned char *const wbytes = reinterpret_cast<const unsigned char *>(wslabs) + (size_t)cot * nchunks * 9 * PP_SLAB_B;
-    auto wchunk = [&](int chunk) -> const unsigned char * { return wbytes + (size_t)chunk * 9 * PP_SLAB_B; };
+    for (int i = 0; i < BT_PIECES; ++i) wino_dma_src((unsigned)(p + 4 * i) * 1024u + (unsigned)lane * 16u, dsrc[i], dsrc4[i]);
     auto dma_piece = [&](auto SQc, auto Kc, const unsigned char *base) __attribute__((always_inline)) {   // piece K (0..5) of slab SQ (0..8) of the period at `base`
         constexpr int sq = decltype(SQc)::value, k = decltype(Kc)::value;
-        constexpr unsigned V0 = sq == 4 ? 0u : ((2 * sq) % 9) * PP_SLAB_B + ((2 * sq) / 9) * PP_KGBLK_B;   // (tap, k-group) of item 2 sq
+        constexpr unsigned V0 = wino_dma_base(sq);
         constexpr unsigned slot = sq % PP_R;
         if (BT_ABL & 4) return;
         bt_dma1(base + V0, sq == 4 ? dsrc4[k] : dsrc[k], lds0 + slot * PP_SLAB_B + (unsigned)(p + 4 * k) * 1024u);
@@ -304,13 +251,9 @@ conv3d_k3_f16x3_wino_bt_kernel(const float *__restrict__ x, const _Float16 *__re
         bt_for<BT_PIECES>([&](auto K) { dma_piece(SQc, K, base); });
     };
 
-    // fragment bases (bytes).  X: the two k-groups of a step read items 2s and 2s+1 — one halo row apart (+16 B), eight rows apart (tap
-    // (kd,2) -> (kd+1,0): +128 B), or (step 4) the last tap of buffer 0 and the first of buffer 1: three per-lane bases, the step's own
-    // offset and the plane (t * 160 B) are immediates
+    // fragment bases (bytes).  X: WinoXBases; the step's own offset and the plane (t * 160 B) are immediates
     const unsigned a_off = (unsigned)(((p * 2 + kgl) * PP_COT + j) * 16);
-    const unsigned b_lane = (unsigned)(PP_LDS_X + p * PP_XPOS_B + (j & 3) * PP_XPAIR_B + (j >> 2) * PP_XROW_B);
-    const unsigned b_row = b_lane + (unsigned)kgl * PP_XROW_B, b_plane = b_lane + (unsigned)kgl * (8u * PP_XROW_B),
-                   b_buf = b_lane + (unsigned)kgl * (unsigned)(PP_XBUF_B - pp_rowoff(8) * PP_XROW_B);
+    const WinoXBases xbase((unsigned)(PP_LDS_X + p * PP_XPOS_B + (j & 3) * PP_XPAIR_B + (j >> 2) * PP_XROW_B), kgl);
     const unsigned d2_k1 = 0u - (unsigned)(kgl * 3 * PP_HH * PP_XROW_B), d2_k0 = 0u - (unsigned)((1 - kgl) * 3 * PP_HH * PP_XROW_B);
     half8 ah[3], al[3], bh[4], bl[4];
     auto ld_a = [&](auto SPc, auto Mc, bool lo) __attribute__((always_inline)) -> half8 {   // weight fragment m of step sp
@@ -323,31 +266,29 @@ conv3d_k3_f16x3_wino_bt_kernel(const float *__restrict__ x, const _Float16 *__re
         constexpr int sp = decltype(SPc)::value, t = decltype(Tc)::value;
         if (BT_ABL & 32) { half8 z = {}; asm volatile("" : "+v"(z)); return z; }
         constexpr int I0 = 2 * sp, I1 = 2 * sp + 1;
-        constexpr unsigned off0 = (I0 / 9) * PP_XBUF_B + pp_rowoff(I0 % 9) * PP_XROW_B;
-        constexpr unsigned off1 = (I1 / 9) * PP_XBUF_B + pp_rowoff(I1 % 9) * PP_XROW_B;
-        static_assert(off1 - off0 == PP_XROW_B || off1 - off0 == 8 * PP_XROW_B || off1 - off0 == PP_XBUF_B - pp_rowoff(8) * PP_XROW_B, "k-group distance");
+        constexpr unsigned off0 = WinoXBases::off(I0);
         constexpr int PLANE = PP_HH * PP_XROW_B;
         constexpr int tb = D2 ? (t < 2 ? t : t + 1) : t;                        // first halo-plane slot of plane t
         constexpr bool z0 = D2 && t == 3 && (I0 % 9) / 3 == 2, z1 = D2 && t == 3 && (I1 % 9) / 3 == 2;   // k-group 0 / 1 would read slot 6: slot 3 instead
-        const unsigned base = (off1 - off0 == PP_XROW_B ? b_row : off1 - off0 == 8 * PP_XROW_B ? b_plane : b_buf);
+        const unsigned base = xbase.base<sp>();
         const unsigned corr = z0 == z1 ? 0u : z1 ? d2_k1 : d2_k0;             // (per lane only where the two k-groups differ)
         const unsigned char *const xb = smem + (base + corr) + (int)(off0 + tb * PLANE) - (z0 && z1 ? 3 * PLANE : 0);
         return *reinterpret_cast<const half8 *>(xb + (lo ? PP_XPART_B : 0));
     };
 
     // ---- prologue: slabs 0, 1, 2 in flight, both halves of period 0 staged, the first step's Wlo / Xhi fragments loaded ---------------
-    PpPeriod cur = period_at(j_first, c_begin), nxt = cur;
+    PpPeriod cur = ws.period_at<D2>(j_first, c_begin), nxt = cur;
     bool nxt_ok = per_total > 1;
-    if (nxt_ok) nxt = period_next(cur);
+    if (nxt_ok) nxt = ws.period_next<D2>(cur);
     if (tid < PP_COT) reinterpret_cast<float *>(smem + PP_LDS_BIAS)[tid] = (gridDim.z == 1 && bias) ? bias[cot * PP_COT + tid] : 0.0f;
     if (fuse_in && !D2) {
-        load_aff(cur.n, tid, 256);
+        wino_load_aff(aff, in_affine, cur.n, Ci, tid, 256);
         aff_n = cur.n;
         lds_barrier();
     }
-    dma_slab(std::integral_constant<int, 0>{}, wchunk(cur.chunk));
-    dma_slab(std::integral_constant<int, 1>{}, wchunk(cur.chunk));
-    dma_slab(std::integral_constant<int, 2>{}, wchunk(cur.chunk));
+    dma_slab(std::integral_constant<int, 0>{}, ws.wchunk(cur.chunk));
+    dma_slab(std::integral_constant<int, 1>{}, ws.wchunk(cur.chunk));
+    dma_slab(std::integral_constant<int, 2>{}, ws.wchunk(cur.chunk));
     bt_for<2>([&](auto R) {
         halo_addr(cur, R);
         bt_for<7>([&](auto L) { halo_load(cur, R, L); });
@@ -373,21 +314,14 @@ conv3d_k3_f16x3_wino_bt_kernel(const float *__restrict__ x, const _Float16 *__re
 #endif
 
     for (int tj = j_first; tj < ntiles; tj += (int)gridDim.x) {
-        const int en = cur.n, ed0 = cur.d0, eh0 = cur.h0, ew0 = cur.w0, etile = tile_at(tj);
-        int tz = 0;
-        asm volatile("" : "+v"(tz));  // opaque 0, new per tile: keeps the epilogue's per-channel address math / bias loads out of the tile loop
+        const int en = cur.n, ed0 = cur.d0, eh0 = cur.h0, ew0 = cur.w0, etile = ws.tile_at(tj);
         f32x16 acc[3][4];
-#pragma unroll
-        for (int m = 0; m < 3; ++m)
-#pragma unroll
-            for (int t = 0; t < 4; ++t)
-#pragma unroll
-                for (int r = 0; r < 16; ++r) acc[m][t][r] = 0.0f;
+        const int tz = wino_tile_begin(acc);
 
         for (int c = c_begin; c < c_end; ++c, ++gp) {
             // here: cur = the period being multiplied, nxt = its successor (if nxt_ok)
-            const unsigned char *const wcur = wchunk(cur.chunk);
-            const unsigned char *const wnxt = wchunk(nxt.chunk);
+            const unsigned char *const wcur = ws.wchunk(cur.chunk);
+            const unsigned char *const wnxt = ws.wchunk(nxt.chunk);
             const bool reload_aff = fuse_in && !D2 && nxt_ok && nxt.n != aff_n;   // (uniform)
             auto step = [&](auto SPc) __attribute__((always_inline)) {
                 constexpr int sp = decltype(SPc)::value;
@@ -467,7 +401,7 @@ conv3d_k3_f16x3_wino_bt_kernel(const float *__restrict__ x, const _Float16 *__re
                     if (BT_ABL & 16) asm volatile("" ::"v"(ah[m]), "v"(bh[t])); else acc[m][t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[m], bh[t], acc[m][t], 0, 0, 0);
                     if constexpr (i < 3) {
                         al[i] = ld_a(SN{}, I, true);
-                        if constexpr (sp == 0 && i == 2) { if (reload_aff && p == 0) dma_aff(nxt.n); }
+                        if constexpr (sp == 0 && i == 2) { if (reload_aff && p == 0) wino_dma_aff(in_affine, nxt.n, Ci, lane, aff_lds); }
                     } else {
                         vm(std::integral_constant<int, 2>{}, I);
                         mop(std::integral_constant<int, (i >= 3 ? i - 3 : 0)>{});
@@ -498,7 +432,7 @@ conv3d_k3_f16x3_wino_bt_kernel(const float *__restrict__ x, const _Float16 *__re
             if (reload_aff) aff_n = nxt.n;
             cur = nxt;
             nxt_ok = gp + 2 < per_total;
-            if (nxt_ok) nxt = period_next(cur);
+            if (nxt_ok) nxt = ws.period_next<D2>(cur);
         }
 
         // ---- output transform + epilogue: six rounds (32-channel row tile x plane pair) through the exchange region; the four positions of a
@@ -516,7 +450,7 @@ conv3d_k3_f16x3_wino_bt_kernel(const float *__restrict__ x, const _Float16 *__re
             continue;
         }
         const int gn_rows = tiles_total * 2;   // channel-major [Co][tile * 2 + plane pair][2] (the finalize kernel reads rows of it)
-        if (gn_part && etile == 0 && tid == 0) gn_part[(size_t)gn_rows * Co * 2] = unscale;   // (behind the partials)
+        if (gn_part && etile == 0 && tid == 0) wino_gn_write_unscale(gn_part, gn_rows, Co, unscale);
         const bool odd = (lane & 1) != 0;
         // (this lane's QUAD of voxels: lanes 2k / 2k+1 store the 4 voxels 4k..4k+3 of a row, for different channels)
         // (D2: plane pair = frame: pair 1 is frame en + 1, d = 0, 1 — absent when N is odd and this is the last tile)
@@ -536,83 +470,21 @@ conv3d_k3_f16x3_wino_bt_kernel(const float *__restrict__ x, const _Float16 *__re
                 const f32x4 bv = *reinterpret_cast<const f32x4 *>(smem + PP_LDS_BIAS + (m * 32 + 8 * P + 4 * kgl) * 4);
 #pragma unroll
                 for (int pair = 0; pair < 2; ++pair) {
-                    // park the units other waves finish: unit u = accumulator registers 4u..4u+3 of a column tile; wave P keeps unit P
-#pragma unroll
-                    for (int tt = 0; tt < 2; ++tt)
-#pragma unroll
-                        for (int u = 0; u < 4; ++u)
-                            if (u != P) {
-                                const int slot = tt * 3 + (u - (u > P ? 1 : 0));
-                                const f32x16 &a = acc[m][2 * pair + tt];
-                                const f32x4 v = {a[4 * u], a[4 * u + 1], a[4 * u + 2], a[4 * u + 3]};
-                                *reinterpret_cast<f32x4 *>(Ex + ((P * 6 + slot) * 64 + lane) * 4) = v;
-                            }
+                    wino_park_units(P, &acc[m][2 * pair], Ex, 0, lane);
                     lds_barrier();
                     float ssum[4] = {0.0f, 0.0f, 0.0f, 0.0f}, qsum[4] = {0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
                     for (int tt = 0; tt < 2; ++tt) {
-                        f32x4 M[4];
-#pragma unroll
-                        for (int q = 0; q < 4; ++q) {
-                            if (q != P) {
-                                const int slot = tt * 3 + (P - (P > q ? 1 : 0));
-                                M[q] = *reinterpret_cast<const f32x4 *>(Ex + ((q * 6 + slot) * 64 + lane) * 4);
-                            } else {
-#pragma unroll
-                                for (int i = 0; i < 4; ++i) M[q][i] = acc[m][2 * pair + tt][4 * q + i];
-                            }
-                        }
-                        float y0[4], y1[4];
-#pragma unroll
-                        for (int i = 0; i < 4; ++i) {
-                            const float r0 = (M[0][i] + M[1][i]) + M[2][i];
-                            const float r1 = (M[1][i] - M[2][i]) - M[3][i];
-                            if (gn_part) {   // (uniform)
-                                ssum[i] += r0 + r1;
-                                qsum[i] = __builtin_fmaf(r0, r0, qsum[i]);
-                                qsum[i] = __builtin_fmaf(r1, r1, qsum[i]);
-                            }
-                            y0[i] = r0 * unscale + bv[i];
-                            y1[i] = r1 * unscale + bv[i];
-                        }
-                        // 16-byte stores: a lane holds one output pair (2 voxels) of 4 channels; lanes 2k / 2k+1 hold neighbouring pairs of a row
-                        // and trade halves (quad_perm [1,0,3,2]): the even lane ends up with 4 consecutive voxels of channels 0-1, the odd lane
-                        // with those of channels 2-3
-#define BT_SWAP(v_) __uint_as_float(__builtin_amdgcn_update_dpp(0, __float_as_uint(v_), 0xB1, 0xf, 0xf, false))
-                        const float g0 = BT_SWAP(odd ? y0[0] : y0[2]), g1 = BT_SWAP(odd ? y1[0] : y1[2]);
-                        const float g2 = BT_SWAP(odd ? y0[1] : y0[3]), g3 = BT_SWAP(odd ? y1[1] : y1[3]);
-#undef BT_SWAP
-                        const f32x4 va = {odd ? g0 : y0[0], odd ? g1 : y1[0], odd ? y0[2] : g0, odd ? y1[2] : g1};
-                        const f32x4 vb = {odd ? g2 : y0[1], odd ? g3 : y1[1], odd ? y0[3] : g2, odd ? y1[3] : g3};
+                        f32x4 M[4], va, vb;
+                        wino_gather_M(P, acc[m][2 * pair + tt], Ex, 0, lane, tt, M);
+                        wino_out_pair(M, bv, unscale, odd, gn_part != nullptr, ssum, qsum, va, vb);
                         unsigned char *const dq = reinterpret_cast<unsigned char *>(ybase + (size_t)(m * 32 + tz) * DHW + pair * pair_stride + (size_t)tt * HW);   // (uniform)
                         if (pair == 0 || pair1_ok) {
                             *reinterpret_cast<f32x4 *>(dq + yoff) = va;
                             *reinterpret_cast<f32x4 *>(dq + (size_t)DHW * 4 + yoff) = vb;
                         }
                     }
-                    if (gn_part) {
-                        // per-channel (sum, sum of squares) of the RAW transformed accumulators over this wave's 2 x 64 voxels of the channel and
-                        // plane pair: the 32 lanes of a half-wave hold one channel's columns (the finalize kernel applies unscale and the bias)
-#pragma unroll
-                        for (int i = 0; i < 4; ++i) {
-#define BT_ROW_ADD(v_, ctrl_) v_ += __uint_as_float(__builtin_amdgcn_update_dpp(0, __float_as_uint(v_), ctrl_, 0xf, 0xf, false));
-                            BT_ROW_ADD(ssum[i], 0x128) BT_ROW_ADD(qsum[i], 0x128)   // row_ror:8, :4, :2, :1 -> every lane of a 16-lane row: the row's sum
-                            BT_ROW_ADD(ssum[i], 0x124) BT_ROW_ADD(qsum[i], 0x124)
-                            BT_ROW_ADD(ssum[i], 0x122) BT_ROW_ADD(qsum[i], 0x122)
-                            BT_ROW_ADD(ssum[i], 0x121) BT_ROW_ADD(qsum[i], 0x121)
-#undef BT_ROW_ADD
-                            // rows 1 and 3 add the totals of rows 0 and 2 (row_bcast:15, row mask 0b1010): lanes 16-31 / 48-63 hold a half-wave's sum
-                            ssum[i] += __uint_as_float(__builtin_amdgcn_update_dpp(0, __float_as_uint(ssum[i]), 0x142, 0xa, 0xf, false));
-                            qsum[i] += __uint_as_float(__builtin_amdgcn_update_dpp(0, __float_as_uint(qsum[i]), 0x142, 0xa, 0xf, false));
-                        }
-                        if (j == 31) {
-#pragma unroll
-                            for (int i = 0; i < 4; ++i) {
-                                const int co = co0 + m * 32 + 8 * P + 4 * kgl + i + tz;
-                                *reinterpret_cast<float2 *>(gn_part + ((size_t)co * gn_rows + (size_t)etile * 2 + pair) * 2) = make_float2(ssum[i], qsum[i]);
-                            }
-                        }
-                    }
+                    if (gn_part) wino_gn_write(gn_part, gn_rows, co0 + m * 32 + 8 * P + 4 * kgl + tz, (size_t)etile * 2 + pair, j, ssum, qsum);
                     lds_barrier();   // the region is rewritten by the next round
                 }
             }
@@ -629,15 +501,7 @@ conv3d_k3_f16x3_wino_bt_kernel(const float *__restrict__ x, const _Float16 *__re
 #endif
     }
 
-    // operands outside the f16 range (non-finite inputs, or finite ones beyond a wrong caller-supplied descriptor) are not clamped — they
-    // propagate as Inf / NaN — but they are counted, per thread that saw any
-    const bool sat_ = xnan_ || xmaxf_ > 0.5f * F16_CLAMP;
-    if (__builtin_amdgcn_ballot_w64(sat_) != 0) {  // never taken in normal operation
-        unsigned tot = sat_;
-#pragma unroll
-        for (int sft = 32; sft >= 1; sft >>= 1) tot += __shfl_xor(tot, sft, 64);
-        if (lane == 0) atomicAdd(&g_f16x3_wino_bt_saturated, (unsigned long long)tot);
-    }
+    wino_count_saturated(xnan_ || xmaxf_ > 0.5f * F16_CLAMP, &g_f16x3_wino_bt_saturated, lane);
 #ifdef MPHIP_BT_PROFILE
     if (lane == 0) {
         const unsigned long long t = bt_memtime();
@@ -650,31 +514,13 @@ conv3d_k3_f16x3_wino_bt_kernel(const float *__restrict__ x, const _Float16 *__re
 }
 
 // ---- host side ---------------------------------------------------------------------------------------------------------------
-int f16x3_wino_bt_saturation(unsigned long long *count, int reset) {
-    if (hipMemcpyFromSymbol(count, HIP_SYMBOL(g_f16x3_wino_bt_saturated), sizeof(unsigned long long)) != hipSuccess) return -1;
-    if (reset) {
-        const unsigned long long z = 0;
-        if (hipMemcpyToSymbol(HIP_SYMBOL(g_f16x3_wino_bt_saturated), &z, sizeof(z)) != hipSuccess) return -1;
-    }
-    return 0;
-}
+int f16x3_wino_bt_saturation(unsigned long long *count, int reset) { return f16x3_counter_read(&g_f16x3_wino_bt_saturated, count, reset); }
 
-void f16x3_wino_bt_launch(dim3 grid, hipStream_t s, hipEvent_t t0, hipEvent_t t1, const float *x, const _Float16 *slabs, const float *hdr,
-                          const float *bias, float *dst, int N, int Ci, int Co, int D, int H, int W, int cps, unsigned xb,
-                          const float *in_affine, int in_relu, const float *x_range, int tiles, int xcd_on, const int *tile_list,
-                          float *gn_part, bool two_frame) {
-#define BT_LAUNCH(F_, D_)                                                                                                                      \
-    {                                                                                                                                          \
-        if (t0 && t1)                                                                                                                          \
-            hipExtLaunchKernelGGL((conv3d_k3_f16x3_wino_bt_kernel<F_, D_>), grid, dim3(256), 0, s, t0, t1, 0, x, slabs, hdr, bias, dst, N, Ci, Co, D, H, \
-                                  W, cps, xb, in_affine, in_relu, x_range, tiles, xcd_on, tile_list, gn_part);                                 \
-        else                                                                                                                                   \
-            hipLaunchKernelGGL((conv3d_k3_f16x3_wino_bt_kernel<F_, D_>), grid, dim3(256), 0, s, x, slabs, hdr, bias, dst, N, Ci, Co, D, H, W, cps, xb,   \
-                               in_affine, in_relu, x_range, tiles, xcd_on, tile_list, gn_part);                                                \
-    }
-    if (two_frame) { if (in_affine) BT_LAUNCH(true, true) else BT_LAUNCH(false, true) }
-    else if (in_affine) BT_LAUNCH(true, false) else BT_LAUNCH(false, false)
-#undef BT_LAUNCH
+void f16x3_wino_bt_launch(dim3 grid, hipStream_t s, hipEvent_t t0, hipEvent_t t1, const F16x3ConvArgs &a, bool two_frame) {
+    auto go = [&](auto kern) { f16x3_wino_launch_kernel(kern, grid, dim3(256), s, t0, t1, a); };
+    if (two_frame) { if (a.in_affine) go(conv3d_k3_f16x3_wino_bt_kernel<true, true>); else go(conv3d_k3_f16x3_wino_bt_kernel<false, true>); }
+    else if (a.in_affine) go(conv3d_k3_f16x3_wino_bt_kernel<true, false>);
+    else go(conv3d_k3_f16x3_wino_bt_kernel<false, false>);
 }
 
 }  // namespace mphip

@@ -20,8 +20,7 @@
 //  MPHIP_PP_PROFILE, PP_PRIO=n                    | conv3d_f16x3_wino_pp.hip   | per-phase wall stamps (mphip_debug_wino_pp_profile); s_setprio policy
 //  MPHIP_BT_PROFILE                               | conv3d_f16x3_wino_bt.hip   | cycles per wave: whole kernel / epilogues / prologue (mphip_debug_wino_bt_profile)
 //  MPHIP_WN_TRACE / MPHIP_K2_TRACE                | conv3d_f16x3_wino / warp   | per-tile / per-workgroup wall-clock traces
-//  MPHIP_F16X3_OLD_FRAGS, MPHIP_BUILTIN_DMA,      | conv3d_f16x3.hip,          | r01's fragment schedule; compiler-issued LDS-DMA; halo write in its own phase
-//    MPHIP_WN_NO_OVERLAP8                         | conv3d_f16x3_wino.hip      |   (same results, other schedules)
+//  MPHIP_F16X3_OLD_FRAGS, MPHIP_BUILTIN_DMA       | conv3d_f16x3.hip           | r01's fragment schedule; compiler-issued LDS-DMA (same results, other schedules)
 #pragma once
 
 #ifndef PP_ABL

@@ -1,5 +1,9 @@
-// Shared between the conv translation units (conv3d.hip: exact fp32 kernels + C ABI; conv3d_f16x3.hip).
+// Shared by every conv translation unit (conv3d.hip: exact fp32 kernels + C ABI; conv3d_f16x3*.hip and their planner; the backward
+// conv), api.hip / plan.hip and the GroupNorm code (norm.hip): buffer-load helpers, the pack / tile layout constants, the plan, the launch
+// contracts.
 #pragma once
+#include <hip/hip_ext.h>
+
 #include "mphip_common.h"
 
 namespace mphip {
@@ -24,6 +28,7 @@ constexpr int F16X3_COT = 96;             // output channels per workgroup (3 MF
 constexpr int SLAB_HALFS = 2 * F16X3_TG * 2 * F16X3_COT * 8;  // [part][tap][kg][co][8] = 9216 halfs = 18432 B
 constexpr int K1_SLAB_HALFS = 2 * 2 * F16X3_COT * 8;   // [part][kg][co][8] = 3072 halfs = 6 KB per (co tile, chunk)
 constexpr int F16X3_AFF_CI = 768;         // fused input GroupNorm table of the direct and two-frame kernels (their AFF_MAX_CI)
+// F(2,3) kernels (conv3d_f16x3_wino*.hip): THE definition of their pack and tile; mphip_wino_tile.h derives its byte-unit PP_* values from these
 constexpr int WN_KC = 16;                                  // input channels per chunk = K of one MFMA
 constexpr int WN_COT = 96;                                 // output channels per workgroup (3 MFMA row tiles)
 constexpr int WN_NG = 9;                                   // (kd,kh) slabs per chunk
@@ -113,28 +118,50 @@ int f16x3_launch(const F16x3Switches &sw, const F16x3Plan &p, const float *x, co
                  float *gn_part = nullptr /* [Co][plan.grid.x][plan.gn_rows][2]: per-wave (sum, sumsq) of the output, splits == 1 only */,
                  hipEvent_t t0 = nullptr, hipEvent_t t1 = nullptr /* stamped with the conv kernel's own begin / end */);
 
-// conv3d_f16x3_wino.hip: the same split-f16 arithmetic in the 1-D Winograd F(2,3) domain (2/3 of the MFMAs), lockstep schedule.  Its
-// slabs live behind the direct slabs of a precision-1 k=3 pack (0 bytes when the layer can never take an F(2,3) kernel).  The three F(2,3)
-// launchers share one contract; f16x3_launch picks among them by F16x3Plan.kernel.
-size_t f16x3_wino_packed_bytes(int Co, int Ci);
-void f16x3_wino_launch(dim3 grid, hipStream_t s, hipEvent_t t0, hipEvent_t t1, const float *x, const _Float16 *slabs, const float *hdr,
-                       const float *bias, float *dst, int N, int Ci, int Co, int D, int H, int W, int cps, unsigned xb,
-                       const float *in_affine, int in_relu, const float *x_range, int tiles, int xcd_on,
-                       const int *tile_list /* demand-driven: {count, tile ids} or NULL */, float *gn_part);
-int f16x3_wino_saturation(unsigned long long *count, int reset);
+// A kernel launch whose begin / end are stamped on t0 / t1 when both are given (the measurement hook's events ride on the kernel command
+// itself, so what another stream's kernel makes the launch WAIT for CUs is not counted as its duration).  The argument types must be the
+// kernel's parameter types.
+template <class K, class... A>
+void launch_timed(K kern, dim3 grid, dim3 block, hipStream_t s, hipEvent_t t0, hipEvent_t t1, A... args) {
+    if (t0 && t1) hipExtLaunchKernelGGL(kern, grid, block, 0, s, t0, t1, 0, args...);
+    else hipLaunchKernelGGL(kern, grid, block, 0, s, args...);
+}
 
-// conv3d_f16x3_wino_pp.hip: the same kernel contract on the role-split ("ping-pong") schedule
-void f16x3_wino_pp_launch(dim3 grid, hipStream_t s, hipEvent_t t0, hipEvent_t t1, const float *x, const _Float16 *slabs, const float *hdr,
-                          const float *bias, float *dst, int N, int Ci, int Co, int D, int H, int W, int cps, unsigned xb,
-                          const float *in_affine, int in_relu, const float *x_range, int tiles, int xcd_on, const int *tile_list,
-                          float *gn_part, bool half_products);
+// The parameters of the 3x3x3 f16x3 forward kernels, in kernarg order (the direct kernels take one more, roi_frames, before gn_part);
+// f16x3_launch fills it once.
+struct F16x3ConvArgs {
+    const float *x;
+    const _Float16 *slabs;
+    const float *hdr, *bias;
+    float *dst;
+    int N, Ci, Co, D, H, W, cps;
+    unsigned xb;
+    const float *in_affine;
+    int in_relu;
+    const float *x_range;
+    int tiles, xcd_on;
+    const int *tile_list;   // demand-driven: {count, tile ids} or NULL
+    float *gn_part;
+};
+template <class K>
+void f16x3_wino_launch_kernel(K kern, dim3 grid, dim3 block, hipStream_t s, hipEvent_t t0, hipEvent_t t1, const F16x3ConvArgs &a) {
+    launch_timed(kern, grid, block, s, t0, t1, a.x, a.slabs, a.hdr, a.bias, a.dst, a.N, a.Ci, a.Co, a.D, a.H, a.W, a.cps, a.xb, a.in_affine,
+                 a.in_relu, a.x_range, a.tiles, a.xcd_on, a.tile_list, a.gn_part);
+}
+
+// The same split-f16 arithmetic in the 1-D Winograd F(2,3) domain (2/3 of the MFMAs).  Its slabs live behind the direct slabs of a
+// precision-1 k=3 pack (0 bytes when the layer can never take an F(2,3) kernel).  Three kernels, one contract; f16x3_launch picks among
+// them by F16x3Plan.kernel.  Each unit keeps a saturation counter (f16x3_counter_read).
+size_t f16x3_wino_packed_bytes(int Co, int Ci);
+// conv3d_f16x3_wino.hip: lockstep schedule (A/B reference)
+void f16x3_wino_launch(dim3 grid, hipStream_t s, hipEvent_t t0, hipEvent_t t1, const F16x3ConvArgs &a);
+int f16x3_wino_saturation(unsigned long long *count, int reset);
+// conv3d_f16x3_wino_pp.hip: role-split ("ping-pong") schedule
+void f16x3_wino_pp_launch(dim3 grid, hipStream_t s, hipEvent_t t0, hipEvent_t t1, const F16x3ConvArgs &a, bool half_products);
 int f16x3_wino_pp_saturation(unsigned long long *count, int reset);
-// conv3d_f16x3_wino_bt.hip: the same contract (three-product arithmetic only) with one wave per SIMD and a 96 x 128 register tile;
-// results bit-identical to the role-split kernel's
-void f16x3_wino_bt_launch(dim3 grid, hipStream_t s, hipEvent_t t0, hipEvent_t t1, const float *x, const _Float16 *slabs, const float *hdr,
-                          const float *bias, float *dst, int N, int Ci, int Co, int D, int H, int W, int cps, unsigned xb,
-                          const float *in_affine, int in_relu, const float *x_range, int tiles, int xcd_on, const int *tile_list,
-                          float *gn_part, bool two_frame);
+// conv3d_f16x3_wino_bt.hip: one wave per SIMD and a 96 x 128 register tile (three-product arithmetic only); results bit-identical to
+// the role-split kernel's
+void f16x3_wino_bt_launch(dim3 grid, hipStream_t s, hipEvent_t t0, hipEvent_t t1, const F16x3ConvArgs &a, bool two_frame);
 int f16x3_wino_bt_saturation(unsigned long long *count, int reset);
 
 // api.hip: the calling thread's conv arithmetic policy (mphip_conv3d_set_half_products): true inside torch.autocast(float16) regions

@@ -1,4 +1,4 @@
-// Shared by the split-f16 ("f16x3") conv translation units (conv3d_f16x3.hip, conv3d_f16x3_wino.hip, mfma_sol.hip).
+// Shared by the split-f16 ("f16x3") conv translation units (conv3d_f16x3.hip, conv3d_f16x3_wino*.hip, mfma_sol.hip).
 #pragma once
 #include "mphip_common.h"
 
@@ -47,5 +47,14 @@ __device__ __forceinline__ void lds_dma_wait() {
 }
 // workgroup barrier that publishes LDS writes and finished LDS reads only (no vmcnt drain: stores and LDS-DMA stay in flight)
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+
+// host: reads a translation unit's saturation counter (a __device__ unsigned long long; `symbol` = its address) and optionally clears it.
+// Every f16x3 conv unit keeps one; mphip_f16x3_saturation_count sums them.
+inline int f16x3_counter_read(const void *symbol, unsigned long long *count, int reset) {
+    if (hipMemcpyFromSymbol(count, symbol, sizeof(unsigned long long)) != hipSuccess) return -1;
+    const unsigned long long z = 0;
+    if (reset && hipMemcpyToSymbol(symbol, &z, sizeof(z)) != hipSuccess) return -1;
+    return 0;
+}
 
 }  // namespace mphip

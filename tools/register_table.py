@@ -1,6 +1,9 @@
 """Register / scratch / LDS table of every kernel in megaportrait-hack_amd/csrc/*.hip at HEAD: compiles each
 translation unit for gfx950 to assembly (no GPU needed) and reads the amdhsa kernel metadata hipcc emits.
 usage: python tools/register_table.py [out.json]     (default: print)
+       python tools/register_table.py --skeleton [csrc dir]    the F(2,3) conv kernels only: metadata + a hash of each kernel's "skeleton", the
+           ordered list of its MFMAs, LDS-DMA pieces, buffer loads, global stores, barriers and s_waitcnt vmcnt(N) — what the hand-counted
+           waits of those kernels rest on.  [csrc dir]: another checkout's csrc (profiles/wino_shared_isa.json compares two commits this way).
 The CPU test tests/test_host.py::test_hot_kernels_have_no_scratch uses collect() on the hot translation units."""
 import concurrent.futures, hashlib, json, os, re, subprocess, sys
 
@@ -32,7 +35,20 @@ def demangle(names):
     return out
 
 
-def one(path):
+SKELETON = re.compile(r"^\s+(v_mfma\w*|global_load_lds\w*|buffer_load\w*|global_store\w*|s_barrier\b|s_waitcnt\b.*?(vmcnt\(\d+\)))")
+WINO = ("conv3d_f16x3_wino.hip", "conv3d_f16x3_wino_pp.hip", "conv3d_f16x3_wino_bt.hip")
+
+
+def skeleton(asm, name):
+    """Hash of kernel `name`'s (mangled) skeleton in the order of the assembly text, and of the sorted list: a cold block that hipcc
+    places elsewhere in the text (same instructions, same execution order) changes the first and not the second."""
+    body = asm[asm.index("\n" + name + ":"):]
+    ops = [m.group(2) or m.group(1) for m in map(SKELETON.match, body[:body.index(".Lfunc_end")].splitlines()) if m]
+    sha = lambda o: hashlib.sha256("\n".join(o).encode()).hexdigest()
+    return {"skeleton_sha256": sha(ops), "skeleton_sorted_sha256": sha(sorted(ops)), "skeleton_ops": len(ops), "mfma": sum(o.startswith("v_mfma") for o in ops)}
+
+
+def one(path, with_skeleton=False):
     asm = subprocess.run([HIPCC] + FLAGS + EXTRA.get(os.path.basename(path), []) + [path], capture_output=True, text=True)
     if asm.returncode != 0:
         raise RuntimeError(f"{path}: {asm.stderr[-2000:]}")
@@ -67,16 +83,18 @@ def one(path):
             mm = re.search(re.escape(key) + r":\s*(\d+)", e)
             if mm:
                 k[key[1:]] = int(mm.group(1))
+        if with_skeleton:
+            k.update(skeleton(asm.stdout, k["name"]))
         kernels.append(k)
     for k, d in zip(kernels, demangle([k["name"] for k in kernels])):
         k["demangled"] = d
     return {"sha256": hashlib.sha256(open(path, "rb").read()).hexdigest(), "kernels": kernels, "asm": asm.stdout if os.environ.get("MPHIP_KEEP_ASM") else None}
 
 
-def collect(files=None):
-    files = files or sorted(f for f in os.listdir(CSRC) if f.endswith(".hip"))
+def collect(files=None, csrc=CSRC, with_skeleton=False):
+    files = files or sorted(f for f in os.listdir(csrc) if f.endswith(".hip"))
     with concurrent.futures.ThreadPoolExecutor(max_workers=min(8, len(files))) as ex:
-        res = list(ex.map(lambda f: one(os.path.join(CSRC, f)), files))
+        res = list(ex.map(lambda f: one(os.path.join(csrc, f), with_skeleton), files))
     return dict(zip(files, res))
 
 
@@ -87,7 +105,10 @@ def head_commit():
         return None
 
 
-if __name__ == "__main__":
+if __name__ == "__main__" and sys.argv[1:2] == ["--skeleton"]:
+    files = collect(WINO, sys.argv[2] if len(sys.argv) > 2 else CSRC, with_skeleton=True)
+    print(json.dumps({f: [{k: v for k, v in kern.items() if k != "name"} for kern in t["kernels"]] for f, t in files.items()}, indent=1))
+elif __name__ == "__main__":
     table = {"_what": "amdhsa metadata of every kernel (hipcc --offload-arch=gfx950 -O3 -S), per translation unit; private_segment_fixed_size = "
                       "scratch bytes per lane", "_commit": head_commit(), "files": collect()}
     worst = sorted(((k.get("private_segment_fixed_size", 0), f, k["demangled"]) for f, t in table["files"].items() for k in t["kernels"]), reverse=True)[:8]
