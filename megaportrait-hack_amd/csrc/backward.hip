@@ -145,6 +145,14 @@ __device__ __forceinline__ float act_grad(float dy, float y, int act) {
 }
 
 constexpr int GNB_CHUNK = 8192;  // floats per workgroup of the reduce pass
+// four consecutive floats: one 16-byte load, or (a pointer that is not 16-byte aligned) four 4-byte loads of the same values
+template <bool ALIGNED>
+__device__ __forceinline__ float4 gn_load4(const float *__restrict__ p) {
+    if (ALIGNED) return *reinterpret_cast<const float4 *>(p);
+    return make_float4(p[0], p[1], p[2], p[3]);
+}
+// ALIGNED: x, y and dy are 16-byte aligned.  Both instantiations add the same values in the same order (same bits).
+template <bool ALIGNED>
 __global__ void __launch_bounds__(256)
 gn_bwd_reduce_kernel(const float *__restrict__ x, const float *__restrict__ y, const float *__restrict__ dy,
                      const float *__restrict__ stats, float *__restrict__ partial, int C, int cpg, int S, int relu, int chunks) {
@@ -157,11 +165,11 @@ gn_bwd_reduce_kernel(const float *__restrict__ x, const float *__restrict__ y, c
     float s1 = 0.0f, s2 = 0.0f;
     if ((S & 3) == 0) {
         for (int i = begin + threadIdx.x * 4; i < end; i += 1024) {
-            const float4 g = *reinterpret_cast<const float4 *>(dy + base + i);
-            const float4 xv = *reinterpret_cast<const float4 *>(x + base + i);
+            const float4 g = gn_load4<ALIGNED>(dy + base + i);
+            const float4 xv = gn_load4<ALIGNED>(x + base + i);
             float du[4] = {g.x, g.y, g.z, g.w};
             if (relu) {
-                const float4 yv = *reinterpret_cast<const float4 *>(y + base + i);
+                const float4 yv = gn_load4<ALIGNED>(y + base + i);
                 du[0] = act_grad(du[0], yv.x, relu);
                 du[1] = act_grad(du[1], yv.y, relu);
                 du[2] = act_grad(du[2], yv.z, relu);
@@ -860,6 +868,16 @@ extern "C" size_t mphip_groupnorm_bwd_workspace_bytes(int N, int C, int S) {
     return N > 0 && C > 0 && S > 0 ? ((size_t)N * C * cdiv(S, GNB_CHUNK) * 2 + (size_t)N * C * 2) * sizeof(float) : 0;
 }
 
+// the reduce pass reads x, dy (and y) four floats at a time when S % 4 == 0: 16-byte loads only where all three pointers allow them
+static void gn_bwd_reduce_launch(const float *x, const float *y, const float *dy, const float *stats, float *partial, int N, int C, int cpg,
+                                 int S, int relu, int chunks, hipStream_t s) {
+    const bool aligned = (((uintptr_t)x | (uintptr_t)dy | (uintptr_t)(y ? y : x)) & 15) == 0;
+    if (aligned)
+        hipLaunchKernelGGL(gn_bwd_reduce_kernel<true>, dim3(N * C * chunks), dim3(256), 0, s, x, y, dy, stats, partial, C, cpg, S, relu, chunks);
+    else
+        hipLaunchKernelGGL(gn_bwd_reduce_kernel<false>, dim3(N * C * chunks), dim3(256), 0, s, x, y, dy, stats, partial, C, cpg, S, relu, chunks);
+}
+
 extern "C" int mphip_groupnorm_bwd_reduce(const float *x, const float *y, const float *dy, const float *stats,
                                           const float *gamma, const float *beta, const float *w2, float *dgamma, float *dbeta,
                                           float *dw2, float *db2, float *ab, int N, int C, int S, int G, int act,
@@ -877,8 +895,7 @@ extern "C" int mphip_groupnorm_bwd_reduce(const float *x, const float *y, const 
     const int chunks = cdiv(S, GNB_CHUNK);
     float *partial = (float *)workspace, *s12 = partial + (size_t)N * C * chunks * 2;
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(gn_bwd_reduce_kernel, dim3(N * C * chunks), dim3(256), 0, s, x, y, dy, stats, partial, C, C / G, S, relu,
-                       chunks);
+    gn_bwd_reduce_launch(x, y, dy, stats, partial, N, C, C / G, S, relu, chunks, s);
     hipLaunchKernelGGL(gn_bwd_fold_kernel, dim3(1), dim3(1024), 0, s, (const float *)partial, gamma, beta, w2, s12, dgamma, dbeta,
                        dw2, db2, ab, N, C, C / G, S, chunks);
     return check_launch("groupnorm_bwd_reduce");
@@ -917,7 +934,7 @@ extern "C" int mphip_groupnorm_bwd(const float *x, const float *y, const float *
     const int chunks = cdiv(S, GNB_CHUNK);
     float *partial = (float *)workspace;
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(gn_bwd_reduce_kernel, dim3(N * C * chunks), dim3(256), 0, s, x, y, dy, stats, partial, C, C / G, S, relu, chunks);
+    gn_bwd_reduce_launch(x, y, dy, stats, partial, N, C, C / G, S, relu, chunks, s);
     const size_t total = (size_t)N * C * S;
     const bool aligned = (((uintptr_t)x | (uintptr_t)dy | (uintptr_t)dx | (uintptr_t)(y ? y : x) | (uintptr_t)(dres ? dres : dx)) & 15) == 0;
     if (S % 4 == 0 && S >= 512 && aligned && (size_t)N * C <= 65535)

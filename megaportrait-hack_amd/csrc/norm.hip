@@ -308,10 +308,9 @@ __global__ void __launch_bounds__(256) gn_apply_pool_kernel(GnParams p, int D, i
                 const float4 r4 = has_res ? *reinterpret_cast<const float4 *>(p.residual + o) : make_float4(0, 0, 0, 0);
                 rv[0] = r4.x; rv[1] = r4.y; rv[2 * PW - 2] = r4.z; rv[2 * PW - 1] = r4.w;
             } else {
-                const float2 x2 = *reinterpret_cast<const float2 *>(p.x + o);
-                xv[0] = x2.x; xv[1] = x2.y;
-                const float2 r2 = has_res ? *reinterpret_cast<const float2 *>(p.residual + o) : make_float2(0, 0);
-                rv[0] = r2.x; rv[1] = r2.y;
+                // (4-byte accesses: this is also the form for pointers that are not 16-byte aligned)
+                xv[0] = p.x[o]; xv[1] = p.x[o + 1];
+                rv[0] = has_res ? p.residual[o] : 0.0f; rv[1] = has_res ? p.residual[o + 1] : 0.0f;
             }
 #pragma unroll
             for (int q = 0; q < PW; ++q) {
@@ -1021,16 +1020,17 @@ extern "C" int mphip_groupnorm_apply(const float *x, const float *stats, const f
     GnParams p{x, stats, gamma, beta, w2, b2, residual, y, C, C / G, relu, tanh_, out_range};
     hipStream_t s = (hipStream_t)stream;
     const int S = D * H * W;
+    const bool aligned = (((uintptr_t)p.x | (uintptr_t)p.y | (uintptr_t)p.residual) & 15) == 0;   // 16-byte loads / stores are possible
     if (pool2) {
         MPHIP_REQUIRE(D % 2 == 0 && H % 2 == 0 && W % 2 == 0, "groupnorm_apply: pool2 needs even D,H,W");
         size_t total = (size_t)N * C * (D / 2) * (H / 2) * (W / 2);
-        if (W % 4 == 0 && (((uintptr_t)p.x | (uintptr_t)p.y | (uintptr_t)p.residual) & 15) == 0) {
+        if (W % 4 == 0 && aligned) {
             total /= 2;
             hipLaunchKernelGGL(gn_apply_pool_kernel<2>, dim3(range_grid(total, out_range)), dim3(256), 0, s, p, D, H, W, total);
         } else {
             hipLaunchKernelGGL(gn_apply_pool_kernel<1>, dim3(range_grid(total, out_range)), dim3(256), 0, s, p, D, H, W, total);
         }
-    } else if (S % 4 == 0) {
+    } else if (S % 4 == 0 && aligned) {
         size_t total = (size_t)N * C * S / 4;
         hipLaunchKernelGGL(gn_apply_kernel<4>, dim3(range_grid(total, out_range)), dim3(256), 0, s, p, S, total);
     } else {

@@ -1208,6 +1208,8 @@ def small_gemm(a: torch.Tensor, b: torch.Tensor, trans_a: bool = False, trans_b:
     a, b = _req(a, "a"), _req(b, "b")
     if a2 is not None:
         a2 = _req(a2, "a2")
+    if bias is not None:
+        bias = _req(bias.detach(), "bias")
     m, k = (a.shape[1], a.shape[0]) if trans_a else (a.shape[0], a.shape[1])
     k2, n = (b.shape[1], b.shape[0]) if trans_b else (b.shape[0], b.shape[1])
     if k != k2:

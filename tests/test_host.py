@@ -377,3 +377,164 @@ def test_big_tile_conv_hand_issued_memory_ops_are_padded_and_counted(monkeypatch
             else:
                 run += 1
         assert sorted(gaps)[len(gaps) // 2] <= 4 and sum(gaps) / len(gaps) < 6.0, (sorted(gaps)[len(gaps) // 2], sum(gaps) / len(gaps))
+
+
+def test_aux_entry_argument_checks_return_before_any_launch(lib):
+    """The resamplers, the two small GEMMs and the GroupNorm backward validate pointers, dims and workspace on the host and return
+    before any launch (the pointers below are never dereferenced)."""
+    p = ctypes.c_void_p(16)
+    EINVAL, EWORKSPACE = -1, -3
+    # small_gemm(a, a2, b, bias, out, M, N, K, sam, sak, sbk, sbn, stream): a2 and bias are optional
+    assert lib.mphip_small_gemm(None, None, p, None, p, 2, 2, 2, 2, 1, 2, 1, None) == EINVAL
+    assert b"small_gemm: null pointer" in lib.mphip_last_error()
+    assert lib.mphip_small_gemm(p, None, None, None, p, 2, 2, 2, 2, 1, 2, 1, None) == EINVAL
+    assert lib.mphip_small_gemm(p, None, p, None, None, 2, 2, 2, 2, 1, 2, 1, None) == EINVAL
+    for m, n, k in ((0, 2, 2), (2, 0, 2), (2, 2, 0), (-1, 2, 2)):
+        assert lib.mphip_small_gemm(p, None, p, None, p, m, n, k, 2, 1, 2, 1, None) == EINVAL
+        assert b"small_gemm: bad dims" in lib.mphip_last_error()
+    # add_matmul(a, a2, m, bias, out, B, K, N, trans, stream)
+    assert lib.mphip_add_matmul(None, None, p, None, p, 1, 4, 4, 0, None) == EINVAL
+    assert b"add_matmul: null pointer" in lib.mphip_last_error()
+    assert lib.mphip_add_matmul(p, None, None, None, p, 1, 4, 4, 0, None) == EINVAL
+    assert lib.mphip_add_matmul(p, None, p, None, None, 1, 4, 4, 1, None) == EINVAL
+    for b, k, n in ((0, 4, 4), (1, 0, 4), (1, 4, 0)):
+        for trans in (0, 1):
+            assert lib.mphip_add_matmul(p, None, p, None, p, b, k, n, trans, None) == EINVAL
+            assert b"add_matmul: bad dims" in lib.mphip_last_error()
+    # the x2 trilinear upsample and its adjoint
+    assert lib.mphip_upsample_trilinear2(None, p, 1, 2, 2, 2, None) == EINVAL
+    assert lib.mphip_upsample_trilinear2(p, None, 1, 2, 2, 2, None) == EINVAL
+    assert lib.mphip_upsample_trilinear2_bwd(None, p, 1, 2, 2, 2, None, 0, None) == EINVAL
+    assert lib.mphip_upsample_trilinear2_bwd(p, None, 1, 2, 2, 2, None, 0, None) == EINVAL
+    for dims in ((0, 2, 2, 2), (1, 0, 2, 2), (1, 2, 0, 2), (1, 2, 2, 0), (1, 2, 2, -2)):
+        assert lib.mphip_upsample_trilinear2(p, p, *dims, None) == EINVAL
+        assert lib.mphip_upsample_trilinear2_bwd(p, p, *dims, None, 0, None) == EINVAL
+        assert lib.mphip_upsample_trilinear2_bwd_workspace_bytes(*dims) == 0
+    need = lib.mphip_upsample_trilinear2_bwd_workspace_bytes(3, 2, 4, 4)
+    assert need == 3 * 2 * 4 * 4 * 6 * 4                                      # [NC,D,2H,2W] and [NC,D,H,2W] floats
+    assert lib.mphip_upsample_trilinear2_bwd(p, p, 3, 2, 4, 4, p, need - 1, None) == EWORKSPACE
+    assert b"upsample_trilinear2_bwd: workspace" in lib.mphip_last_error()
+    # the scaled trilinear upsample, its adjoint (dx: 16-byte aligned, a multiple of 16 bytes), nearest and its adjoint
+    for fn in (lib.mphip_upsample_trilinear, lib.mphip_upsample_trilinear_bwd, lib.mphip_upsample_nearest, lib.mphip_upsample_nearest_bwd):
+        assert fn(None, p, 1, 2, 2, 2, 2, 2, 2, None) == EINVAL
+        assert b"null pointer" in lib.mphip_last_error()
+        assert fn(p, None, 1, 2, 2, 2, 2, 2, 2, None) == EINVAL
+        for args in ((0, 2, 2, 2, 2, 2, 2), (1, 0, 2, 2, 2, 2, 2), (1, 2, 0, 2, 2, 2, 2), (1, 2, 2, 0, 2, 2, 2), (1, 2, 2, 2, 0, 2, 2),
+                     (1, 2, 2, 2, 2, 0, 2), (1, 2, 2, 2, 2, 2, 0), (1, 2, 2, 2, 2, 2, -1)):
+            assert fn(p, p, *args, None) == EINVAL
+            assert b"bad dims" in lib.mphip_last_error()
+    assert lib.mphip_upsample_trilinear_bwd(p, ctypes.c_void_p(20), 1, 2, 2, 2, 2, 2, 2, None) == EINVAL     # dx 4 bytes past a 16-byte boundary
+    assert b"16-byte aligned" in lib.mphip_last_error()
+    assert lib.mphip_upsample_trilinear_bwd(p, p, 1, 1, 1, 3, 2, 2, 2, None) == EINVAL                       # 3 floats: not a multiple of 16 bytes
+    # avgpool2_bwd: D, H, W are the dims of dx and must be even
+    assert lib.mphip_avgpool2_bwd(None, p, 1, 2, 2, 2, None) == EINVAL
+    assert lib.mphip_avgpool2_bwd(p, None, 1, 2, 2, 2, None) == EINVAL
+    for dims in ((1, 3, 2, 2), (1, 2, 3, 2), (1, 2, 2, 3), (0, 2, 2, 2), (1, 2, 2, 0)):
+        assert lib.mphip_avgpool2_bwd(p, p, *dims, None) == EINVAL
+        assert b"avgpool2_bwd: bad dims" in lib.mphip_last_error()
+    # upsample_trilinear2_roi(x, y, roi, roi_frames, N, C, D, H, W, tD, tH, tW, stream): W even; roi_frames > 0 means ONE volume, many boxes
+    assert lib.mphip_upsample_trilinear2_roi(p, p, None, 0, 1, 2, 2, 2, 2, 2, 8, 8, None) == EINVAL
+    assert lib.mphip_upsample_trilinear2_roi(p, p, p, 0, 1, 2, 2, 2, 3, 2, 8, 8, None) == EINVAL
+    assert b"upsample_trilinear2_roi: bad dims" in lib.mphip_last_error()
+    assert lib.mphip_upsample_trilinear2_roi(p, p, p, 0, 1, 2, 2, 2, 2, 0, 8, 8, None) == EINVAL
+    assert lib.mphip_upsample_trilinear2_roi(p, p, p, 3, 2, 2, 2, 2, 2, 2, 8, 8, None) == EINVAL
+    assert b"roi_frames > 0 needs N == 1" in lib.mphip_last_error()
+    assert lib.mphip_upsample_trilinear2_roi(p, p, p, -1, 1, 2, 2, 2, 2, 2, 8, 8, None) == EINVAL
+    # groupnorm_bwd(x, y, dy, stats, gamma, beta, w2, dx, dres, dgamma, dbeta, dw2, db2, N, C, S, G, act, workspace, bytes, stream)
+    gn = lambda act, ws, nbytes, y=p, w2=None, c=64, g=32: lib.mphip_groupnorm_bwd(p, y, p, p, p, None, w2, p, None, p, p, None, None, 2, c, 512, g,
+                                                                                    act, ws, nbytes, None)
+    need = lib.mphip_groupnorm_bwd_workspace_bytes(2, 64, 512)
+    assert need == (2 * 64 * 1 * 2 + 2 * 64 * 2) * 4 and lib.mphip_groupnorm_bwd_workspace_bytes(2, 64, 0) == 0
+    assert gn(1, p, need - 1) == EWORKSPACE and b"groupnorm_bwd: workspace" in lib.mphip_last_error()
+    assert gn(0, None, need) == EWORKSPACE
+    for act in (-1, 3):
+        assert gn(act, p, need) == EINVAL and b"act must be" in lib.mphip_last_error()
+    assert gn(1, p, need, y=None) == EINVAL                          # an activation needs the forward output
+    assert gn(0, p, need, w2=p) == EINVAL                            # the second affine needs beta, dw2 and db2
+    assert gn(0, p, need, c=60) == EINVAL and b"groupnorm_bwd: bad dims" in lib.mphip_last_error()    # C % G
+    # the three-launch pair shares the rules
+    assert lib.mphip_groupnorm_bwd_reduce(p, p, p, p, p, None, None, p, p, None, None, p, 2, 64, 512, 32, 3, p, need, None) == EINVAL
+    assert lib.mphip_groupnorm_bwd_reduce(p, p, p, p, p, None, None, p, p, None, None, p, 2, 64, 512, 32, 1, p, need - 1, None) == EWORKSPACE
+    assert lib.mphip_groupnorm_bwd_apply(p, None, p, p, p, None, p, p, None, 2, 64, 512, 32, 1, None) == EINVAL
+    assert lib.mphip_groupnorm_bwd_apply(p, p, p, p, p, None, p, p, None, 2, 64, 0, 32, 1, None) == EINVAL
+
+
+# include/mphip.h entries that are not operations: lifecycle, queries (sizes, support, variants, flags) and measurement / debug hooks
+NOT_OPERATIONS = [
+    "mphip_version", "mphip_build_flags", "mphip_graph_memset_nodes_left", "mphip_conv3d_supported", "mphip_flowfield_conv_gn_supported",
+    "mphip_conv3d_bwd_weight_supported", "mphip_conv3d_splits", "mphip_conv3d_roi_granule", "mphip_conv3d_kernel_variant",
+    "mphip_conv3d_set_half_products", "mphip_f16x3_saturation_count", "mphip_pack_table_create", "mphip_pack_table_destroy",
+    "mphip_hot_slice_plan_create", "mphip_hot_slice_plan_set_tables", "mphip_hot_slice_plan_set_precision", "mphip_hot_slice_plan_profile",
+    "mphip_hot_slice_plan_profile_read", "mphip_hot_slice_plan_refresh",
+    "mphip_debug_conv3d_plan", "mphip_debug_mfma_sol", "mphip_debug_dma_stream",
+]
+# operation entries that no test file names: entry -> (source file that calls it, the wrapper there, a test that runs the wrapper).
+# "csrc/plan.hip" entries are launched by the C plan only: the wrapper is the plan's forward, the test compares it bitwise with the Python schedule.
+_PLAN = ("megaportrait-hack_amd/csrc/plan.hip", "mphip_hot_slice_forward", "tests/test_gpu_plan.py::test_plan_equals_python_schedule_bitwise")
+_OPS = "megaportrait-hack_amd/ops.py"
+COVERED_THROUGH_WRAPPER = {
+    "mphip_conv3d_bwd_data": (_OPS, "conv3d_bwd_data", "tests/test_gpu_backward.py::test_conv3d_bwd_data"),
+    "mphip_conv3d_bwd_weight": (_OPS, "conv3d_bwd_weight", "tests/test_gpu_backward.py::test_conv3d_bwd_weight"),
+    "mphip_conv3d_bwd_weight_roi": (_OPS, "conv3d_bwd_weight", "tests/test_gpu_plan.py::test_demand_driven_conv_backward_equals_the_full_backward"),
+    "mphip_conv3d_fwd_split": (_OPS, "conv3d_split", "tests/test_gpu_parity.py::test_split_aware_groupnorm_chain"),
+    "mphip_conv3d_gn_table_fwd": _PLAN,
+    "mphip_flowfield_compact_weight": _PLAN,
+    "mphip_flowfield_conv_gn_compact": _PLAN,
+    "mphip_warp_volume_dsum_coords": _PLAN,
+    "mphip_grad_prep": (_OPS, "grad_prep", "tests/test_gpu_backward.py::test_conv3d_bwd_weight"),
+    "mphip_groupnorm_apply_split": (_OPS, "groupnorm_apply", "tests/test_gpu_parity.py::test_split_aware_groupnorm_chain"),
+    "mphip_groupnorm_small_fused": (_OPS, "groupnorm_small", "tests/test_gpu_parity.py::test_split_aware_groupnorm_chain"),
+    "mphip_groupnorm_stats_split": (_OPS, "groupnorm_stats", "tests/test_gpu_groupnorm_stats.py::test_groupnorm_stats_split_k"),
+    "mphip_pack_conv_weight_bwd_data": (_OPS, "PackedConv", "tests/test_gpu_backward.py::test_conv3d_bwd_data"),
+    "mphip_pack_conv_weight_bwd_data_like": (_OPS, "PackedConv", "tests/test_gpu_backward.py::test_conv3d_bwd_data"),
+    "mphip_pack_table_run": (_OPS, "PackTable", "tests/test_gpu_backward.py::test_pack_table_rewrites_every_pack_bitwise"),
+    "mphip_rt_theta": (_OPS, "rt_theta", "tests/test_gpu_parity.py::test_rt_theta"),
+    "mphip_rt_theta_bwd": (_OPS, "rt_theta_bwd", "tests/test_gpu_backward.py::test_rt_theta_backward"),
+    "mphip_warp_field_compose_bwd": (_OPS, "warp_field_compose_bwd", "tests/test_gpu_backward.py::test_warp_field_compose_backward"),
+    "mphip_warp_sample_box": _PLAN,
+    "mphip_warp_volume_bwd": (_OPS, "warp_volume_bwd", "tests/test_gpu_backward.py::test_warp_volume_backward_dense_equals_tiled_at_full_size"),
+    "mphip_warp_volume_dsum_shared": (_OPS, "warp_volume_dsum", "tests/test_gpu_parity.py::test_full_size_properties"),
+}
+
+
+def test_every_operation_entry_of_the_header_is_named_by_a_test():
+    """Keeps the gap closed: an `int mphip_*` operation entry of include/mphip.h must be named in a test file, or be listed above with the
+    wrapper that reaches it and a test that runs that wrapper (both must exist).  A new entry point with no test fails here."""
+    hdr = open(os.path.join(ROOT, "include", "mphip.h")).read()
+    entries = sorted(set(re.findall(r"^int\s+(mphip_[a-z0-9_]+)\s*\(", hdr, flags=re.M)))
+    assert len(entries) >= 70 and "mphip_small_gemm" in entries and "mphip_upsample_nearest_bwd" in entries
+    assert set(NOT_OPERATIONS) <= set(entries), sorted(set(NOT_OPERATIONS) - set(entries))
+    tests_dir = os.path.join(ROOT, "tests")
+    this = os.path.basename(__file__)
+    text = {}
+    for dirpath, _, files in os.walk(tests_dir):
+        for f in files:
+            if f.endswith((".py", ".c")) and "__pycache__" not in dirpath:
+                text[os.path.relpath(os.path.join(dirpath, f), ROOT)] = open(os.path.join(dirpath, f)).read()
+    # in this file the lists above name entries without testing them: only its test bodies count
+    own = text[os.path.join("tests", this)]
+    text[os.path.join("tests", this)] = own[:own.index("NOT_OPERATIONS = [")] + own[own.index("def test_every_operation_entry"):]
+    autograd_src = open(os.path.join(ROOT, "megaportrait-hack_amd", "autograd.py")).read()
+    missing = []
+    for e in entries:
+        if e in NOT_OPERATIONS:
+            continue
+        if any(re.search(r"\b%s\b" % e, t) for t in text.values()):
+            assert e not in COVERED_THROUGH_WRAPPER, f"{e} is named by a test now: drop it from COVERED_THROUGH_WRAPPER"
+            continue
+        if e not in COVERED_THROUGH_WRAPPER:
+            missing.append(e)
+            continue
+        source, wrapper, test_id = COVERED_THROUGH_WRAPPER[e]
+        src = open(os.path.join(ROOT, source)).read()
+        assert re.search(r"\b%s\b" % e, src), f"{source} does not call {e}"
+        assert re.search(r"^(def|class) %s\b" % wrapper, src, flags=re.M) or (source.endswith(".hip") and re.search(r"\b%s\(" % wrapper, src)), \
+            f"{source} has no {wrapper}"
+        path, func = test_id.split("::")
+        assert re.search(r"^def %s\(" % func, text[path], flags=re.M), f"{test_id} does not exist"
+        if source == _OPS:   # the test file uses the wrapper, or an autograd Function whose body calls it
+            fns = [m.group(1) for m in re.finditer(r"^class (\w+)\(.*?(?=^class |\Z)", autograd_src, flags=re.M | re.S)
+                   if re.search(r"\bops\.%s\(" % wrapper, m.group(0))]
+            assert any(re.search(r"\b%s\b" % n, text[path]) for n in [wrapper] + fns), f"{path} never uses ops.{wrapper}"
+    assert not missing, f"operation entries of mphip.h that no test names and COVERED_THROUGH_WRAPPER does not map: {missing}"
+    assert not set(COVERED_THROUGH_WRAPPER) - set(entries)
