@@ -5,6 +5,8 @@
 #include <stdint.h>
 #include <stdio.h>
 
+#include <type_traits>
+
 #include "../../include/mphip.h"
 
 namespace mphip {
@@ -171,6 +173,19 @@ template <> __device__ __forceinline__ bf16_bits narrow<MPHIP_DTYPE_BF16>(float 
     bf16_bits r;
     r.u = v != v ? (unsigned short)0x7FC0u : (unsigned short)((u + 0x7FFFu + ((u >> 16) & 1u)) >> 16);
     return r;
+}
+
+// Runtime dtype -> template argument: f(std::integral_constant<int, MPHIP_DTYPE_*>{}) for the dtype given, its result returned.  An unknown
+// dtype is MPHIP_EINVAL with the message "<unknown> <dtype>" (`unknown`: e.g. "warp_volume: unknown source dtype").
+template <typename F>
+inline int dispatch_dtype(int dtype, const char *unknown, F &&f) {
+    switch (dtype) {
+        case MPHIP_DTYPE_F32: return f(std::integral_constant<int, MPHIP_DTYPE_F32>{});
+        case MPHIP_DTYPE_F16: return f(std::integral_constant<int, MPHIP_DTYPE_F16>{});
+        case MPHIP_DTYPE_BF16: return f(std::integral_constant<int, MPHIP_DTYPE_BF16>{});
+    }
+    set_error("%s %d", unknown, dtype);
+    return MPHIP_EINVAL;
 }
 
 // value of a split-K tensor element: slab[0][o] + slab[1][o] + ... (z ascending, the reduce kernel's order).

@@ -303,3 +303,64 @@ def test_mixed_dtype_module_raises():
     inp = _hot_inputs(1, 51, torch.float16)
     with torch.no_grad(), pytest.raises(RuntimeError, match="mix dtypes"):
         hot(**inp)
+
+
+# ------------------------------------------------------------------ 8. the untyped warp entry points forward to the typed implementations
+def _small_field(b, d, h, w, kind):
+    g = torch.Generator(device="cpu").manual_seed(29)
+    f = ((torch.rand(b, 3, d, h, w, generator=g) - 0.5) * 2.0).to(DEV)   # samples in the low corner (_fields)
+    if kind == "travelling":   # samples spread over the whole volume
+        f[:, 0] += torch.linspace(0, w - 1, w, device=DEV).view(1, 1, 1, w)
+        f[:, 1] += torch.linspace(0, h - 1, h, device=DEV).view(1, 1, h, 1)
+        f[:, 2] += torch.linspace(0, d - 1, d, device=DEV).view(1, d, 1, 1)
+    return f
+
+
+@pytest.mark.parametrize("kind", ["corner", "travelling"])
+@pytest.mark.parametrize("w", [8, 6])   # (6: W % 4 != 0, the scalar fallback of mphip_warp_volume)
+def test_untyped_warp_entries_equal_typed_entries_with_f32(kind, w):
+    """Every forwarded pair: the `_typed` entry point given MPHIP_DTYPE_F32 writes exactly what the untyped entry point writes."""
+    lib, P, S = _lib.load(), ops._ptr, ops._stream
+    b, c, d, h = 2, 6, 4, 8
+    f32 = ops.dtype_code(torch.float32)
+    v = torch.randn(b, c, d, h, w, device=DEV) * 2.0
+    field = _small_field(b, d, h, w, kind)
+    tables = [ops.linspace_table(n, v.device) for n in (d, h, w)]
+    lin = [P(t) for t in tables]
+    img_bytes = lib.mphip_warp_corner_image_bytes(b, c)
+    ws_bytes = lib.mphip_warp_workspace_bytes(b, d, h, w) + img_bytes
+    new = lambda shape, fill, dtype=torch.float32: torch.full(shape, fill, dtype=dtype, device=DEV)   # (distinct fills: an unwritten result differs)
+
+    def run(fn, typed, fill):   # mphip_warp_volume(_typed)
+        out, coords, idx, rng = new(v.shape, fill), new((b, d, h, w, 3), fill), new((b, d, h, w, 3), int(fill), torch.int32), ops.new_range(v.device)
+        ws = new((ws_bytes // 4,), 0.0)
+        head = (P(v), f32) if typed else (P(v),)
+        assert fn(*head, P(field), *lin, P(out), P(coords), P(idx), P(rng), b, c, d, h, w, d, h, w, P(ws), ws_bytes, S()) == 0, lib.mphip_last_error()
+        n = int(rng[3:4].view(torch.int32))
+        return out, coords, idx, rng[:4 + n].clone()
+
+    plain, typed = run(lib.mphip_warp_volume, False, 1.0), run(lib.mphip_warp_volume_typed, True, 2.0)
+    for x, y in zip(plain, typed):
+        assert torch.equal(x, y)
+    coords = plain[1]
+    if w % 4 != 0:
+        return   # (the entry points below need W % 4 == 0 or do not depend on W's path)
+    # the corner image and K2 on given coordinates with it
+    imgs = [new((img_bytes // 4,), 1.0), new((img_bytes // 4,), 2.0)]
+    assert lib.mphip_warp_corner_image(P(v), P(imgs[0]), img_bytes, b, c, d, h, w, S()) == 0, lib.mphip_last_error()
+    assert lib.mphip_warp_corner_image_typed(P(v), f32, P(imgs[1]), img_bytes, b, c, d, h, w, S()) == 0, lib.mphip_last_error()
+    assert torch.equal(imgs[0], imgs[1])
+    outs, ws = [new(v.shape, 1.0), new(v.shape, 2.0)], new((ws_bytes // 4,), 0.0)
+    assert lib.mphip_warp_volume_coords_img(P(v), P(coords), P(outs[0]), None, b, c, d, h, w, P(ws), ws_bytes, P(imgs[0]), S()) == 0, lib.mphip_last_error()
+    assert lib.mphip_warp_volume_coords_img_typed(P(v), f32, P(coords), P(outs[1]), None, b, c, d, h, w, P(ws), ws_bytes, P(imgs[0]), S()) == 0, lib.mphip_last_error()
+    assert torch.equal(outs[0], outs[1]) and torch.equal(outs[0], plain[0])
+    # K3: on given coordinates, and with its own coordinate pass (own and shared source volume)
+    for shared in (0, 1):
+        src = v[:1].contiguous() if shared else v
+        sums = [new((b, c, h, w), float(k)) for k in range(1, 5)]
+        assert lib.mphip_warp_volume_dsum_coords(P(src), P(coords), P(sums[0]), b, c, d, h, w, shared, S()) == 0, lib.mphip_last_error()
+        assert lib.mphip_warp_volume_dsum_coords_typed(P(src), P(coords), P(sums[1]), f32, b, c, d, h, w, shared, S()) == 0, lib.mphip_last_error()
+        fn = lib.mphip_warp_volume_dsum_shared if shared else lib.mphip_warp_volume_dsum
+        assert fn(P(src), P(field), *lin, P(sums[2]), b, c, d, h, w, d, h, w, P(ws), ws_bytes, S()) == 0, lib.mphip_last_error()
+        assert lib.mphip_warp_volume_dsum_typed(P(src), shared, P(field), *lin, P(sums[3]), f32, b, c, d, h, w, d, h, w, P(ws), ws_bytes, S()) == 0, lib.mphip_last_error()
+        assert torch.equal(sums[0], sums[1]) and torch.equal(sums[2], sums[3]) and torch.equal(sums[0], sums[2])

@@ -3,6 +3,7 @@
 import ctypes
 import json
 import os
+import re
 
 import pytest
 import torch
@@ -99,7 +100,7 @@ def test_training_a_half_module_is_refused_before_any_launch():
 
 def test_fp32_warp_kernels_keep_their_resources():
     """The K2/K3 kernels the fp32 path launches: registers, spills, scratch and LDS as recorded before the typed instantiations were
-    added (the typed kernels are separate instantiations; tools/register_table.py)."""
+    added (every kernel is one template over the dtype; its fp32 instantiation, `name<0>`, is pinned here; tools/register_table.py)."""
     import sys
 
     sys.path.insert(0, os.path.join(ROOT, "tools"))
@@ -112,7 +113,8 @@ def test_fp32_warp_kernels_keep_their_resources():
         assert name in kernels, name
         got = {k: kernels[name].get(k) for k in meta}
         assert got == meta, (name, got, meta)
-    typed = [n for n in kernels if "typed" in n]
-    assert len(typed) >= 10, sorted(kernels)
+    # the fp16 / bf16 instantiations of the six K2/K3 kernels: the dtype is the (last) template argument
+    typed = [n for n in kernels if re.fullmatch(r"warp_(gather(_columns|_direct|_scalar|_dsum)?|corner_image)_kernel<(\d+, )?[12]>", n)]
+    assert len(typed) == 12, sorted(kernels)
     for n in typed:
         assert kernels[n].get("private_segment_fixed_size", 0) == 0 and kernels[n].get("vgpr_spill_count", 0) == 0, (n, kernels[n])

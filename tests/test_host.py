@@ -480,7 +480,6 @@ COVERED_THROUGH_WRAPPER = {
     "mphip_conv3d_gn_table_fwd": _PLAN,
     "mphip_flowfield_compact_weight": _PLAN,
     "mphip_flowfield_conv_gn_compact": _PLAN,
-    "mphip_warp_volume_dsum_coords": _PLAN,
     "mphip_grad_prep": (_OPS, "grad_prep", "tests/test_gpu_backward.py::test_conv3d_bwd_weight"),
     "mphip_groupnorm_apply_split": (_OPS, "groupnorm_apply", "tests/test_gpu_parity.py::test_split_aware_groupnorm_chain"),
     "mphip_groupnorm_small_fused": (_OPS, "groupnorm_small", "tests/test_gpu_parity.py::test_split_aware_groupnorm_chain"),
@@ -493,7 +492,6 @@ COVERED_THROUGH_WRAPPER = {
     "mphip_warp_field_compose_bwd": (_OPS, "warp_field_compose_bwd", "tests/test_gpu_backward.py::test_warp_field_compose_backward"),
     "mphip_warp_sample_box": _PLAN,
     "mphip_warp_volume_bwd": (_OPS, "warp_volume_bwd", "tests/test_gpu_backward.py::test_warp_volume_backward_dense_equals_tiled_at_full_size"),
-    "mphip_warp_volume_dsum_shared": (_OPS, "warp_volume_dsum", "tests/test_gpu_parity.py::test_full_size_properties"),
 }
 
 

@@ -6,7 +6,10 @@ import csv, glob, json, os, re, sys
 from collections import defaultdict
 
 root = sys.argv[1]
-KEEP = ("warp_gather_kernel", "warp_gather_columns_kernel", "warp_gather_direct_kernel", "warp_gather_dsum_kernel", "warp_coords_kernel", "warp_corner_image_kernel")
+# bare kernel name (the key of the summary, what bench.py reads) -> how rocprofv3 spells the fp32 instantiation that is recorded under it
+KEEP = {"warp_gather_kernel": "warp_gather_kernel<0>(", "warp_gather_columns_kernel": "warp_gather_columns_kernel<0>(",
+        "warp_gather_direct_kernel": "warp_gather_direct_kernel<0>(", "warp_gather_dsum_kernel": "warp_gather_dsum_kernel<16, 0>(",
+        "warp_coords_kernel": "warp_coords_kernel<", "warp_corner_image_kernel": "warp_corner_image_kernel<0>("}
 out = {}
 for d in sorted(glob.glob(os.path.join(root, "pmc_*_B*_*"))):
     if not os.path.isdir(d):
@@ -20,8 +23,8 @@ for d in sorted(glob.glob(os.path.join(root, "pmc_*_B*_*"))):
         with open(f, newline="") as fh:
             for row in csv.DictReader(fh):
                 name = row["Kernel_Name"]
-                for k in KEEP:
-                    if k + "(" in name or k + "<" in name:
+                for k, spelled in KEEP.items():
+                    if spelled in name:
                         if row["Counter_Name"] == ctr:
                             acc[k].append((int(row["Dispatch_Id"]), float(row["Counter_Value"]), int(row["End_Timestamp"]) - int(row["Start_Timestamp"])))
     for k, vals in acc.items():

@@ -1,5 +1,5 @@
 """Wrap the summary of tools/pmc_warps.sh (tools/pmc_summary.py output) into profiles/r02_pmc_warps.json: the per-kernel counters under
-"kernels" (what bench.py's roofline_hbm reads) plus the method and a one-line reading per (kernel family, field kind) at B=8.
+"kernels" (what bench.py's roofline_hbm reads; a kernel's fp32 instantiation, `name<0>`, is recorded under its bare name) plus the method and a one-line reading per (kernel family, field kind) at B=8.
 usage: python tools/pmc_warps_profile.py <summary.json> <out.json>"""
 import json
 import sys

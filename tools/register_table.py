@@ -4,6 +4,9 @@ usage: python tools/register_table.py [out.json]     (default: print)
        python tools/register_table.py --skeleton [csrc dir]    the F(2,3) conv kernels only: metadata + a hash of each kernel's "skeleton", the
            ordered list of its MFMAs, LDS-DMA pieces, buffer loads, global stores, barriers and s_waitcnt vmcnt(N) — what the hand-counted
            waits of those kernels rest on.  [csrc dir]: another checkout's csrc (profiles/wino_shared_isa.json compares two commits this way).
+       python tools/register_table.py --isa <csrc dir> file.hip [file.hip ...]    every kernel of the given files: metadata, the number of
+           instructions and a SHA-256 of the whole instruction stream (local labels and mangled symbol names normalised; comments, blank lines
+           and .text / .section directives dropped).  profiles/warp_unify_isa.json compares two commits' warp kernels this way.
 The CPU test tests/test_host.py::test_hot_kernels_have_no_scratch uses collect() on the hot translation units."""
 import concurrent.futures, hashlib, json, os, re, subprocess, sys
 
@@ -48,7 +51,19 @@ def skeleton(asm, name):
     return {"skeleton_sha256": sha(ops), "skeleton_sorted_sha256": sha(sorted(ops)), "skeleton_ops": len(ops), "mfma": sum(o.startswith("v_mfma") for o in ops)}
 
 
-def one(path, with_skeleton=False):
+def isa(asm, name):
+    """Kernel `name`'s (mangled) instruction stream, normalised so that a renamed or re-ordered kernel with the same code hashes the same."""
+    body = asm[asm.index("\n" + name + ":") + len(name) + 2:]
+    lines = []
+    for ln in body[:body.index(".Lfunc_end")].splitlines():
+        ln = re.sub(r"\b_Z\w+", "SYM", re.sub(r"\.L(BB|tmp|JTI)\d+_", r".L\1_", ln.split(";")[0])).strip()
+        if ln and not ln.startswith((".text", ".section")):
+            lines.append(ln)
+    return {"isa_instructions": sum(not (ln.endswith(":") or ln.startswith(".")) for ln in lines),
+            "isa_sha256": hashlib.sha256("\n".join(lines).encode()).hexdigest()}
+
+
+def one(path, with_skeleton=False, with_isa=False):
     asm = subprocess.run([HIPCC] + FLAGS + EXTRA.get(os.path.basename(path), []) + [path], capture_output=True, text=True)
     if asm.returncode != 0:
         raise RuntimeError(f"{path}: {asm.stderr[-2000:]}")
@@ -85,16 +100,18 @@ def one(path, with_skeleton=False):
                 k[key[1:]] = int(mm.group(1))
         if with_skeleton:
             k.update(skeleton(asm.stdout, k["name"]))
+        if with_isa:
+            k.update(isa(asm.stdout, k["name"]))
         kernels.append(k)
     for k, d in zip(kernels, demangle([k["name"] for k in kernels])):
         k["demangled"] = d
     return {"sha256": hashlib.sha256(open(path, "rb").read()).hexdigest(), "kernels": kernels, "asm": asm.stdout if os.environ.get("MPHIP_KEEP_ASM") else None}
 
 
-def collect(files=None, csrc=CSRC, with_skeleton=False):
+def collect(files=None, csrc=CSRC, with_skeleton=False, with_isa=False):
     files = files or sorted(f for f in os.listdir(csrc) if f.endswith(".hip"))
     with concurrent.futures.ThreadPoolExecutor(max_workers=min(8, len(files))) as ex:
-        res = list(ex.map(lambda f: one(os.path.join(csrc, f), with_skeleton), files))
+        res = list(ex.map(lambda f: one(os.path.join(csrc, f), with_skeleton, with_isa), files))
     return dict(zip(files, res))
 
 
@@ -105,8 +122,11 @@ def head_commit():
         return None
 
 
-if __name__ == "__main__" and sys.argv[1:2] == ["--skeleton"]:
-    files = collect(WINO, sys.argv[2] if len(sys.argv) > 2 else CSRC, with_skeleton=True)
+if __name__ == "__main__" and sys.argv[1:2] in (["--skeleton"], ["--isa"]):
+    if sys.argv[1] == "--isa":
+        files = collect(sys.argv[3:], sys.argv[2], with_isa=True)
+    else:
+        files = collect(WINO, sys.argv[2] if len(sys.argv) > 2 else CSRC, with_skeleton=True)
     print(json.dumps({f: [{k: v for k, v in kern.items() if k != "name"} for kern in t["kernels"]] for f, t in files.items()}, indent=1))
 elif __name__ == "__main__":
     table = {"_what": "amdhsa metadata of every kernel (hipcc --offload-arch=gfx950 -O3 -S), per translation unit; private_segment_fixed_size = "
