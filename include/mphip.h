@@ -39,7 +39,7 @@ extern "C" {
 
 /* ABI version of this header.  Bumped whenever an exported signature or a packed layout changes; mphip_version() returns the
  * value the LIBRARY was built with — compare the two after dlopen (the ctypes binding does, and refuses a mismatch). */
-#define MPHIP_ABI_VERSION 16
+#define MPHIP_ABI_VERSION 17
 int mphip_version(void);
 /* hipGraph hygiene (ABI 13).  On ROCm 7.x a MEMSET node of a captured hipGraph is not reliably ordered with its neighbouring kernel nodes
  * (observed twice: stale f16x3 pack headers, r03; a training step's loss that kept its previous value, r04-r05 — ATen's multi-block
@@ -523,6 +523,25 @@ int mphip_hot_slice_forward_typed(mphip_hot_slice_plan *plan, const void *vs, in
 size_t mphip_g3d_workspace_bytes_typed(mphip_hot_slice_plan *plan, int B, int x_dtype, int y_dtype);
 int mphip_g3d_forward_typed(mphip_hot_slice_plan *plan, const void *x, int x_dtype, const float *x_range, void *y, int y_dtype, int B,
                             void *workspace, size_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------ G2d's exit (ABI 17)
+ * model.py:747-752, 762: final_conv = GroupNorm(G=32, C=64) -> ReLU -> Conv2d(64, Co=3, 3, padding=1) -> Sigmoid on x [N,64,H,W] (NCHW).
+ * C = 64, G = 32, Co = 3 is the only shape covered (anything else: MPHIP_EINVAL); any H, W >= 1.
+ *   mphip_g2d_final_fwd: two launches, two reads of x, one write of y [N,3,H,W].  x in x_dtype (widened on load, no fp32 copy), y in
+ *          y_dtype (the fp32 result rounded once); gamma, beta [64], w [3,64,3,3] (the module's own tensor, nothing is packed) and
+ *          bias [3] are fp32.  The conv pads the ACTIVATED tensor with zeros.  stats_out (may be NULL): [N*G][2] (mean, rstd), what the
+ *          backward needs.  workspace: mphip_g2d_final_workspace_bytes(.., backward = 0).
+ *   mphip_g2d_final_bwd: fp32 only.  From x, the forward's y and stats, and dy: dx [N,64,H,W], dgamma, dbeta [64], dw [3,64,3,3],
+ *          db [3] (dw / db may be NULL).  The activated tensor and its gradient are two [N,64,H,W] fp32 tensors inside the workspace
+ *          (mphip_g2d_final_workspace_bytes(.., backward = 1), 16-byte aligned), handed to mphip_groupnorm_bwd (act = ReLU).  dw and db
+ *          are per-workgroup partials folded in a fixed order: bitwise reproducible run to run.                                   */
+size_t mphip_g2d_final_workspace_bytes(int N, int C, int H, int W, int G, int backward);
+int mphip_g2d_final_fwd(const void *x, int x_dtype, const float *gamma, const float *beta, const float *w, const float *bias, void *y,
+                        int y_dtype, float *stats_out, int N, int C, int Co, int H, int W, int G, float eps, void *workspace,
+                        size_t workspace_bytes, void *stream);
+int mphip_g2d_final_bwd(const float *x, const float *y, const float *dy, const float *stats, const float *gamma, const float *beta,
+                        const float *w, float *dx, float *dgamma, float *dbeta, float *dw, float *db, int N, int C, int Co, int H, int W,
+                        int G, void *workspace, size_t workspace_bytes, void *stream);
 
 /* The reference's reduced-precision policy for the convs (train.py:145,188: the generator step runs under torch.cuda.amp.autocast(), its
  * conv3d calls take f16 operands with fp32 accumulation).  mphip_conv3d_set_half_products(1) makes the CALLING THREAD's subsequent precision-1

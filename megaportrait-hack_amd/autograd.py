@@ -163,6 +163,29 @@ def adaptive_groupnorm(x, agn, residual=None, relu=False):
     return GroupNormFn.apply(x, gn.weight, gn.bias, agn.weight, agn.bias, residual, gn.num_groups, gn.eps, int(relu))
 
 
+class G2dFinal(torch.autograd.Function):
+    """y = sigmoid(conv2d(relu(group_norm(x, 32, gamma, beta, eps)), w, bias, padding=1)): G2d's final_conv (model.py:747-752).
+    Saves x, the GroupNorm statistics and y — not the activated [N,64,H,W] tensor, which the backward recomputes."""
+
+    @staticmethod
+    @_fwd
+    def forward(ctx, x, gamma, beta, w, bias, eps):
+        x = x.float().contiguous()   # (the backward is fp32 only; NCHW)
+        y, stats = ops.g2d_final(x, gamma, beta, w, bias, eps, return_stats=True)
+        ctx.save_for_backward(x, y, stats, gamma, beta, w)
+        return y
+
+    @staticmethod
+    @once_differentiable  # no double backward (the reference's losses need none): asking for one raises instead of returning zeros
+    @_bwd
+    def backward(ctx, dy):
+        x, y, stats, gamma, beta, w = ctx.saved_tensors
+        need = ctx.needs_input_grad
+        dx, dgamma, dbeta, dw, db = ops.g2d_final_bwd(x, y, dy.contiguous(), stats, gamma, beta, w, want_params=need[3] or need[4])
+        return (dx if need[0] else None, dgamma if need[1] else None, dbeta if need[2] else None, dw if need[3] else None,
+                db if need[4] else None, None)
+
+
 def needs_grad(module, *tensors) -> bool:
     return torch.is_grad_enabled() and (any(isinstance(t, torch.Tensor) and t.requires_grad for t in tensors)
                                         or any(p.requires_grad for p in module.parameters()))

@@ -331,6 +331,13 @@ class G2d(M.G2dHead):
         self.upsample3 = nn.Sequential(up(), ResBlock2D(128, 64))
         self.final_conv = nn.Sequential(nn.GroupNorm(32, 64), nn.ReLU(inplace=True), nn.Conv2d(64, 3, 3, padding=1), nn.Sigmoid())
 
+    def native_final_conv(self, enable: bool = True) -> "G2d":
+        """Opt-in: run `final_conv` as the two fused HIP launches of model.G2dFinalConv (built over the same four modules: same
+        Parameter objects, same state-dict keys) instead of four PyTorch-ROCm modules; `enable=False` puts the original nn.Sequential
+        object back.  The kernels read NCHW: under channels_last the [B,64,H,W] map is copied once."""
+        M.native_final_conv(self, enable)
+        return self
+
     def body(self, x):
         """[B,512,h,w] (the head's output) -> image [B,3,8h,8w] in (0,1) (model.py:758-762)."""
         x = self.res_blocks(x)

@@ -51,6 +51,13 @@ class Gbase(M._HotSliceRunner, nn.Module):
                     t.data = t.data.contiguous(memory_format=fmt)
         return self
 
+    def native_final_conv(self, enable: bool = True) -> "Gbase":
+        """Opt-in (off by default): `G2d.final_conv` — GroupNorm-ReLU-conv-sigmoid on the [B,64,512,512] map — as the fused HIP
+        kernels of model.G2dFinalConv; `enable=False` restores the original nn.Sequential.  Same parameters and state-dict keys.
+        With channels_last_2d() the map reaches the kernels in NHWC and is copied to NCHW first."""
+        M.native_final_conv(self.G2d, enable)
+        return self
+
     def _nhwc(self, x):
         return x.contiguous(memory_format=torch.channels_last) if getattr(self, "_cl2d", False) and x.dim() == 4 else x
 

@@ -654,6 +654,75 @@ class G2dHead(_ModelDtype, nn.Module):
         return y.reshape(b, 512, h, w)
 
 
+class G2dFinalConv(_ModelDtype, nn.Sequential):
+    """G2d's exit, model.py:747-752 + 762: `final_conv` = GroupNorm(32,64) -> ReLU -> Conv2d(64,3,3,padding=1) -> Sigmoid on the
+    [B,64,H,W] map (the largest activation of the generator), as two HIP launches that read the map twice and write the image
+    (csrc/g2d_final.hip) instead of five to six passes of stock kernels.  The children are the reference's four modules at indices
+    0-3 — parameter containers, their own forward is never called — so the state-dict keys are `0.weight, 0.bias, 2.weight, 2.bias`
+    and every checkpoint loads unchanged.  Opt-in: encoders2d.G2d.native_final_conv() / gbase.Gbase.native_final_conv() /
+    integration.install(g2d_final=True) swap it in; nothing uses it otherwise.
+
+    A .half() / .bfloat16() instance reads and writes the half dtype directly (no fp32 copy of the map); its output is bitwise its fp32
+    twin's on the widened input, rounded once.  An fp32 instance fed a half map returns fp32.  The kernels read NCHW: a channels_last
+    map is copied to NCHW first."""
+
+    def __init__(self):
+        super().__init__(nn.GroupNorm(32, 64), nn.ReLU(inplace=True), nn.Conv2d(64, 3, 3, padding=1), nn.Sigmoid())
+
+    @staticmethod
+    def matches(seq) -> bool:
+        """Is `seq` the reference's final_conv (four modules of the expected kinds and shapes)?"""
+        if not isinstance(seq, nn.Sequential) or len(seq) != 4:
+            return False
+        gn, act, conv, sig = seq[0], seq[1], seq[2], seq[3]
+        return (isinstance(gn, nn.GroupNorm) and gn.num_groups == 32 and gn.num_channels == 64 and gn.affine
+                and isinstance(act, nn.ReLU) and isinstance(sig, nn.Sigmoid) and isinstance(conv, nn.Conv2d)
+                and tuple(conv.weight.shape) == (3, 64, 3, 3) and conv.bias is not None and conv.stride == (1, 1)
+                and conv.padding == (1, 1) and conv.dilation == (1, 1) and conv.groups == 1 and conv.padding_mode == "zeros")
+
+    @classmethod
+    def from_sequential(cls, seq: nn.Sequential) -> "G2dFinalConv":
+        """A G2dFinalConv over `seq`'s own four modules: the SAME Parameter objects (an optimizer built earlier stays valid), the same
+        eps, device, dtype and train/eval mode."""
+        if not cls.matches(seq):
+            raise TypeError("G2dFinalConv.from_sequential: expected nn.Sequential(GroupNorm(32, 64), ReLU, Conv2d(64, 3, 3, padding=1), "
+                            f"Sigmoid), got {seq}")
+        new = cls.__new__(cls)
+        nn.Sequential.__init__(new, seq[0], seq[1], seq[2], seq[3])
+        new.train(seq.training)
+        return new
+
+    def forward(self, x):
+        gn, conv = self[0], self[2]
+        dt = model_dtype(self)
+        if dt != torch.float32:
+            _refuse_half_training(self, dt, x)
+            twin = _twin(self)
+            gn, conv = twin[0], twin[2]
+            return ops.g2d_final(x, gn.weight, gn.bias, conv.weight, conv.bias, gn.eps, out_dtype=dt)
+        if ag.needs_grad(self, x):
+            return ag.G2dFinal.apply(x, gn.weight, gn.bias, conv.weight, conv.bias, gn.eps)
+        return ops.g2d_final(x, gn.weight, gn.bias, conv.weight, conv.bias, gn.eps, out_dtype=torch.float32)
+
+
+def native_final_conv(g2d: nn.Module, enable: bool = True) -> bool:
+    """Swaps `g2d.final_conv` (this package's G2d or the reference's, model.py:747-752) for a G2dFinalConv over the same modules, or
+    back to the very nn.Sequential object it replaced.  Returns whether anything changed.  Off by default everywhere."""
+    cur = getattr(g2d, "final_conv", None)
+    if enable:
+        if isinstance(cur, G2dFinalConv):
+            return False
+        new = G2dFinalConv.from_sequential(cur)
+        new.__dict__["_replaced"] = cur   # (not a registered child: the module tree and the state-dict keys stay as they were)
+        g2d.final_conv = new
+        return True
+    if not isinstance(cur, G2dFinalConv):
+        return False
+    old = cur.__dict__.pop("_replaced", None)
+    g2d.final_conv = old if old is not None else nn.Sequential(*cur.children())
+    return True
+
+
 class _HotSliceRunner(_ModelDtype):
     """model.py:1151-1171 over `self.warp_generator_s2c`, `self.warp_generator_c2d`, `self.G3d` — shared by
     GbaseHotSlice (the slice alone) and gbase.Gbase (the orchestrator)."""

@@ -1122,6 +1122,67 @@ def groupnorm_bwd(x, y, dy, stats, gamma, groups: int, relu, want_res: bool, bet
     return dx, dgamma, dbeta, dres
 
 
+# ------------------------------------------------------------------ G2d's exit (csrc/g2d_final.hip, model.py:747-752)
+_G2D_FINAL = (64, 32, 3)   # (C, G, Co): the only shape the kernels cover
+
+
+def _g2d_final_params(gamma, beta, w, bias):
+    return tuple(_req(t.detach(), n) for t, n in ((gamma, "gamma"), (beta, "beta"), (w, "w"), (bias, "bias")))
+
+
+def g2d_final(x: torch.Tensor, gamma, beta, w, bias, eps: float = 1e-5, out_dtype: Optional[torch.dtype] = None,
+              return_stats: bool = False):
+    """sigmoid(conv2d(relu(group_norm(x, 32, gamma, beta, eps)), w, bias, padding=1)) for x [N,64,H,W] -> [N,3,H,W] in two launches
+    (mphip_g2d_final_fwd).  x: fp32, fp16 or bf16, read as it is; the parameters are fp32; the result is rounded once to out_dtype
+    (default: x's dtype).  The kernels read NCHW: a channels_last x is first copied to NCHW-contiguous memory (one extra read and write
+    of x).  return_stats: also the [N*32, 2] (mean, rstd) the backward needs."""
+    x = _req_typed(x, "x")
+    gamma, beta, w, bias = _g2d_final_params(gamma, beta, w, bias)
+    c, g, co = _G2D_FINAL
+    if x.dim() != 4 or x.shape[1] != c or tuple(w.shape) != (co, c, 3, 3) or gamma.numel() != c or beta.numel() != c or bias.numel() != co:
+        raise RuntimeError(f"g2d_final: expected x [N,{c},H,W], gamma/beta [{c}], w [{co},{c},3,3], bias [{co}]; got x {tuple(x.shape)}, "
+                           f"w {tuple(w.shape)}")
+    out_dtype = x.dtype if out_dtype is None else out_dtype
+    n, _, h, wd = x.shape
+    dev = x.device
+    y = torch.empty((n, co, h, wd), dtype=out_dtype, device=dev)
+    stats = torch.empty((n * g, 2), dtype=torch.float32, device=dev) if return_stats else None
+    if x.numel():
+        lib = _lib.load()
+        ws_bytes = lib.mphip_g2d_final_workspace_bytes(n, c, h, wd, g, 0)
+        ws = torch.empty(ws_bytes // 8, dtype=torch.float64, device=dev)
+        _lib.check(lib.mphip_g2d_final_fwd(_ptr(x), dtype_code(x.dtype), _ptr(gamma), _ptr(beta), _ptr(w), _ptr(bias), _ptr(y),
+                                           dtype_code(out_dtype), _ptr(stats), n, c, co, h, wd, g, float(eps), _ptr(ws), ws_bytes, _stream()),
+                   "mphip_g2d_final_fwd")
+    return (y, stats) if return_stats else y
+
+
+def g2d_final_bwd(x, y, dy, stats, gamma, beta, w, want_params: bool = True):
+    """Backward of g2d_final (fp32 only) from the saved x, y and stats -> (dx, dgamma, dbeta, dw, db); dw and db are None (and their
+    reduction is skipped) when want_params is False.  The activated tensor and its gradient live in the call's workspace: two
+    [N,64,H,W] fp32 tensors."""
+    x, y, dy, stats = _req(x, "x"), _req(y, "y"), _req(dy, "dy"), _req(stats, "stats")
+    gamma, beta, w = (_req(t.detach(), n) for t, n in ((gamma, "gamma"), (beta, "beta"), (w, "w")))
+    c, g, co = _G2D_FINAL
+    n, _, h, wd = x.shape
+    if x.dim() != 4 or x.shape[1] != c or tuple(y.shape) != (n, co, h, wd) or y.shape != dy.shape or tuple(w.shape) != (co, c, 3, 3):
+        raise RuntimeError(f"g2d_final_bwd: expected x [N,{c},H,W], y and dy [N,{co},H,W]; got {tuple(x.shape)}, {tuple(y.shape)}, "
+                           f"{tuple(dy.shape)}")
+    dev = x.device
+    lib = _lib.load()
+    ws_bytes = lib.mphip_g2d_final_workspace_bytes(n, c, h, wd, g, 1)
+    ws = torch.empty(ws_bytes // 4, dtype=torch.float32, device=dev)
+    dx = torch.empty_like(x)
+    dgamma = torch.empty(c, dtype=torch.float32, device=dev)
+    dbeta = torch.empty(c, dtype=torch.float32, device=dev)
+    dw = torch.empty((co, c, 3, 3), dtype=torch.float32, device=dev) if want_params else None
+    db = torch.empty(co, dtype=torch.float32, device=dev) if want_params else None
+    _lib.check(lib.mphip_g2d_final_bwd(_ptr(x), _ptr(y), _ptr(dy), _ptr(stats), _ptr(gamma), _ptr(beta), _ptr(w), _ptr(dx), _ptr(dgamma),
+                                       _ptr(dbeta), _ptr(dw), _ptr(db), n, c, co, h, wd, g, _ptr(ws), ws_bytes, _stream()),
+               "mphip_g2d_final_bwd")
+    return dx, dgamma, dbeta, dw, db
+
+
 def avgpool2_bwd(dout: torch.Tensor) -> torch.Tensor:
     dout = _req(dout, "dout")
     n, c, d, h, w = dout.shape
