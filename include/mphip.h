@@ -39,7 +39,7 @@ extern "C" {
 
 /* ABI version of this header.  Bumped whenever an exported signature or a packed layout changes; mphip_version() returns the
  * value the LIBRARY was built with — compare the two after dlopen (the ctypes binding does, and refuses a mismatch). */
-#define MPHIP_ABI_VERSION 17
+#define MPHIP_ABI_VERSION 18
 int mphip_version(void);
 /* hipGraph hygiene (ABI 13).  On ROCm 7.x a MEMSET node of a captured hipGraph is not reliably ordered with its neighbouring kernel nodes
  * (observed twice: stale f16x3 pack headers, r03; a training step's loss that kept its previous value, r04-r05 — ATen's multi-block
@@ -570,6 +570,19 @@ int mphip_conv3d_kernel_variant(int N, int Ci, int Co, int D, int H, int W, int 
  * lockstep, role-split, big-tile, two-frame schedule (all four answer 5 to mphip_conv3d_kernel_variant).  Returns 1, or 0 with out zeroed
  * when the shape takes no such launch.  Host only: no GPU is touched.                                                           */
 int mphip_debug_conv3d_plan(int N, int Ci, int Co, int D, int H, int W, int roi, int out[12]);
+
+/* (ABI 18) Tests only: the decision the library takes for an exact-fp32 (precision 0) forward or bwd-data launch of this shape, with the
+ * environment as it stands (MPHIP_CONV_GATHER forces the gather kernel).  out = { tiled: 0 = the gather kernel, 4 / 2 = the LDS-tiled
+ * 3x3x3 kernel on a (4,8,8) / (2,8,8) voxel tile; MT, NT: 32-channel rows and 32-voxel columns per wave; WCO: waves along Co; skip: taps
+ * that fall outside a thin volume are skipped; splits; input channels (gather) or 2-channel chunks (tiled) per split; grid x, y, z }.
+ * A tiled plan reports MT 3, NT tiled / 2, WCO 1, skip 0.  Returns 1, or 0 with out zeroed for a shape the library refuses.  Host only. */
+int mphip_debug_conv3d_f32_plan(int N, int Ci, int Co, int D, int H, int W, int k, int out[10]);
+
+/* (ABI 18) Tests only: the exact-fp32 backward-weight kernel mphip_conv3d_bwd_weight launches at precision 0 for this shape (the first
+ * three also serve precision 1 on tiny volumes), dy_aligned: dy is 16-byte aligned.  out = { kernel, splits }; kernel: 0 = one thread per
+ * dW element, 1 = the small-map MFMA kernel, 2 = one wave per (co, ci) pair, 3 = the LDS-tiled MFMA kernel, whose `splits` slabs a second
+ * launch reduces.  MPHIP_BWD_WEIGHT_WAVE in the environment turns 1 into 2.  Returns 1, or 0 with out zeroed for a bad shape.  Host only. */
+int mphip_debug_conv3d_bwd_weight_f32_kernel(int N, int Ci, int Co, int D, int H, int W, int k, int dy_aligned, int out[2]);
 
 /* Measurement only (tools/mfma_sol.py, bench.py `roofline.sustained_peak`): the f16x3 convs' MFMA stream and nothing else — three
  * v_mfma_f32_32x32x16_f16 per product on random hi/lo fragments, 3 x 2 accumulator tiles per wave, 8 waves per workgroup; mode 1 reads

@@ -765,6 +765,26 @@ static int bw_splits(long ntiles, int blocks_xy) {
     return s;
 }
 
+// The exact-fp32 backward-weight kernel of a shape (the tiny-volume kernels serve both precisions).  The one place that decides:
+// bwd_weight_impl launches what this returns, mphip_debug_conv3d_bwd_weight_f32_kernel reports it.
+enum BwdWeightKernel { BWK_PER_THREAD = 0, BWK_SMALL_MFMA = 1, BWK_WAVE = 2, BWK_TILED = 3 };
+struct BwdWeightChoice {
+    int kernel;  // BwdWeightKernel
+    int splits;  // slabs of the tiled kernel (slab_reduce_kernel folds them); 1 for the others
+};
+static BwdWeightChoice bwd_weight_f32_choice(int N, int Ci, int Co, int D, int H, int W, int k, bool dy_aligned) {
+    if (bwd_weight_direct(N, D, H, W)) {
+        // a handful of voxels whose count the MFMA kernel's 16-byte loads cannot take: one thread per dW element (maps of 4 k
+        // voxels, FlowField's 4x1x1 included, go to the MFMA kernel: 512x256x27 outputs 45 -> ~15 us)
+        if ((long)N * D * H * W <= 64 && (D * H * W) % 4 != 0) return {BWK_PER_THREAD, 1};
+        if ((D * H * W) % 4 == 0 && dy_aligned && !getenv("MPHIP_BWD_WEIGHT_WAVE")) return {BWK_SMALL_MFMA, 1};  // (env: the older kernel, for A/B)
+        return {BWK_WAVE, 1};
+    }
+    const long ntiles = (long)N * D * ((H + 7) / 8) * ((W + 7) / 8);
+    const int bxy = ((Ci + 31) / 32) * ((Co + 95) / 96) * (k == 3 ? 3 : 1);
+    return {BWK_TILED, bw_splits(ntiles, bxy)};
+}
+
 extern "C" int mphip_conv3d_bwd_weight_supported(int N, int Ci, int Co, int D, int H, int W, int k, int precision) {
     if (N <= 0 || Ci <= 0 || Co <= 0 || D <= 0 || H <= 0 || W <= 0 || (k != 1 && k != 3)) return 0;
     if (precision == 0) return 1;
@@ -777,9 +797,20 @@ extern "C" size_t mphip_conv3d_bwd_weight_workspace_bytes(int N, int Ci, int Co,
     if (!mphip_conv3d_bwd_weight_supported(N, Ci, Co, D, H, W, k, precision)) return 0;
     if (bwd_weight_direct(N, D, H, W)) return 16;  // unused
     if (precision == 1) return BW_RANGE_BYTES + bwd_weight_f16x3_ws_bytes(N, Ci, Co, D, H, W, k);  // head: a library-computed range of x
-    const long ntiles = (long)N * D * ((H + 7) / 8) * ((W + 7) / 8);
-    const int bxy = ((Ci + 31) / 32) * ((Co + 95) / 96) * (k == 3 ? 3 : 1);
-    return (size_t)bw_splits(ntiles, bxy) * Co * Ci * k * k * k * sizeof(float);
+    return (size_t)bwd_weight_f32_choice(N, Ci, Co, D, H, W, k, true).splits * Co * Ci * k * k * k * sizeof(float);
+}
+
+// (tests / measurement only) which exact-fp32 backward-weight kernel mphip_conv3d_bwd_weight launches at precision 0 for this shape,
+// given whether dy is 16-byte aligned: out = {kernel, splits}; kernel 0 = one thread per dW element, 1 = small-map MFMA,
+// 2 = one wave per (co, ci) pair, 3 = LDS-tiled MFMA + slab reduce.  Returns 1, or 0 with out zeroed for a bad shape.  Host only.
+extern "C" int mphip_debug_conv3d_bwd_weight_f32_kernel(int N, int Ci, int Co, int D, int H, int W, int k, int dy_aligned, int out[2]) {
+    if (!out) return 0;
+    out[0] = out[1] = 0;
+    if (!mphip_conv3d_bwd_weight_supported(N, Ci, Co, D, H, W, k, 0)) return 0;
+    const BwdWeightChoice c = bwd_weight_f32_choice(N, Ci, Co, D, H, W, k, dy_aligned != 0);
+    out[0] = c.kernel;
+    out[1] = c.splits;
+    return 1;
 }
 
 static int bwd_weight_impl(const float *x, const float *x_range, const float *dy, const float *dy_scale, float *dw, int N, int Ci, int Co, int D,
@@ -815,16 +846,14 @@ static int bwd_weight_impl(const float *x, const float *x_range, const float *dy
         return MPHIP_EWORKSPACE;
     }
     hipStream_t s = (hipStream_t)stream;
-    if (bwd_weight_direct(N, D, H, W)) {
+    const BwdWeightChoice choice = bwd_weight_f32_choice(N, Ci, Co, D, H, W, k, ((uintptr_t)dy & 15) == 0);
+    if (choice.kernel != BWK_TILED) {   // the tiny-volume kernels, whatever the precision
         const size_t nw = (size_t)Co * Ci * k * k * k;
-        // a handful of voxels whose count the MFMA kernel's 16-byte loads cannot take: one thread per dW element (maps of 4 k
-        // voxels, FlowField's 4x1x1 included, go to the MFMA kernel: 512x256x27 outputs 45 -> ~15 us)
-        const bool per_thread = (long)N * D * H * W <= 64 && (D * H * W) % 4 != 0;
-        if (per_thread && k == 3)
+        if (choice.kernel == BWK_PER_THREAD && k == 3)
             hipLaunchKernelGGL(conv_bwd_weight_direct_kernel<3>, dim3(cdiv(nw, 256)), dim3(256), 0, s, x, dy, dw, N, Ci, Co, D, H, W);
-        else if (per_thread)
+        else if (choice.kernel == BWK_PER_THREAD)
             hipLaunchKernelGGL(conv_bwd_weight_direct_kernel<1>, dim3(cdiv(nw, 256)), dim3(256), 0, s, x, dy, dw, N, Ci, Co, D, H, W);
-        else if ((D * H * W) % 4 == 0 && ((uintptr_t)dy & 15) == 0 && !getenv("MPHIP_BWD_WEIGHT_WAVE")) {  // (env: the older kernel, for A/B)
+        else if (choice.kernel == BWK_SMALL_MFMA) {
             const dim3 grid((unsigned)(((Co + 31) / 32) * ((Ci + 31) / 32)), k == 3 ? 27 : 1);
             if (k == 3)
                 hipLaunchKernelGGL((conv_bwd_weight_small_mfma_kernel<3, 4>), grid, dim3(256), 0, s, x, dy, dw, N, Ci, Co, D, H, W);
@@ -850,7 +879,7 @@ static int bwd_weight_impl(const float *x, const float *x_range, const float *dy
     }
     const long ntiles = (long)N * D * ((H + 7) / 8) * ((W + 7) / 8);
     const int ci_tiles = (Ci + 31) / 32, co_tiles = (Co + 95) / 96;
-    const int splits = bw_splits(ntiles, ci_tiles * co_tiles * (k == 3 ? 3 : 1));
+    const int splits = choice.splits;
     const int tps = (int)((ntiles + splits - 1) / splits);
     dim3 grid(ci_tiles * co_tiles, k == 3 ? 3 : 1, splits);
     if (k == 3)

@@ -884,6 +884,21 @@ extern "C" int mphip_debug_conv3d_plan(int N, int Ci, int Co, int D, int H, int 
     return 1;
 }
 
+// the decision plan_conv takes for an exact-fp32 (precision 0) launch of this shape, under the environment as it stands (MPHIP_CONV_GATHER
+// is honoured: this IS plan_conv): out = {tiled (0 = gather kernel, 4 / 2 = conv3d_k3_tiled_kernel<4|2,8,8,3,2>), MT, NT, WCO, skip, splits,
+// channels (gather) or chunks (tiled) per split, grid x, y, z}; a tiled plan reports its kernel's template: MT 3, NT tiled / 2, WCO 1, no
+// skip.  Returns 1, or 0 with out zeroed for a shape the library refuses.  Tests / measurement only; host only.
+extern "C" int mphip_debug_conv3d_f32_plan(int N, int Ci, int Co, int D, int H, int W, int k, int out[10]) {
+    if (!out) return 0;
+    for (int i = 0; i < 10; ++i) out[i] = 0;
+    if (!conv_supported(f16x3_switches(), N, Ci, Co, D, H, W, k, 0)) return 0;
+    const ConvPlan p = plan_conv(N, Ci, Co, D, H, W, k);
+    const int v[10] = {p.tiled, p.tiled ? 3 : p.MT, p.tiled ? p.tiled / 2 : p.NT, p.tiled ? 1 : p.WCO, (!p.tiled && p.skip) ? 1 : 0,
+                       p.splits, p.ci_per_split, (int)p.grid.x, (int)p.grid.y, (int)p.grid.z};
+    for (int i = 0; i < 10; ++i) out[i] = v[i];
+    return 1;
+}
+
 extern "C" int mphip_conv3d_splits(int N, int Ci, int Co, int D, int H, int W, int k, int precision) {
     const F16x3Switches sw = f16x3_switches();
     if (!conv_supported(sw, N, Ci, Co, D, H, W, k, precision)) return 0;

@@ -12,7 +12,7 @@ def test_library_exports_the_entries():
     lib = _lib.load()
     for name in ("mphip_g2d_final_workspace_bytes", "mphip_g2d_final_fwd", "mphip_g2d_final_bwd"):
         assert name in _lib.SIGNATURES and getattr(lib, name) is not None
-    assert lib.mphip_version() == 17 == _lib.EXPECTED_ABI_VERSION == _lib.header_abi_version()
+    assert lib.mphip_version() == _lib.EXPECTED_ABI_VERSION == _lib.header_abi_version() >= 17     # the entries exist since ABI 17
 
 
 def test_module_constructs_on_the_cpu():

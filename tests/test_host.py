@@ -467,6 +467,7 @@ NOT_OPERATIONS = [
     "mphip_hot_slice_plan_create", "mphip_hot_slice_plan_set_tables", "mphip_hot_slice_plan_set_precision", "mphip_hot_slice_plan_profile",
     "mphip_hot_slice_plan_profile_read", "mphip_hot_slice_plan_refresh",
     "mphip_debug_conv3d_plan", "mphip_debug_mfma_sol", "mphip_debug_dma_stream",
+    "mphip_debug_conv3d_f32_plan", "mphip_debug_conv3d_bwd_weight_f32_kernel",
 ]
 # operation entries that no test file names: entry -> (source file that calls it, the wrapper there, a test that runs the wrapper).
 # "csrc/plan.hip" entries are launched by the C plan only: the wrapper is the plan's forward, the test compares it bitwise with the Python schedule.
