@@ -39,7 +39,7 @@ extern "C" {
 
 /* ABI version of this header.  Bumped whenever an exported signature or a packed layout changes; mphip_version() returns the
  * value the LIBRARY was built with — compare the two after dlopen (the ctypes binding does, and refuses a mismatch). */
-#define MPHIP_ABI_VERSION 18
+#define MPHIP_ABI_VERSION 19
 int mphip_version(void);
 /* hipGraph hygiene (ABI 13).  On ROCm 7.x a MEMSET node of a captured hipGraph is not reliably ordered with its neighbouring kernel nodes
  * (observed twice: stale f16x3 pack headers, r03; a training step's loss that kept its previous value, r04-r05 — ATen's multi-block
@@ -542,6 +542,32 @@ int mphip_g2d_final_fwd(const void *x, int x_dtype, const float *gamma, const fl
 int mphip_g2d_final_bwd(const float *x, const float *y, const float *dy, const float *stats, const float *gamma, const float *beta,
                         const float *w, float *dx, float *dgamma, float *dbeta, float *dw, float *db, int N, int C, int Co, int H, int W,
                         int G, void *workspace, size_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------ Conv2d 3x3 on the matrix cores (ABI 19)
+ * nn.Conv2d(Ci, Co, 3, stride=1, padding=1) on NCHW fp32 with a fused epilogue, for G2d's ResBlock2D body at inference (BatchNorm
+ * folded into w and bias by the caller):
+ *     y = act( conv(x, w) + bias[co] (+ residual[n,co,h,w]) ),   act = ReLU (relu != 0) or identity
+ * The arithmetic is the precision-1 ("f16x3") arithmetic of the 3-D convs: each operand tensor scaled by its own power of two, split
+ * into two f16 halves, three f16 products per multiply accumulated in fp32 (~2^-21 relative per term); bias, residual and ReLU in fp32.
+ * Out-of-range and non-finite inputs are passed through, not clamped, and counted by mphip_f16x3_saturation_count.  Bitwise
+ * reproducible: no floating-point atomics.
+ * Shapes: Ci % 16 == 0, Co % 32 == 0, any N, H, W >= 1 (edges are masked), N*Ci*H*W and N*Co*H*W below 2^31 elements; everything else
+ * is refused (mphip_conv2d_supported returns 0, the launch MPHIP_EINVAL).
+ *   mphip_pack_conv2d_weight: w_oihw [Co,Ci,3,3] fp32 -> w_packed (mphip_conv2d_packed_weight_bytes, 16-byte aligned): a 16-byte header
+ *          {1/scale, scale, max|w| bits, -} and the hi/lo f16 LDS image of every (64-channel co tile, 16-channel chunk) slab
+ *          [part][tap][kg][co][8].  One reduction and one pack launch; once per weight version.
+ *   mphip_conv2d_fwd: x [N,Ci,H,W], bias [Co], residual [N,Co,H,W] or NULL, y [N,Co,H,W] (y must not alias x or residual).
+ *          x_range: a range descriptor of x (see "Range descriptors"), or NULL: the library computes one with one extra read of x in
+ *          `workspace` (mphip_conv2d_workspace_bytes; not needed when x_range is given).  out_range (optional, MPHIP_RANGE_FLOATS
+ *          floats): receives a descriptor of y in derive mode whose partial maxima fold to the EXACT max|y|, so the next conv takes
+ *          the same scale whether it is fed this descriptor or scans y itself.                                                      */
+int mphip_conv2d_supported(int N, int Ci, int Co, int H, int W);
+size_t mphip_conv2d_packed_weight_bytes(int Co, int Ci);
+int mphip_pack_conv2d_weight(const float *w_oihw, void *w_packed, int Co, int Ci, void *stream);
+size_t mphip_conv2d_workspace_bytes(int N, int Ci, int Co, int H, int W);
+int mphip_conv2d_fwd(const float *x, const float *x_range, const void *w_packed, const float *bias, const float *residual, float *y,
+                     float *out_range, int N, int Ci, int Co, int H, int W, int relu, void *workspace, size_t workspace_bytes,
+                     void *stream);
 
 /* The reference's reduced-precision policy for the convs (train.py:145,188: the generator step runs under torch.cuda.amp.autocast(), its
  * conv3d calls take f16 operands with fp32 accumulation).  mphip_conv3d_set_half_products(1) makes the CALLING THREAD's subsequent precision-1

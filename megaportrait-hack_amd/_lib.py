@@ -138,6 +138,12 @@ SIGNATURES = {
     "mphip_g2d_final_workspace_bytes": (_sz, [_i] * 6),
     "mphip_g2d_final_fwd": (_i, [_p, _i, _p, _p, _p, _p, _p, _i, _p] + [_i] * 6 + [ctypes.c_float, _p, _sz, _p]),
     "mphip_g2d_final_bwd": (_i, [_p] * 12 + [_i] * 6 + [_p, _sz, _p]),
+    # Conv2d 3x3 on the matrix cores (ABI 19)
+    "mphip_conv2d_supported": (_i, [_i] * 5),
+    "mphip_conv2d_packed_weight_bytes": (_sz, [_i, _i]),
+    "mphip_pack_conv2d_weight": (_i, [_p, _p, _i, _i, _p]),
+    "mphip_conv2d_workspace_bytes": (_sz, [_i] * 5),
+    "mphip_conv2d_fwd": (_i, [_p] * 7 + [_i] * 6 + [_p, _sz, _p]),
     "mphip_build_flags": (_i, []),
     "mphip_graph_memsets_to_kernels": (_i, [_p, ctypes.POINTER(ctypes.c_int)]),
     "mphip_graph_memset_nodes_left": (_i, [_p, ctypes.POINTER(ctypes.c_int)]),
@@ -152,7 +158,7 @@ _lib = None
 # The ABI version the SIGNATURES table above mirrors.  Checked against the library at load time, and against include/mphip.h by
 # tests/test_host.py — NOT read from the header at run time: a relocated / installed package ships libmphip.so without the repository's
 # include/ directory.
-EXPECTED_ABI_VERSION = 18
+EXPECTED_ABI_VERSION = 19
 
 
 def header_abi_version() -> int:

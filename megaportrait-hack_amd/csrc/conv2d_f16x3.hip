@@ -1,0 +1,367 @@
+// Conv2d 3x3 (stride 1, padding 1) on the f16 matrix cores with fp32-class accuracy: the "f16x3" split of conv3d_f16x3.hip on NCHW
+// maps, with the epilogue G2d's ResBlock2D needs at inference (BatchNorm folded into weights and bias by the caller):
+//     y = act( conv(x, w) + bias[co] (+ residual[n,co,h,w]) ),   act = ReLU or identity
+//
+// Arithmetic (the 3-D direct kernel's): each operand tensor is scaled by its own power of two and split v*S = hi + lo with split_f16;
+// the product is Wlo*Xhi + Whi*Xhi + Whi*Xlo in the fp32 accumulator of v_mfma_f32_32x32x16_f16; the accumulator is unscaled (a power
+// of two: exact) and bias, residual and ReLU are applied in fp32.  Out-of-range and non-finite inputs are not clamped (split_f16), they
+// are counted in this unit's saturation counter, which mphip_f16x3_saturation_count sums with the others.
+//
+// Tile: a workgroup of 4 waves computes 64 output channels x (16 rows x 16 columns); a wave owns all 64 channels of 4 rows = 2 x 2
+// MFMA tiles (64 accumulator registers), so one tap costs 8 fragment reads for 12 MFMAs.  Per 16-channel chunk the workgroup stages
+//   the 18 x 18 halo tile, split while staging:      [part][kg][pixel][8] f16 = 20736 B   (zero padding lives in the masked loads)
+//   the chunk's packed 9-tap weight slab:            [part][tap][kg][co][8] f16 = 36864 B
+// = 57600 B of LDS, single buffered: two workgroups share a CU (2 waves per SIMD, 256 registers each) and one computes while the
+// other stages; inside a workgroup the next chunk's global loads are issued before the current chunk's MFMAs and written to LDS
+// after them.  Fragment reads are 16-byte and conflict-free: weights are co-contiguous, and a 16-lane ds_read_b128 group reads one
+// whole 16-pixel row (the lane -> pixel slot permutation of the 3-D kernel).
+//
+// MFMA operand layout (conv3d_f16x3.hip): A = weights [32 co x 16 ci], B = pixels [16 ci x 32 px]; lane l holds k = 8*(l>>5)..+7 of
+// row / column l&31; C: column = lane&31, row = (reg&3) + 8*(reg>>2) + 4*(lane>>5).
+#include <algorithm>
+
+#include "mphip_common.h"
+#include "mphip_conv.h"
+#include "mphip_f16x3.h"
+
+namespace mphip {
+
+__device__ unsigned long long g_conv2d_saturated;
+
+constexpr int C2_KC = 16;                              // input channels per chunk = K of one MFMA
+constexpr int C2_COT = 64;                             // output channels per workgroup (2 MFMA row tiles)
+constexpr int C2_TH = 16, C2_TW = 16;                  // output pixels per workgroup
+constexpr int C2_HH = C2_TH + 2, C2_HW = C2_TW + 2;    // halo tile
+constexpr int C2_XV = C2_HH * C2_HW;                   // 324 halo pixels
+constexpr int C2_X_PART = 2 * C2_XV * 8;               // halfs per part (hi or lo): [kg][pixel][8]
+constexpr int C2_SLAB_HALFS = 2 * 9 * 2 * C2_COT * 8;  // [part][tap][kg][co][8] = 18432 halfs = 36864 B per (co tile, chunk)
+constexpr int C2_NTHR = 256;
+
+static inline int c2_cots(int Co) { return (Co + C2_COT - 1) / C2_COT; }
+static size_t c2_packed_bytes(int Co, int Ci) { return 16 + (size_t)c2_cots(Co) * (Ci / C2_KC) * C2_SLAB_HALFS * 2; }
+
+static bool c2_supported(int N, int Ci, int Co, int H, int W) {
+    if (N < 1 || Ci < C2_KC || Co < 32 || H < 1 || W < 1 || Ci % C2_KC || Co % 32) return false;
+    const unsigned long long hw = (unsigned long long)H * (unsigned long long)W;
+    if (hw >= (1ull << 31)) return false;
+    if ((unsigned long long)N * Ci * hw >= (1ull << 31) || (unsigned long long)N * Co * hw >= (1ull << 31)) return false;
+    return c2_cots(Co) <= 65535;
+}
+
+// ---- weight packing: header (16 B, the 3-D pack's: [0] 1/scale [1] scale [2] max|w| bits [3] unused), then the slabs ---------------
+__global__ void __launch_bounds__(256) conv2d_absmax_kernel(const float *__restrict__ w, size_t n, unsigned *__restrict__ hdr) {
+    float m = 0.0f;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) m = fmaxf(m, fabsf(w[i]));
+    unsigned b = wave_umax(__float_as_uint(m));   // (non-negative floats order like their bits)
+    __shared__ unsigned red[4];
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = b;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        b = max(max(red[0], red[1]), max(red[2], red[3]));
+        if (b > __hip_atomic_load(hdr + 2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(hdr + 2, b);
+    }
+}
+
+// one thread = one 16-byte fragment (8 consecutive ci of one co and tap), hi and lo; output channels past Co are zeros
+__global__ void __launch_bounds__(256)
+conv2d_pack_kernel(const float *__restrict__ w, _Float16 *__restrict__ out, const unsigned *__restrict__ hdr_in, float *__restrict__ hdr_out,
+                   int Co, int Ci, int total) {
+    const float scale = weight_scale(hdr_in[2]);
+    const int nchunks = Ci / C2_KC;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i < total) {
+        const int co = i % C2_COT;
+        int r = i / C2_COT;
+        const int kg = r % 2; r /= 2;
+        const int tap = r % 9; r /= 9;
+        const int chunk = r % nchunks;
+        const int cot = r / nchunks;
+        const int cog = cot * C2_COT + co;
+        half8 hi, lo;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const int ci = chunk * C2_KC + kg * 8 + e;
+            const float v = cog < Co ? w[((size_t)cog * Ci + ci) * 9 + tap] : 0.0f;
+            _Float16 h, l;
+            split_f16(v * scale, h, l);
+            hi[e] = h; lo[e] = l;
+        }
+        const size_t slab = (size_t)cot * nchunks + chunk;
+        const size_t inner = ((size_t)(tap * 2 + kg) * C2_COT + co) * 8;
+        *reinterpret_cast<half8 *>(out + slab * C2_SLAB_HALFS + inner) = hi;
+        *reinterpret_cast<half8 *>(out + slab * C2_SLAB_HALFS + C2_SLAB_HALFS / 2 + inner) = lo;
+    }
+    if (i == 0) {
+        hdr_out[0] = 1.0f / scale;
+        hdr_out[1] = scale;
+    }
+}
+
+// ---- range descriptors -----------------------------------------------------------------------------------------------------------
+// max|x| of the input when the caller hands in no descriptor: one partial maximum per workgroup (any alignment of x)
+__global__ void __launch_bounds__(256) conv2d_range_kernel(const float *__restrict__ x, size_t n, float *__restrict__ range) {
+    unsigned m = 0;
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) m = max(m, range_bits(x[i]));
+    range_note_block(m, range, blockIdx.x, gridDim.x);
+}
+// the output's descriptor before the conv fills it: derive mode, `nslots` partial maxima at 0 (the epilogue folds its tiles into them
+// with an integer atomicMax on the float's bits: order-independent, so the descriptor is reproducible)
+__global__ void __launch_bounds__(256) conv2d_out_range_init_kernel(float *__restrict__ range, unsigned nslots) {
+    unsigned *r = reinterpret_cast<unsigned *>(range);
+    const unsigned i = blockIdx.x * 256 + threadIdx.x;
+    if (i < 4) r[i] = i == 3 ? nslots : 0u;
+    if (i < nslots) r[4 + i] = 0u;
+}
+
+// ---- the conv kernel -------------------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(C2_NTHR) __attribute__((amdgpu_waves_per_eu(2, 2)))
+conv2d_k3_f16x3_kernel(const float *__restrict__ x, const float *__restrict__ x_range, const _Float16 *__restrict__ wslabs,
+                       const float *__restrict__ whdr, const float *__restrict__ bias, const float *__restrict__ residual,
+                       float *__restrict__ y, float *__restrict__ out_range, int Ci, int Co, int H, int W, int relu, int tiles_w,
+                       int tiles_h, unsigned nslots) {
+    __shared__ __attribute__((aligned(16))) _Float16 smem[C2_SLAB_HALFS + 2 * C2_X_PART];
+    __shared__ unsigned red[4];
+    _Float16 *const Ws = smem;                  // [part][tap][kg][co][8]
+    _Float16 *const Xs = smem + C2_SLAB_HALFS;  // [part][kg][pixel][8]
+
+    float x_scale, x_unscale;
+    range_scale_block(x_range, x_scale, x_unscale);   // (folds the producer's partial maxima; barriers inside)
+
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int j = lane & 31, kg = lane >> 5;
+    int bid = blockIdx.x;
+    const int tw = bid % tiles_w; bid /= tiles_w;
+    const int th = bid % tiles_h;
+    const int n = bid / tiles_h;
+    const int cot = blockIdx.y;
+    const int h0 = th * C2_TH, w0 = tw * C2_TW;
+    const int nchunks = Ci / C2_KC;
+    const size_t HW = (size_t)H * W;
+    const unsigned HWu = (unsigned)HW;   // (a chunk's 16 channels hold fewer than 2^31 elements: 32-bit element offsets)
+    const float *const xn = x + (size_t)n * Ci * HW;
+
+    // X staging: an item is (channel pair p, halo pixel r): two 4-byte loads (the zero padding and the ragged edge are the mask), scale,
+    // split, one b32 write of hi and one of lo.  The four pairs of a 16-byte fragment go to neighbouring lanes: conflict-free writes.
+    constexpr int NX = 8 * C2_XV;                        // items per chunk
+    constexpr int XI = (NX + C2_NTHR - 1) / C2_NTHR;     // 11 per thread
+    constexpr int WI = C2_SLAB_HALFS * 2 / 16 / C2_NTHR; // 9 16-byte pieces of the weight slab per thread
+    static_assert(C2_SLAB_HALFS * 2 % (16 * C2_NTHR) == 0, "weight slab / thread count");
+    float xa[XI], xb[XI];
+    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+    u32x4 wq[WI];
+    unsigned sat = 0, okm = 0;
+#define C2_LOAD_CHUNK(c_)                                                                              \
+    {                                                                                                  \
+        const float *const xc_ = xn + (size_t)(c_) * C2_KC * HW;                                       \
+        int tid_ = tid;                                                                                \
+        asm volatile("" : "+v"(tid_)); /* opaque: keeps the per-item offsets out of registers across the K loop */ \
+        _Pragma("unroll") for (int i = 0; i < XI; ++i) {                                               \
+            const int e_ = i * C2_NTHR + tid_, ec_ = min(e_, NX - 1);                                  \
+            const int rest_ = ec_ >> 2;                                                                \
+            const int p_ = (rest_ / C2_XV) * 4 + (ec_ & 3), r_ = rest_ % C2_XV;                        \
+            const int gh_ = h0 - 1 + r_ / C2_HW, gw_ = w0 - 1 + r_ % C2_HW;                            \
+            const bool ok_ = e_ < NX && (unsigned)gh_ < (unsigned)H && (unsigned)gw_ < (unsigned)W;    \
+            /* unconditional loads from a clamped (always valid) address, a select later: no branch per load */ \
+            const unsigned off_ = (unsigned)(2 * p_) * HWu + (unsigned)min(max(gh_, 0), H - 1) * W + min(max(gw_, 0), W - 1); \
+            xa[i] = xc_[off_];                                                                         \
+            xb[i] = xc_[off_ + HWu];                                                                   \
+            okm = ok_ ? okm | (1u << i) : okm & ~(1u << i);   /* the select waits until the values are written to LDS */ \
+        }                                                                                              \
+        const u32x4 *const ws_ = reinterpret_cast<const u32x4 *>(wslabs + ((size_t)cot * nchunks + (c_)) * C2_SLAB_HALFS); \
+        _Pragma("unroll") for (int i = 0; i < WI; ++i) wq[i] = ws_[i * C2_NTHR + tid_];                \
+    }
+#define C2_WRITE_CHUNK()                                                                               \
+    {                                                                                                  \
+        int tid_ = tid;                                                                                \
+        asm volatile("" : "+v"(tid_));                                                                 \
+        _Pragma("unroll") for (int i = 0; i < XI; ++i) {                                               \
+            const int e_ = i * C2_NTHR + tid_;                                                         \
+            if (e_ < NX) {                                                                             \
+                const int dst_ = (e_ >> 2) * 8 + (e_ & 3) * 2;   /* e_ >> 2 = kg * C2_XV + pixel */    \
+                const bool ok_ = (okm >> i) & 1u;                                                      \
+                const float v0_ = ok_ ? xa[i] * x_scale : 0.0f, v1_ = ok_ ? xb[i] * x_scale : 0.0f;    \
+                sat += !(fabsf(v0_) <= F16_CLAMP) + !(fabsf(v1_) <= F16_CLAMP);   /* NaN counts */     \
+                _Float16 hA_, lA_, hB_, lB_;                                                           \
+                split_f16(v0_, hA_, lA_);                                                              \
+                split_f16(v1_, hB_, lB_);                                                              \
+                const half2v hv_ = {hA_, hB_}, lv_ = {lA_, lB_};                                       \
+                *reinterpret_cast<half2v *>(Xs + dst_) = hv_;                                          \
+                *reinterpret_cast<half2v *>(Xs + C2_X_PART + dst_) = lv_;                              \
+            }                                                                                          \
+        }                                                                                              \
+        _Pragma("unroll") for (int i = 0; i < WI; ++i) reinterpret_cast<u32x4 *>(Ws)[i * C2_NTHR + tid_] = wq[i]; \
+    }
+
+    // ds_read_b128 is serviced in 16-lane groups {0-3,12-15,20-27} / {4-11,16-19,28-31} per half-wave: slot jv gives each group one
+    // whole 16-pixel row (256 contiguous bytes = every bank once).  Slots only name accumulator columns, any bijection works.
+    const int jg = ((j >> 2) & 1) ^ ((j >> 3) & 1) ^ ((j >> 4) & 1);
+    const int jpos = j < 4 ? j : j < 12 ? j - 4 : j < 20 ? j - 8 : j < 28 ? j - 12 : j - 16;
+    const int jv = jg * 16 + jpos;
+    const int prow = wave * 4 + (jv >> 4), pcol = jv & 15;       // this lane's pixel in column tile t: (prow + 2t, pcol)
+    const int a_base = (kg * C2_COT + j) * 8;                    // + ((part*9 + tap)*2*64 + m*32)*8
+    const int b_base = (kg * C2_XV + prow * C2_HW + pcol) * 8;   // + (t*2*18 + tap offset)*8
+
+    f32x16 acc[2][2];
+#pragma unroll
+    for (int m = 0; m < 2; ++m)
+#pragma unroll
+        for (int t = 0; t < 2; ++t)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[m][t][r] = 0.0f;
+
+    C2_LOAD_CHUNK(0)
+    C2_WRITE_CHUNK()
+    __syncthreads();
+    for (int c = 0; c < nchunks; ++c) {
+        const bool more = c + 1 < nchunks;
+        if (more) C2_LOAD_CHUNK(c + 1)   // in flight during this chunk's MFMAs
+#pragma unroll
+        for (int tap = 0; tap < 9; ++tap) {
+            half8 ah[2], al[2], bh[2], bl[2];
+            const int toff = ((tap / 3) * C2_HW + tap % 3) * 8;
+#pragma unroll
+            for (int m = 0; m < 2; ++m) {
+                ah[m] = *reinterpret_cast<const half8 *>(Ws + a_base + (tap * 2 * C2_COT + m * 32) * 8);
+                al[m] = *reinterpret_cast<const half8 *>(Ws + C2_SLAB_HALFS / 2 + a_base + (tap * 2 * C2_COT + m * 32) * 8);
+            }
+#pragma unroll
+            for (int t = 0; t < 2; ++t) {
+                bh[t] = *reinterpret_cast<const half8 *>(Xs + b_base + t * 2 * C2_HW * 8 + toff);
+                bl[t] = *reinterpret_cast<const half8 *>(Xs + C2_X_PART + b_base + t * 2 * C2_HW * 8 + toff);
+            }
+#pragma unroll
+            for (int m = 0; m < 2; ++m)
+#pragma unroll
+                for (int t = 0; t < 2; ++t) acc[m][t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[m], bh[t], acc[m][t], 0, 0, 0);
+#pragma unroll
+            for (int m = 0; m < 2; ++m)
+#pragma unroll
+                for (int t = 0; t < 2; ++t) acc[m][t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[m], bh[t], acc[m][t], 0, 0, 0);
+#pragma unroll
+            for (int m = 0; m < 2; ++m)
+#pragma unroll
+                for (int t = 0; t < 2; ++t) acc[m][t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[m], bl[t], acc[m][t], 0, 0, 0);
+        }
+        if (more) {
+            __syncthreads();   // every wave is past its last fragment read of this chunk
+            C2_WRITE_CHUNK()
+            __syncthreads();
+        }
+    }
+
+#undef C2_LOAD_CHUNK
+#undef C2_WRITE_CHUNK
+
+    // epilogue: unscale (a power of two), bias, residual, ReLU in fp32; stores masked at the ragged edge and past Co
+    const float unscale = whdr[0] * x_unscale;
+    unsigned ymax = 0;
+#pragma unroll
+    for (int m = 0; m < 2; ++m) {
+        const int co0 = cot * C2_COT + m * 32;
+        if (co0 < Co) {   // (Co % 32 == 0: a row tile is whole or absent; workgroup-uniform)
+#pragma unroll
+            for (int t = 0; t < 2; ++t) {
+                const int gh = h0 + prow + 2 * t, gw = w0 + pcol;
+                if (gh < H && gw < W) {
+                    const size_t o = ((size_t)n * Co + co0 + 4 * kg) * HW + (size_t)gh * W + gw;
+#pragma unroll
+                    for (int reg = 0; reg < 16; ++reg) {
+                        const int row = (reg & 3) + 8 * (reg >> 2);
+                        const size_t oi = o + (size_t)row * HW;
+                        float v = acc[m][t][reg] * unscale + bias[co0 + 4 * kg + row];
+                        if (residual) v += residual[oi];
+                        if (relu) v = v < 0.0f ? 0.0f : v;   // (keeps NaN, like torch's relu)
+                        y[oi] = v;
+                        ymax = max(ymax, range_bits(v));
+                    }
+                }
+            }
+        }
+    }
+    if (out_range) {   // workgroup-uniform
+        ymax = wave_umax(ymax);
+        if (lane == 0) red[wave] = ymax;
+        __syncthreads();
+        if (tid == 0) {
+            const unsigned mx = max(max(red[0], red[1]), max(red[2], red[3]));
+            const unsigned slot = (blockIdx.x + gridDim.x * blockIdx.y) % nslots;
+            if (mx) atomicMax(reinterpret_cast<unsigned *>(out_range) + 4 + slot, mx);
+        }
+    }
+    if (__builtin_amdgcn_ballot_w64(sat != 0) != 0) {  // never taken in normal operation
+        unsigned tot = sat;
+#pragma unroll
+        for (int sft = 32; sft >= 1; sft >>= 1) tot += __shfl_xor(tot, sft, 64);
+        if (lane == 0) atomicAdd(&g_conv2d_saturated, (unsigned long long)tot);
+    }
+}
+
+int conv2d_f16x3_saturation(unsigned long long *count, int reset) { return f16x3_counter_read(&g_conv2d_saturated, count, reset); }
+
+}  // namespace mphip
+
+using namespace mphip;
+
+extern "C" int mphip_conv2d_supported(int N, int Ci, int Co, int H, int W) { return c2_supported(N, Ci, Co, H, W) ? 1 : 0; }
+
+extern "C" size_t mphip_conv2d_packed_weight_bytes(int Co, int Ci) {
+    if (Ci < C2_KC || Co < 32 || Ci % C2_KC || Co % 32) return 0;
+    return c2_packed_bytes(Co, Ci);
+}
+
+extern "C" int mphip_pack_conv2d_weight(const float *w_oihw, void *w_packed, int Co, int Ci, void *stream) {
+    MPHIP_REQUIRE(w_oihw && w_packed, "pack_conv2d_weight: null pointer");
+    MPHIP_REQUIRE(Ci >= C2_KC && Co >= 32 && Ci % C2_KC == 0 && Co % 32 == 0 && c2_cots(Co) <= 65535,
+                  "pack_conv2d_weight: Co = %d, Ci = %d: Ci must be a multiple of 16 and Co a multiple of 32", Co, Ci);
+    MPHIP_REQUIRE(((uintptr_t)w_packed & 15) == 0, "pack_conv2d_weight: w_packed must be 16-byte aligned");
+    const long long total = (long long)c2_cots(Co) * (Ci / C2_KC) * 9 * 2 * C2_COT;
+    MPHIP_REQUIRE(total < (1ll << 31) - 256, "pack_conv2d_weight: Co = %d, Ci = %d is too large", Co, Ci);
+    hipStream_t s = (hipStream_t)stream;
+    zero_fill(w_packed, 16, s);   // header: the absmax kernel accumulates with atomicMax
+    const size_t n = (size_t)Co * Ci * 9;
+    hipLaunchKernelGGL(conv2d_absmax_kernel, dim3((unsigned)std::min<size_t>(1024, (n + 2047) / 2048)), dim3(256), 0, s, w_oihw, n,
+                       (unsigned *)w_packed);
+    hipLaunchKernelGGL(conv2d_pack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, w_oihw,
+                       (_Float16 *)((char *)w_packed + 16), (const unsigned *)w_packed, (float *)w_packed, Co, Ci, (int)total);
+    return check_launch("pack_conv2d_weight");
+}
+
+extern "C" size_t mphip_conv2d_workspace_bytes(int N, int Ci, int Co, int H, int W) {
+    if (!c2_supported(N, Ci, Co, H, W)) return 0;
+    return (size_t)MPHIP_RANGE_FLOATS * sizeof(float);   // the library-computed descriptor of x (x_range == NULL)
+}
+
+extern "C" int mphip_conv2d_fwd(const float *x, const float *x_range, const void *w_packed, const float *bias, const float *residual,
+                                float *y, float *out_range, int N, int Ci, int Co, int H, int W, int relu, void *workspace,
+                                size_t workspace_bytes, void *stream) {
+    MPHIP_REQUIRE(x && w_packed && bias && y, "conv2d_fwd: null pointer");
+    MPHIP_REQUIRE(c2_supported(N, Ci, Co, H, W),
+                  "conv2d_fwd: unsupported shape N=%d Ci=%d Co=%d H=%d W=%d (Ci %% 16 == 0, Co %% 32 == 0, N, H, W >= 1, fewer than 2^31 "
+                  "elements per tensor)", N, Ci, Co, H, W);
+    MPHIP_REQUIRE(((uintptr_t)w_packed & 15) == 0 && ((uintptr_t)x & 3) == 0 && ((uintptr_t)y & 3) == 0,
+                  "conv2d_fwd: w_packed must be 16-byte aligned, x and y 4-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    if (!x_range) {
+        const size_t need = (size_t)MPHIP_RANGE_FLOATS * sizeof(float);
+        if (!workspace || workspace_bytes < need) {
+            set_error("conv2d_fwd: workspace %zu bytes < required %zu", workspace_bytes, need);
+            return MPHIP_EWORKSPACE;
+        }
+        MPHIP_REQUIRE(((uintptr_t)workspace & 3) == 0, "conv2d_fwd: the workspace must be 4-byte aligned");
+        const size_t n = (size_t)N * Ci * H * W;
+        const unsigned blocks = (unsigned)std::min<size_t>(2048, (n + 8191) / 8192);
+        hipLaunchKernelGGL(conv2d_range_kernel, dim3(blocks ? blocks : 1), dim3(256), 0, s, x, n, (float *)workspace);
+        x_range = (const float *)workspace;
+    }
+    const int tiles_w = cdiv(W, C2_TW), tiles_h = cdiv(H, C2_TH);
+    const long long tiles = (long long)N * tiles_h * tiles_w;
+    MPHIP_REQUIRE(tiles < (1ll << 31), "conv2d_fwd: %lld tiles do not fit a launch", tiles);
+    const dim3 grid((unsigned)tiles, (unsigned)c2_cots(Co));
+    const unsigned nslots = (unsigned)std::min<long long>(tiles * c2_cots(Co), (long long)RANGE_MAX_PARTS);
+    if (out_range) hipLaunchKernelGGL(conv2d_out_range_init_kernel, dim3(cdiv(nslots + 4, 256)), dim3(256), 0, s, out_range, nslots);
+    hipLaunchKernelGGL(conv2d_k3_f16x3_kernel, grid, dim3(C2_NTHR), 0, s, x, x_range, (const _Float16 *)((const char *)w_packed + 16),
+                       (const float *)w_packed, bias, residual, y, out_range, Ci, Co, H, W, relu, tiles_w, tiles_h, nslots);
+    return check_launch("conv2d_fwd");
+}

@@ -338,6 +338,14 @@ class G2d(M.G2dHead):
         M.native_final_conv(self, enable)
         return self
 
+    def native_body(self, enable: bool = True) -> "G2d":
+        """Opt-in, inference only: run every ResBlock2D of the body (`res_blocks`, `upsample1/2/3[1]`) as model.ResBlock2DFused —
+        BatchNorm folded, the 3x3 convs on the matrix cores with fp32-class accuracy (csrc/conv2d_f16x3.hip) — over the blocks' own
+        children: same Parameter objects, same state-dict keys.  `enable=False` puts the original blocks back.  In train mode, under
+        autograd or on a half model the fused blocks evaluate the original PyTorch expression."""
+        M.native_g2d_body(self, enable)
+        return self
+
     def body(self, x):
         """[B,512,h,w] (the head's output) -> image [B,3,8h,8w] in (0,1) (model.py:758-762)."""
         x = self.res_blocks(x)

@@ -58,6 +58,12 @@ class Gbase(M._HotSliceRunner, nn.Module):
         M.native_final_conv(self.G2d, enable)
         return self
 
+    def native_body(self, enable: bool = True) -> "Gbase":
+        """Opt-in (off by default), inference only: G2d's ResBlock2D body as model.ResBlock2DFused — BatchNorm folded, 3x3 convs on the
+        matrix cores (model.native_g2d_body); `enable=False` restores the original blocks.  Same parameters and state-dict keys."""
+        M.native_g2d_body(self.G2d, enable)
+        return self
+
     def _nhwc(self, x):
         return x.contiguous(memory_format=torch.channels_last) if getattr(self, "_cl2d", False) and x.dim() == 4 else x
 

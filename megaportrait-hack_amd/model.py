@@ -18,6 +18,7 @@ import os
 
 import torch
 import torch.nn as nn
+import torch.nn.functional as F
 
 from . import autograd as ag
 from . import ops
@@ -721,6 +722,148 @@ def native_final_conv(g2d: nn.Module, enable: bool = True) -> bool:
     old = cur.__dict__.pop("_replaced", None)
     g2d.final_conv = old if old is not None else nn.Sequential(*cur.children())
     return True
+
+
+def fold_batchnorm(conv: nn.Module, bn: nn.Module):
+    """Eval-mode `bn(conv(x))` as one conv: s = gamma / sqrt(running_var + eps), w' = w * s[:, None, None, None],
+    b' = (b - running_mean) * s + beta, in the parameters' own dtype (fp32 on the native path) -> (w', b')."""
+    w, b = conv.weight.detach(), conv.bias.detach()
+    s = bn.weight.detach() / torch.sqrt(bn.running_var + bn.eps)
+    return (w * s[:, None, None, None]).contiguous(), ((b - bn.running_mean) * s + bn.bias.detach()).contiguous()
+
+
+def _is_conv2d(m, k: int) -> bool:
+    return (isinstance(m, nn.Conv2d) and m.kernel_size == (k, k) and m.stride == (1, 1) and m.padding == ((k - 1) // 2,) * 2
+            and m.dilation == (1, 1) and m.groups == 1 and m.padding_mode == "zeros" and m.bias is not None)
+
+
+def _is_bn2d(m, channels: int) -> bool:
+    return (isinstance(m, nn.BatchNorm2d) and m.num_features == channels and m.affine and m.track_running_stats
+            and m.running_mean is not None and m.running_var is not None)
+
+
+class ResBlock2DFused(nn.Module):
+    """G2d's ResBlock2D (model.py:600-640, `downsample` off) with an opt-in inference path on the matrix cores: BatchNorm folded into
+    the convs, each 3x3 conv one launch of csrc/conv2d_f16x3.hip (f16x3 arithmetic: fp32-class accuracy) with bias, ReLU and the
+    residual add in its epilogue.  The children are the original block's own `conv1, bn1, conv2, bn2, shortcut` — the same Parameter
+    and buffer objects, the same state-dict keys — built over an existing block by `from_block`.
+
+    The native path runs only in eval mode, without autograd (ag.needs_grad false), on an fp32 module and a supported shape (Ci % 16,
+    Co % 32); otherwise forward evaluates the original block's expression in PyTorch, exactly encoders2d.ResBlock2D.forward.  There are
+    NO backward kernels and NO half-model path for this block: training, fine-tuning and .half() / .bfloat16() instances take the
+    PyTorch expression.  fp16 / bf16 inputs (torch.autocast upstream) are widened (model._f32) and the result is fp32; channels_last
+    inputs are copied to NCHW once.  A 1x1 shortcut runs through the existing k = 1 conv with its BatchNorm folded.  Each conv leaves
+    the range descriptor of its output on the tensor, so a fused block that directly follows does not scan its input again."""
+
+    def __init__(self, in_channels: int, out_channels: int):
+        super().__init__()
+        self.downsample = False
+        self.conv1 = nn.Conv2d(in_channels, out_channels, 3, stride=1, padding=1)
+        self.bn1 = nn.BatchNorm2d(out_channels)
+        self.conv2 = nn.Conv2d(out_channels, out_channels, 3, stride=1, padding=1)
+        self.bn2 = nn.BatchNorm2d(out_channels)
+        if in_channels != out_channels:
+            self.shortcut = nn.Sequential(nn.Conv2d(in_channels, out_channels, 1, stride=1), nn.BatchNorm2d(out_channels))
+        else:
+            self.shortcut = nn.Identity()
+
+    @staticmethod
+    def matches(block) -> bool:
+        """Duck-typed: is `block` a ResBlock2D (this package's or the reference's) the fused path can stand in for?"""
+        if isinstance(block, ResBlock2DFused):
+            return False
+        conv1, bn1, conv2, bn2 = (getattr(block, n, None) for n in ("conv1", "bn1", "conv2", "bn2"))
+        sc = getattr(block, "shortcut", None)
+        if getattr(block, "downsample", True) is not False or not (_is_conv2d(conv1, 3) and _is_conv2d(conv2, 3)):
+            return False
+        co = conv1.out_channels
+        if conv2.in_channels != co or conv2.out_channels != co or not (_is_bn2d(bn1, co) and _is_bn2d(bn2, co)):
+            return False
+        if isinstance(sc, nn.Identity):
+            return conv1.in_channels == co
+        return (isinstance(sc, nn.Sequential) and len(sc) == 2 and _is_conv2d(sc[0], 1) and sc[0].in_channels == conv1.in_channels
+                and sc[0].out_channels == co and _is_bn2d(sc[1], co))
+
+    @classmethod
+    def from_block(cls, block: nn.Module) -> "ResBlock2DFused":
+        if not cls.matches(block):
+            raise TypeError(f"ResBlock2DFused.from_block: expected a ResBlock2D without downsampling (3x3 stride-1 convs with bias, "
+                            f"BatchNorm2d with running statistics, Identity or Conv2d 1x1 + BatchNorm2d shortcut), got {block}")
+        new = cls.__new__(cls)
+        nn.Module.__init__(new)
+        new.downsample = False
+        for name in ("conv1", "bn1", "conv2", "bn2", "shortcut"):
+            setattr(new, name, getattr(block, name))
+        new.training = block.training   # (the children keep their own flags: they are the block's)
+        return new
+
+    def _native_ok(self, x) -> bool:
+        if self.training or ag.needs_grad(self, x) or self.conv1.weight.dtype != torch.float32:
+            return False
+        if not (isinstance(x, torch.Tensor) and x.dim() == 4 and x.shape[1] == self.conv1.in_channels and x.numel() > 0):
+            return False
+        n, ci, h, w = x.shape
+        co = self.conv1.out_channels
+        return ops.conv2d_supported(n, ci, co, h, w) and ops.conv2d_supported(n, co, co, h, w)
+
+    def _folded(self):
+        """(conv1', conv2', shortcut' or None): BatchNorm folded in fp32 torch ops and packed; cached until a parameter or a running
+        buffer changes (their versions are the key)."""
+        mods = [self.conv1, self.bn1, self.conv2, self.bn2] + (list(self.shortcut) if isinstance(self.shortcut, nn.Sequential) else [])
+        ts = [t for m in mods for t in ((m.weight, m.bias) + ((m.running_mean, m.running_var) if isinstance(m, nn.BatchNorm2d) else ()))]
+        key = tuple((t.data_ptr(), t._version) for t in ts) + (str(ts[0].device), ops.weight_epoch())
+        hit = self.__dict__.get("_mphip_fold")
+        if hit is None or hit[0] != key or ops.repacking():
+            with torch.no_grad():
+                p1 = ops.PackedConv2d(*fold_batchnorm(self.conv1, self.bn1))
+                p2 = ops.PackedConv2d(*fold_batchnorm(self.conv2, self.bn2))
+                ps = None
+                if len(mods) > 4:
+                    ws, bs = fold_batchnorm(mods[4], mods[5])
+                    ps = ops.PackedConv(ws.view(ws.shape[0], ws.shape[1], 1, 1, 1), bs)
+            hit = (key, (p1, p2, ps))
+            self.__dict__["_mphip_fold"] = hit
+        return hit[1]
+
+    def forward(self, x):
+        if not self._native_ok(x):
+            y = F.relu(self.bn1(self.conv1(x)))
+            y = self.bn2(self.conv2(y))
+            return F.relu(y + self.shortcut(x))
+        xc = _f32(x).contiguous()   # (the kernels read NCHW: a channels_last map is copied once)
+        p1, p2, ps = self._folded()
+        y1 = ops.conv2d(xc, p1, relu=True, want_range=True)
+        if ps is not None:
+            n, c, h, w = xc.shape
+            idt = ops.conv3d(xc.reshape(n, c, 1, h, w), ps, x_range=ops.current_range(xc)).reshape(n, ps.co, h, w)
+        else:
+            idt = xc
+        return ops.conv2d(y1, p2, residual=idt, relu=True, want_range=True)
+
+
+_G2D_BODY_SLOTS = (("upsample1", 1), ("upsample2", 1), ("upsample3", 1))
+
+
+def native_g2d_body(g2d: nn.Module, enable: bool = True) -> bool:
+    """Swaps every matching ResBlock2D of `g2d.res_blocks`, `g2d.upsample1[1]`, `upsample2[1]`, `upsample3[1]` (this package's G2d or
+    the reference's, model.py:720-746) for a ResBlock2DFused over the same children, or puts the very objects it replaced back.
+    Returns whether anything changed.  Off by default everywhere."""
+    seqs = [(getattr(g2d, "res_blocks", None), None)] + [(getattr(g2d, name, None), idx) for name, idx in _G2D_BODY_SLOTS]
+    changed = False
+    for seq, only in seqs:
+        if not isinstance(seq, nn.Sequential):
+            continue
+        for i in (range(len(seq)) if only is None else [only] if len(seq) > only else []):
+            cur = seq[i]
+            if enable and ResBlock2DFused.matches(cur):
+                new = ResBlock2DFused.from_block(cur)
+                new.__dict__["_replaced"] = cur   # (not a registered child: the module tree and the state-dict keys stay as they were)
+                seq[i] = new
+                changed = True
+            elif not enable and isinstance(cur, ResBlock2DFused) and "_replaced" in cur.__dict__:
+                seq[i] = cur.__dict__.pop("_replaced")
+                changed = True
+    return changed
 
 
 class _HotSliceRunner(_ModelDtype):

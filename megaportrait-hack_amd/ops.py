@@ -146,6 +146,14 @@ def absmax_range(x: torch.Tensor) -> torch.Tensor:
     return rng
 
 
+def current_range(x: torch.Tensor) -> Optional[torch.Tensor]:
+    """The descriptor its producer left on x, if it can be trusted here (see _range_for on hipGraph captures), else None."""
+    hit = tensor_range(x) if _RANGES_ENABLED else None
+    if hit is not None and torch.cuda.is_current_stream_capturing() and getattr(x, "_mphip_range_capture", -1) != _capture_epoch:
+        hit = None
+    return hit
+
+
 def _range_for(x: torch.Tensor, given: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Operand-scale descriptor of a conv input: the one its producer noted, else one streaming pass.
     While a hipGraph is being captured a descriptor cached on a tensor of unknown origin is NOT
@@ -1181,6 +1189,74 @@ def g2d_final_bwd(x, y, dy, stats, gamma, beta, w, want_params: bool = True):
                                        _ptr(dbeta), _ptr(dw), _ptr(db), n, c, co, h, wd, g, _ptr(ws), ws_bytes, _stream()),
                "mphip_g2d_final_bwd")
     return dx, dgamma, dbeta, dw, db
+
+
+# ------------------------------------------------------------------ Conv2d 3x3 on the matrix cores (csrc/conv2d_f16x3.hip)
+class PackedConv2d:
+    """One 3x3, stride 1, padding 1 Conv2d for ops.conv2d: OIHW fp32 weight + bias, packed lazily into the f16x3 slabs described in
+    include/mphip.h (mphip_pack_conv2d_weight).  `key` = (data_ptr, _version, device, weight_epoch()) of the tensors it was built from,
+    like the other packs: an owner re-creates the object when `PackedConv2d.key_of(weight, bias) != pack.key`."""
+
+    __slots__ = ("weight", "bias", "co", "ci", "key", "_packed")
+
+    def __init__(self, weight: torch.Tensor, bias: torch.Tensor):
+        self.key = PackedConv2d.key_of(weight, bias)
+        weight = _req(weight.detach(), "conv2d weight")
+        if weight.dim() != 4 or tuple(weight.shape[2:]) != (3, 3):
+            raise RuntimeError(f"PackedConv2d: expected an OIHW 3x3 weight, got {tuple(weight.shape)}")
+        if bias is None or tuple(bias.shape) != (weight.shape[0],):
+            raise RuntimeError("PackedConv2d: a bias of Co elements is required")
+        self.co, self.ci = int(weight.shape[0]), int(weight.shape[1])
+        if _lib.load().mphip_conv2d_packed_weight_bytes(self.co, self.ci) == 0:
+            raise RuntimeError(f"PackedConv2d: Co={self.co} Ci={self.ci} unsupported (Ci % 16 == 0 and Co % 32 == 0 are required)")
+        self.weight = weight
+        self.bias = _req(bias.detach(), "conv2d bias")
+        self._packed = None
+
+    @staticmethod
+    def key_of(weight: torch.Tensor, bias: Optional[torch.Tensor]):
+        return (weight.data_ptr(), weight._version, None if bias is None else (bias.data_ptr(), bias._version), str(weight.device),
+                weight_epoch())
+
+    def packed(self) -> torch.Tensor:
+        if self._packed is None:
+            lib = _lib.load()
+            nbytes = lib.mphip_conv2d_packed_weight_bytes(self.co, self.ci)
+            wp = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=self.weight.device)
+            _lib.check(lib.mphip_pack_conv2d_weight(_ptr(self.weight), _ptr(wp), self.co, self.ci, _stream()), "mphip_pack_conv2d_weight")
+            self._packed = wp
+        return self._packed
+
+
+def conv2d_supported(n: int, ci: int, co: int, h: int, w: int) -> bool:
+    return bool(_lib.load().mphip_conv2d_supported(int(n), int(ci), int(co), int(h), int(w)))
+
+
+def conv2d(x: torch.Tensor, pack: PackedConv2d, residual: Optional[torch.Tensor] = None, relu: bool = False,
+           x_range: Optional[torch.Tensor] = None, want_range: bool = False) -> torch.Tensor:
+    """y = act(conv3x3(x) + bias (+ residual)) on NCHW fp32, padding 1 (mphip_conv2d_fwd): the f16x3 arithmetic, fp32-class accuracy.
+    x_range: the input's range descriptor; without one the descriptor its producer tagged on x is used, else the library scans x.
+    want_range: y comes back tagged with the descriptor of its exact max|y| (ops.tensor_range(y)), which the next conv2d picks up."""
+    x = _req(x, "x")
+    if x.dim() != 4 or x.shape[1] != pack.ci:
+        raise RuntimeError(f"conv2d: input {tuple(x.shape)} does not match Ci={pack.ci}")
+    n, ci, h, w = x.shape
+    lib = _lib.load()
+    if not lib.mphip_conv2d_supported(n, ci, pack.co, h, w):
+        raise RuntimeError(f"conv2d: unsupported shape N={n} Ci={ci} Co={pack.co} H={h} W={w} (there is no fallback)")
+    if residual is not None:
+        residual = _req(residual, "residual")
+        if tuple(residual.shape) != (n, pack.co, h, w):
+            raise RuntimeError(f"conv2d: residual {tuple(residual.shape)} does not match the output {(n, pack.co, h, w)}")
+    xr = x_range if x_range is not None else current_range(x)   # None: the library scans x
+    ws_bytes = lib.mphip_conv2d_workspace_bytes(n, ci, pack.co, h, w)
+    ws = torch.empty((ws_bytes + 3) // 4, dtype=torch.float32, device=x.device) if xr is None else None
+    y = torch.empty((n, pack.co, h, w), dtype=torch.float32, device=x.device)
+    out_range = new_range(x.device) if want_range else None
+    _lib.check(lib.mphip_conv2d_fwd(_ptr(x), _ptr(xr), _ptr(pack.packed()), _ptr(pack.bias), _ptr(residual), _ptr(y), _ptr(out_range),
+                                    n, ci, pack.co, h, w, int(bool(relu)), _ptr(ws), ws_bytes if ws is not None else 0, _stream()),
+               "mphip_conv2d_fwd")
+    return tag_range(y, out_range)
 
 
 def avgpool2_bwd(dout: torch.Tensor) -> torch.Tensor:

@@ -43,6 +43,9 @@ def parse(argv=None):
                     help="run motionEncoder and G2d in torch.channels_last (MIOpen NHWC kernels; +15 %% frames/s with --fp16 on MI355X)")
     ap.add_argument("--native-final-conv", action="store_true",
                     help="run G2d's final GroupNorm-ReLU-conv-sigmoid as the fused HIP kernels (gbase.Gbase.native_final_conv; off by default)")
+    ap.add_argument("--native-g2d-body", action="store_true",
+                    help="run G2d's ResBlock2D body with BatchNorm folded and its 3x3 convs on the matrix cores "
+                         "(gbase.Gbase.native_body; inference only, fp32 models; off by default)")
     ap.add_argument("--fp16", action="store_true",
                     help="run the PyTorch-ROCm 2D modules under torch.autocast(float16) (the reference's policy, train.py:188); "
                          "the HIP hot path stays fp32-class")
@@ -163,6 +166,8 @@ def run(job: dict, args, rank: int, world: int) -> List[str]:
         g.channels_last_2d()
     if args.native_final_conv:
         g.native_final_conv()
+    if args.native_g2d_body:
+        g.native_body()
     xs = _load_tensor(job["source_tensor"]) if job["source_tensor"] else _load_image(job["source"])
     n = _load_tensor(job["drivers_tensor"]).shape[0] if job["drivers_tensor"] else len(job["drivers"])
     b, e, outputs = shard_plan(job, n, rank, world)
