@@ -39,7 +39,7 @@ extern "C" {
 
 /* ABI version of this header.  Bumped whenever an exported signature or a packed layout changes; mphip_version() returns the
  * value the LIBRARY was built with — compare the two after dlopen (the ctypes binding does, and refuses a mismatch). */
-#define MPHIP_ABI_VERSION 19
+#define MPHIP_ABI_VERSION 20
 int mphip_version(void);
 /* hipGraph hygiene (ABI 13).  On ROCm 7.x a MEMSET node of a captured hipGraph is not reliably ordered with its neighbouring kernel nodes
  * (observed twice: stale f16x3 pack headers, r03; a training step's loss that kept its previous value, r04-r05 — ATen's multi-block
@@ -568,6 +568,24 @@ size_t mphip_conv2d_workspace_bytes(int N, int Ci, int Co, int H, int W);
 int mphip_conv2d_fwd(const float *x, const float *x_range, const void *w_packed, const float *bias, const float *residual, float *y,
                      float *out_range, int N, int Ci, int Co, int H, int W, int relu, void *workspace, size_t workspace_bytes,
                      void *stream);
+/* Two sources, normalised while staged (ABI 20; csrc/conv2d_gn_f16x3.hip), for Eapp's ResBlock_Custom (reference model.py:110-123):
+ *     y = act( conv([s1 ; s2], w) + bias (+ residual) ),   s_i = x_i, or relu_i?(x_i * scale_i[n,c] + shift_i[n,c]) with a table
+ * the conv of the channel concatenation of x1 [N,C1,H,W] and x2 [N,C2,H,W] (x2 == NULL and C2 == 0: one source), which is never
+ * written.  w_packed is the ordinary pack (mphip_pack_conv2d_weight) of an OIHW weight with Ci = C1 + C2; tile, arithmetic, epilogue and
+ * out_range are mphip_conv2d_fwd's, and without tables and a second source so are the bits of y.
+ *   affine_i: NULL, or table [N][C_i][2] = (scale, shift) of mphip_groupnorm_affine_table.  An in-image pixel is staged as
+ *          x * scale + shift (a multiply, then an add), then max(., 0) if relu_i; padding stays 0 in the ACTIVATED map.  A source with a
+ *          table must bring its descriptor x_i_range, the table call's out_range (the bound of the normalised tensor, not of x_i).
+ *   x_i_range: descriptor of what the source stages; NULL on a source without a table: the library scans it (workspace:
+ *          mphip_conv2d_cat_workspace_bytes).  The kernel folds both and uses the smaller power-of-two scale for both sources.
+ *   y must not overlap x1, x2 or residual.  C1 % 16 == 0, C2 % 16 == 0, Co % 32 == 0, N*(C1+C2)*H*W and N*Co*H*W below 2^31.
+ * GroupNorm without parameters (F.group_norm(x, 32)): mphip_groupnorm_stats, then the table call with gamma = 1, beta = 0.           */
+int mphip_conv2d_cat_supported(int N, int C1, int C2, int Co, int H, int W);
+size_t mphip_conv2d_cat_workspace_bytes(int N, int C1, int C2, int Co, int H, int W);
+int mphip_conv2d_cat_fwd(const float *x1, const float *affine1, int relu1, const float *x1_range, int C1, const float *x2,
+                         const float *affine2, int relu2, const float *x2_range, int C2, const void *w_packed, const float *bias,
+                         const float *residual, float *y, float *out_range, int N, int Co, int H, int W, int relu, void *workspace,
+                         size_t workspace_bytes, void *stream);
 
 /* The reference's reduced-precision policy for the convs (train.py:145,188: the generator step runs under torch.cuda.amp.autocast(), its
  * conv3d calls take f16 operands with fp32 accumulation).  mphip_conv3d_set_half_products(1) makes the CALLING THREAD's subsequent precision-1

@@ -18,35 +18,11 @@
 //
 // MFMA operand layout (conv3d_f16x3.hip): A = weights [32 co x 16 ci], B = pixels [16 ci x 32 px]; lane l holds k = 8*(l>>5)..+7 of
 // row / column l&31; C: column = lane&31, row = (reg&3) + 8*(reg>>2) + 4*(lane>>5).
-#include <algorithm>
-
-#include "mphip_common.h"
-#include "mphip_conv.h"
-#include "mphip_f16x3.h"
+#include "conv2d_f16x3_tile.h"   // the constants, the shape rule and the tile code (shared with conv2d_gn_f16x3.hip)
 
 namespace mphip {
 
 __device__ unsigned long long g_conv2d_saturated;
-
-constexpr int C2_KC = 16;                              // input channels per chunk = K of one MFMA
-constexpr int C2_COT = 64;                             // output channels per workgroup (2 MFMA row tiles)
-constexpr int C2_TH = 16, C2_TW = 16;                  // output pixels per workgroup
-constexpr int C2_HH = C2_TH + 2, C2_HW = C2_TW + 2;    // halo tile
-constexpr int C2_XV = C2_HH * C2_HW;                   // 324 halo pixels
-constexpr int C2_X_PART = 2 * C2_XV * 8;               // halfs per part (hi or lo): [kg][pixel][8]
-constexpr int C2_SLAB_HALFS = 2 * 9 * 2 * C2_COT * 8;  // [part][tap][kg][co][8] = 18432 halfs = 36864 B per (co tile, chunk)
-constexpr int C2_NTHR = 256;
-
-static inline int c2_cots(int Co) { return (Co + C2_COT - 1) / C2_COT; }
-static size_t c2_packed_bytes(int Co, int Ci) { return 16 + (size_t)c2_cots(Co) * (Ci / C2_KC) * C2_SLAB_HALFS * 2; }
-
-static bool c2_supported(int N, int Ci, int Co, int H, int W) {
-    if (N < 1 || Ci < C2_KC || Co < 32 || H < 1 || W < 1 || Ci % C2_KC || Co % 32) return false;
-    const unsigned long long hw = (unsigned long long)H * (unsigned long long)W;
-    if (hw >= (1ull << 31)) return false;
-    if ((unsigned long long)N * Ci * hw >= (1ull << 31) || (unsigned long long)N * Co * hw >= (1ull << 31)) return false;
-    return c2_cots(Co) <= 65535;
-}
 
 // ---- weight packing: header (16 B, the 3-D pack's: [0] 1/scale [1] scale [2] max|w| bits [3] unused), then the slabs ---------------
 __global__ void __launch_bounds__(256) conv2d_absmax_kernel(const float *__restrict__ w, size_t n, unsigned *__restrict__ hdr) {
@@ -113,189 +89,22 @@ __global__ void __launch_bounds__(256) conv2d_out_range_init_kernel(float *__res
     if (i < nslots) r[4 + i] = 0u;
 }
 
-// ---- the conv kernel -------------------------------------------------------------------------------------------------------------
+// ---- the conv kernel: the plain instantiation of conv2d_f16x3_tile.h ----------------------------------------------------------------
 __global__ void __launch_bounds__(C2_NTHR) __attribute__((amdgpu_waves_per_eu(2, 2)))
 conv2d_k3_f16x3_kernel(const float *__restrict__ x, const float *__restrict__ x_range, const _Float16 *__restrict__ wslabs,
                        const float *__restrict__ whdr, const float *__restrict__ bias, const float *__restrict__ residual,
                        float *__restrict__ y, float *__restrict__ out_range, int Ci, int Co, int H, int W, int relu, int tiles_w,
                        int tiles_h, unsigned nslots) {
-    __shared__ __attribute__((aligned(16))) _Float16 smem[C2_SLAB_HALFS + 2 * C2_X_PART];
-    __shared__ unsigned red[4];
-    _Float16 *const Ws = smem;                  // [part][tap][kg][co][8]
-    _Float16 *const Xs = smem + C2_SLAB_HALFS;  // [part][kg][pixel][8]
+    conv2d_k3_tile<false, &g_conv2d_saturated>(x, x_range, C2CatArgs{}, wslabs, whdr, bias, residual, y, out_range, Ci, Co, H, W, relu, tiles_w,
+                                               tiles_h, nslots);
+}
 
-    float x_scale, x_unscale;
-    range_scale_block(x_range, x_scale, x_unscale);   // (folds the producer's partial maxima; barriers inside)
-
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int j = lane & 31, kg = lane >> 5;
-    int bid = blockIdx.x;
-    const int tw = bid % tiles_w; bid /= tiles_w;
-    const int th = bid % tiles_h;
-    const int n = bid / tiles_h;
-    const int cot = blockIdx.y;
-    const int h0 = th * C2_TH, w0 = tw * C2_TW;
-    const int nchunks = Ci / C2_KC;
-    const size_t HW = (size_t)H * W;
-    const unsigned HWu = (unsigned)HW;   // (a chunk's 16 channels hold fewer than 2^31 elements: 32-bit element offsets)
-    const float *const xn = x + (size_t)n * Ci * HW;
-
-    // X staging: an item is (channel pair p, halo pixel r): two 4-byte loads (the zero padding and the ragged edge are the mask), scale,
-    // split, one b32 write of hi and one of lo.  The four pairs of a 16-byte fragment go to neighbouring lanes: conflict-free writes.
-    constexpr int NX = 8 * C2_XV;                        // items per chunk
-    constexpr int XI = (NX + C2_NTHR - 1) / C2_NTHR;     // 11 per thread
-    constexpr int WI = C2_SLAB_HALFS * 2 / 16 / C2_NTHR; // 9 16-byte pieces of the weight slab per thread
-    static_assert(C2_SLAB_HALFS * 2 % (16 * C2_NTHR) == 0, "weight slab / thread count");
-    float xa[XI], xb[XI];
-    typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-    u32x4 wq[WI];
-    unsigned sat = 0, okm = 0;
-#define C2_LOAD_CHUNK(c_)                                                                              \
-    {                                                                                                  \
-        const float *const xc_ = xn + (size_t)(c_) * C2_KC * HW;                                       \
-        int tid_ = tid;                                                                                \
-        asm volatile("" : "+v"(tid_)); /* opaque: keeps the per-item offsets out of registers across the K loop */ \
-        _Pragma("unroll") for (int i = 0; i < XI; ++i) {                                               \
-            const int e_ = i * C2_NTHR + tid_, ec_ = min(e_, NX - 1);                                  \
-            const int rest_ = ec_ >> 2;                                                                \
-            const int p_ = (rest_ / C2_XV) * 4 + (ec_ & 3), r_ = rest_ % C2_XV;                        \
-            const int gh_ = h0 - 1 + r_ / C2_HW, gw_ = w0 - 1 + r_ % C2_HW;                            \
-            const bool ok_ = e_ < NX && (unsigned)gh_ < (unsigned)H && (unsigned)gw_ < (unsigned)W;    \
-            /* unconditional loads from a clamped (always valid) address, a select later: no branch per load */ \
-            const unsigned off_ = (unsigned)(2 * p_) * HWu + (unsigned)min(max(gh_, 0), H - 1) * W + min(max(gw_, 0), W - 1); \
-            xa[i] = xc_[off_];                                                                         \
-            xb[i] = xc_[off_ + HWu];                                                                   \
-            okm = ok_ ? okm | (1u << i) : okm & ~(1u << i);   /* the select waits until the values are written to LDS */ \
-        }                                                                                              \
-        const u32x4 *const ws_ = reinterpret_cast<const u32x4 *>(wslabs + ((size_t)cot * nchunks + (c_)) * C2_SLAB_HALFS); \
-        _Pragma("unroll") for (int i = 0; i < WI; ++i) wq[i] = ws_[i * C2_NTHR + tid_];                \
-    }
-#define C2_WRITE_CHUNK()                                                                               \
-    {                                                                                                  \
-        int tid_ = tid;                                                                                \
-        asm volatile("" : "+v"(tid_));                                                                 \
-        _Pragma("unroll") for (int i = 0; i < XI; ++i) {                                               \
-            const int e_ = i * C2_NTHR + tid_;                                                         \
-            if (e_ < NX) {                                                                             \
-                const int dst_ = (e_ >> 2) * 8 + (e_ & 3) * 2;   /* e_ >> 2 = kg * C2_XV + pixel */    \
-                const bool ok_ = (okm >> i) & 1u;                                                      \
-                const float v0_ = ok_ ? xa[i] * x_scale : 0.0f, v1_ = ok_ ? xb[i] * x_scale : 0.0f;    \
-                sat += !(fabsf(v0_) <= F16_CLAMP) + !(fabsf(v1_) <= F16_CLAMP);   /* NaN counts */     \
-                _Float16 hA_, lA_, hB_, lB_;                                                           \
-                split_f16(v0_, hA_, lA_);                                                              \
-                split_f16(v1_, hB_, lB_);                                                              \
-                const half2v hv_ = {hA_, hB_}, lv_ = {lA_, lB_};                                       \
-                *reinterpret_cast<half2v *>(Xs + dst_) = hv_;                                          \
-                *reinterpret_cast<half2v *>(Xs + C2_X_PART + dst_) = lv_;                              \
-            }                                                                                          \
-        }                                                                                              \
-        _Pragma("unroll") for (int i = 0; i < WI; ++i) reinterpret_cast<u32x4 *>(Ws)[i * C2_NTHR + tid_] = wq[i]; \
-    }
-
-    // ds_read_b128 is serviced in 16-lane groups {0-3,12-15,20-27} / {4-11,16-19,28-31} per half-wave: slot jv gives each group one
-    // whole 16-pixel row (256 contiguous bytes = every bank once).  Slots only name accumulator columns, any bijection works.
-    const int jg = ((j >> 2) & 1) ^ ((j >> 3) & 1) ^ ((j >> 4) & 1);
-    const int jpos = j < 4 ? j : j < 12 ? j - 4 : j < 20 ? j - 8 : j < 28 ? j - 12 : j - 16;
-    const int jv = jg * 16 + jpos;
-    const int prow = wave * 4 + (jv >> 4), pcol = jv & 15;       // this lane's pixel in column tile t: (prow + 2t, pcol)
-    const int a_base = (kg * C2_COT + j) * 8;                    // + ((part*9 + tap)*2*64 + m*32)*8
-    const int b_base = (kg * C2_XV + prow * C2_HW + pcol) * 8;   // + (t*2*18 + tap offset)*8
-
-    f32x16 acc[2][2];
-#pragma unroll
-    for (int m = 0; m < 2; ++m)
-#pragma unroll
-        for (int t = 0; t < 2; ++t)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[m][t][r] = 0.0f;
-
-    C2_LOAD_CHUNK(0)
-    C2_WRITE_CHUNK()
-    __syncthreads();
-    for (int c = 0; c < nchunks; ++c) {
-        const bool more = c + 1 < nchunks;
-        if (more) C2_LOAD_CHUNK(c + 1)   // in flight during this chunk's MFMAs
-#pragma unroll
-        for (int tap = 0; tap < 9; ++tap) {
-            half8 ah[2], al[2], bh[2], bl[2];
-            const int toff = ((tap / 3) * C2_HW + tap % 3) * 8;
-#pragma unroll
-            for (int m = 0; m < 2; ++m) {
-                ah[m] = *reinterpret_cast<const half8 *>(Ws + a_base + (tap * 2 * C2_COT + m * 32) * 8);
-                al[m] = *reinterpret_cast<const half8 *>(Ws + C2_SLAB_HALFS / 2 + a_base + (tap * 2 * C2_COT + m * 32) * 8);
-            }
-#pragma unroll
-            for (int t = 0; t < 2; ++t) {
-                bh[t] = *reinterpret_cast<const half8 *>(Xs + b_base + t * 2 * C2_HW * 8 + toff);
-                bl[t] = *reinterpret_cast<const half8 *>(Xs + C2_X_PART + b_base + t * 2 * C2_HW * 8 + toff);
-            }
-#pragma unroll
-            for (int m = 0; m < 2; ++m)
-#pragma unroll
-                for (int t = 0; t < 2; ++t) acc[m][t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[m], bh[t], acc[m][t], 0, 0, 0);
-#pragma unroll
-            for (int m = 0; m < 2; ++m)
-#pragma unroll
-                for (int t = 0; t < 2; ++t) acc[m][t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[m], bh[t], acc[m][t], 0, 0, 0);
-#pragma unroll
-            for (int m = 0; m < 2; ++m)
-#pragma unroll
-                for (int t = 0; t < 2; ++t) acc[m][t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[m], bl[t], acc[m][t], 0, 0, 0);
-        }
-        if (more) {
-            __syncthreads();   // every wave is past its last fragment read of this chunk
-            C2_WRITE_CHUNK()
-            __syncthreads();
-        }
-    }
-
-#undef C2_LOAD_CHUNK
-#undef C2_WRITE_CHUNK
-
-    // epilogue: unscale (a power of two), bias, residual, ReLU in fp32; stores masked at the ragged edge and past Co
-    const float unscale = whdr[0] * x_unscale;
-    unsigned ymax = 0;
-#pragma unroll
-    for (int m = 0; m < 2; ++m) {
-        const int co0 = cot * C2_COT + m * 32;
-        if (co0 < Co) {   // (Co % 32 == 0: a row tile is whole or absent; workgroup-uniform)
-#pragma unroll
-            for (int t = 0; t < 2; ++t) {
-                const int gh = h0 + prow + 2 * t, gw = w0 + pcol;
-                if (gh < H && gw < W) {
-                    const size_t o = ((size_t)n * Co + co0 + 4 * kg) * HW + (size_t)gh * W + gw;
-#pragma unroll
-                    for (int reg = 0; reg < 16; ++reg) {
-                        const int row = (reg & 3) + 8 * (reg >> 2);
-                        const size_t oi = o + (size_t)row * HW;
-                        float v = acc[m][t][reg] * unscale + bias[co0 + 4 * kg + row];
-                        if (residual) v += residual[oi];
-                        if (relu) v = v < 0.0f ? 0.0f : v;   // (keeps NaN, like torch's relu)
-                        y[oi] = v;
-                        ymax = max(ymax, range_bits(v));
-                    }
-                }
-            }
-        }
-    }
-    if (out_range) {   // workgroup-uniform
-        ymax = wave_umax(ymax);
-        if (lane == 0) red[wave] = ymax;
-        __syncthreads();
-        if (tid == 0) {
-            const unsigned mx = max(max(red[0], red[1]), max(red[2], red[3]));
-            const unsigned slot = (blockIdx.x + gridDim.x * blockIdx.y) % nslots;
-            if (mx) atomicMax(reinterpret_cast<unsigned *>(out_range) + 4 + slot, mx);
-        }
-    }
-    if (__builtin_amdgcn_ballot_w64(sat != 0) != 0) {  // never taken in normal operation
-        unsigned tot = sat;
-#pragma unroll
-        for (int sft = 32; sft >= 1; sft >>= 1) tot += __shfl_xor(tot, sft, 64);
-        if (lane == 0) atomicAdd(&g_conv2d_saturated, (unsigned long long)tot);
-    }
+void conv2d_range_launch(const float *x, size_t n, float *range, hipStream_t s) {
+    const unsigned blocks = (unsigned)std::min<size_t>(2048, (n + 8191) / 8192);
+    hipLaunchKernelGGL(conv2d_range_kernel, dim3(blocks ? blocks : 1), dim3(256), 0, s, x, n, range);
+}
+void conv2d_out_range_init_launch(float *range, unsigned nslots, hipStream_t s) {
+    hipLaunchKernelGGL(conv2d_out_range_init_kernel, dim3(cdiv(nslots + 4, 256)), dim3(256), 0, s, range, nslots);
 }
 
 int conv2d_f16x3_saturation(unsigned long long *count, int reset) { return f16x3_counter_read(&g_conv2d_saturated, count, reset); }
@@ -350,9 +159,7 @@ extern "C" int mphip_conv2d_fwd(const float *x, const float *x_range, const void
             return MPHIP_EWORKSPACE;
         }
         MPHIP_REQUIRE(((uintptr_t)workspace & 3) == 0, "conv2d_fwd: the workspace must be 4-byte aligned");
-        const size_t n = (size_t)N * Ci * H * W;
-        const unsigned blocks = (unsigned)std::min<size_t>(2048, (n + 8191) / 8192);
-        hipLaunchKernelGGL(conv2d_range_kernel, dim3(blocks ? blocks : 1), dim3(256), 0, s, x, n, (float *)workspace);
+        conv2d_range_launch(x, (size_t)N * Ci * H * W, (float *)workspace, s);
         x_range = (const float *)workspace;
     }
     const int tiles_w = cdiv(W, C2_TW), tiles_h = cdiv(H, C2_TH);
@@ -360,7 +167,7 @@ extern "C" int mphip_conv2d_fwd(const float *x, const float *x_range, const void
     MPHIP_REQUIRE(tiles < (1ll << 31), "conv2d_fwd: %lld tiles do not fit a launch", tiles);
     const dim3 grid((unsigned)tiles, (unsigned)c2_cots(Co));
     const unsigned nslots = (unsigned)std::min<long long>(tiles * c2_cots(Co), (long long)RANGE_MAX_PARTS);
-    if (out_range) hipLaunchKernelGGL(conv2d_out_range_init_kernel, dim3(cdiv(nslots + 4, 256)), dim3(256), 0, s, out_range, nslots);
+    if (out_range) conv2d_out_range_init_launch(out_range, nslots, s);
     hipLaunchKernelGGL(conv2d_k3_f16x3_kernel, grid, dim3(C2_NTHR), 0, s, x, x_range, (const _Float16 *)((const char *)w_packed + 16),
                        (const float *)w_packed, bias, residual, y, out_range, Ci, Co, H, W, relu, tiles_w, tiles_h, nslots);
     return check_launch("conv2d_fwd");

@@ -165,6 +165,8 @@ void f16x3_wino_bt_launch(dim3 grid, hipStream_t s, hipEvent_t t0, hipEvent_t t1
 int f16x3_wino_bt_saturation(unsigned long long *count, int reset);
 // conv2d_f16x3.hip: the 2-D 3x3 conv (mphip_conv2d_fwd) keeps a counter of its own as well
 int conv2d_f16x3_saturation(unsigned long long *count, int reset);
+// conv2d_gn_f16x3.hip: its two-source form (mphip_conv2d_cat_fwd), likewise
+int conv2d_gn_f16x3_saturation(unsigned long long *count, int reset);
 
 // api.hip: the calling thread's conv arithmetic policy (mphip_conv3d_set_half_products): true inside torch.autocast(float16) regions
 bool conv_half_products();

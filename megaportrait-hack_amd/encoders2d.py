@@ -131,6 +131,15 @@ class Eapp(nn.Module):
         self.custom_resnet50 = CustomResNet50()
         self.fc = nn.Linear(2048, COMPRESS_DIM)
 
+    def native_trunk(self, enable: bool = True) -> "Eapp":
+        """Opt-in, inference only: run `resblock_128 / _256 / _512` as model.ResBlockCustomFused — two launches per block on the matrix
+        cores with fp32-class accuracy (csrc/conv2d_gn_f16x3.hip): GroupNorm + ReLU folded into the convs' input staging, the skip conv
+        folded into the last conv — over the blocks' own children: same Parameter objects, same state-dict keys.  `enable=False` puts the
+        original blocks back.  Under autograd or on a half model the fused blocks evaluate the original PyTorch expression.  The 7x7
+        stem, the average pools and conv_1 stay on PyTorch."""
+        M.native_eapp_trunk(self, enable)
+        return self
+
     def trunk2d(self, x):
         """image [B,3,H,W] -> conv_1 output [B,1536,H/8,W/8] (model.py:248-268)."""
         out = self.avgpool(self.resblock_128(self.conv(x)))

@@ -64,6 +64,13 @@ class Gbase(M._HotSliceRunner, nn.Module):
         M.native_g2d_body(self.G2d, enable)
         return self
 
+    def native_trunk(self, enable: bool = True) -> "Gbase":
+        """Opt-in (off by default), inference only: the three ResBlock_Custom of the appearance encoder's 2-D trunk as
+        model.ResBlockCustomFused — GroupNorm, ReLU and the skip conv folded into two matrix-core conv launches per block
+        (model.native_eapp_trunk); `enable=False` restores the original blocks.  Same parameters and state-dict keys."""
+        M.native_eapp_trunk(self.appearanceEncoder, enable)
+        return self
+
     def _nhwc(self, x):
         return x.contiguous(memory_format=torch.channels_last) if getattr(self, "_cl2d", False) and x.dim() == 4 else x
 

@@ -866,6 +866,126 @@ def native_g2d_body(g2d: nn.Module, enable: bool = True) -> bool:
     return changed
 
 
+def standardise_weight(w: torch.Tensor) -> torch.Tensor:
+    """Conv2d_WS.forward's weight (model.py:61-67): per output filter, minus its mean over dims 1-3, over (unbiased std + 1e-5)."""
+    w = w - w.mean(dim=(1, 2, 3), keepdim=True)
+    return w / (w.flatten(1).std(dim=1).view(-1, 1, 1, 1) + 1e-5)
+
+
+def fold_resblock_custom(conv_res: nn.Module, conv_ws: nn.Module, conv: nn.Module):
+    """ResBlock_Custom as two convs -> ((w_ws', b_ws), (w_cat, b_cat)) in the parameters' own dtype: conv_ws with its weight
+    standardised, and conv(a) + conv_res(x) as ONE conv over the channel concatenation [a ; x]: w_cat = [W_conv | W_res] along dim 1,
+    b_cat = b_conv + b_res."""
+    w_ws = standardise_weight(conv_ws.weight.detach()).contiguous()
+    w_cat = torch.cat([conv.weight.detach(), conv_res.weight.detach()], dim=1).contiguous()
+    return (w_ws, conv_ws.bias.detach().contiguous()), (w_cat, (conv.bias.detach() + conv_res.bias.detach()).contiguous())
+
+
+class ResBlockCustomFused(nn.Module):
+    """Eapp's 2-D ResBlock_Custom (model.py:88-130)
+        out = conv(relu(GN32(conv_ws(relu(GN32(x)))))) + conv_res(x)          GN32 = F.group_norm(., 32), no parameters
+    with an opt-in path on the matrix cores: two launches of csrc/conv2d_gn_f16x3.hip (f16x3 arithmetic: fp32-class accuracy), each
+    normalising its input while it stages it, the second one reading x as a second source so that the skip conv and the add cost no
+    launch and no pass over memory (fold_resblock_custom).  The children are the original block's own `conv_res, conv_ws, conv` — the
+    same Parameter objects, the same state-dict keys — built over an existing block by `from_block`.
+
+    The native path runs without autograd (ag.needs_grad false) on an fp32 module, a CUDA input and a supported shape, in train and in
+    eval mode alike (the block has no mode-dependent layer); otherwise forward evaluates the original block's expression in PyTorch.
+    There are NO backward kernels and NO half-model path: training, fine-tuning and .half() / .bfloat16() instances take the PyTorch
+    expression.  fp16 / bf16 inputs are widened (model._f32) and the result is fp32; channels_last inputs are copied to NCHW once."""
+
+    def __init__(self, dimension: int, in_channels: int, out_channels: int):
+        super().__init__()
+        from .encoders2d import Conv2d_WS
+
+        if dimension != 2:
+            raise NotImplementedError("ResBlockCustomFused: the 2-D block only")
+        self.dimension, self.in_channels, self.out_channels = dimension, in_channels, out_channels
+        self.conv_res = nn.Conv2d(in_channels, out_channels, 3, padding=1)
+        self.conv_ws = Conv2d_WS(in_channels, out_channels, 3, padding=1)
+        self.conv = nn.Conv2d(out_channels, out_channels, 3, padding=1)
+
+    @staticmethod
+    def matches(block) -> bool:
+        """Duck-typed: is `block` a 2-D ResBlock_Custom (this package's or the reference's) the fused path can stand in for?"""
+        if isinstance(block, ResBlockCustomFused) or getattr(block, "dimension", None) != 2:
+            return False
+        res, ws, conv = (getattr(block, n, None) for n in ("conv_res", "conv_ws", "conv"))
+        if not (_is_conv2d(res, 3) and _is_conv2d(ws, 3) and _is_conv2d(conv, 3)) or type(ws).__name__ != "Conv2d_WS":
+            return False
+        ci, co = res.in_channels, res.out_channels
+        return (ws.in_channels, ws.out_channels, conv.in_channels, conv.out_channels) == (ci, co, co, co)
+
+    @classmethod
+    def from_block(cls, block: nn.Module) -> "ResBlockCustomFused":
+        if not cls.matches(block):
+            raise TypeError(f"ResBlockCustomFused.from_block: expected a 2-D ResBlock_Custom (conv_res, conv_ws (Conv2d_WS), conv: 3x3 "
+                            f"stride-1 padding-1 convs with bias), got {block}")
+        new = cls.__new__(cls)
+        nn.Module.__init__(new)
+        new.dimension, new.in_channels, new.out_channels = 2, block.conv_res.in_channels, block.conv_res.out_channels
+        for name in ("conv_res", "conv_ws", "conv"):
+            setattr(new, name, getattr(block, name))
+        new.training = block.training
+        return new
+
+    def _native_ok(self, x) -> bool:
+        if ag.needs_grad(self, x) or any(p.dtype != torch.float32 for p in self.parameters()):
+            return False
+        if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dim() == 4 and x.shape[1] == self.in_channels and x.numel() > 0
+                and x.is_floating_point()):
+            return False
+        n, ci, h, w = x.shape
+        co = self.out_channels
+        return ops.conv2d_cat_supported(n, ci, 0, co, h, w) and ops.conv2d_cat_supported(n, co, ci, co, h, w)
+
+    def _folded(self):
+        """(conv_ws', [conv | conv_res]) packed; cached until a parameter changes (their versions are the key)."""
+        ts = [t for m in (self.conv_res, self.conv_ws, self.conv) for t in (m.weight, m.bias)]
+        key = tuple((t.data_ptr(), t._version) for t in ts) + (str(ts[0].device), ops.weight_epoch())
+        hit = self.__dict__.get("_mphip_fold")
+        if hit is None or hit[0] != key or ops.repacking():
+            with torch.no_grad():
+                ws, cat = fold_resblock_custom(self.conv_res, self.conv_ws, self.conv)
+                hit = (key, (ops.PackedConv2d(*ws), ops.PackedConv2d(*cat)))
+            self.__dict__["_mphip_fold"] = hit
+        return hit[1]
+
+    def forward(self, x):
+        if not self._native_ok(x):
+            skip = self.conv_res(x)
+            y = self.conv_ws(F.relu(F.group_norm(x, 32)))
+            y = self.conv(F.relu(F.group_norm(y, 32)))
+            return y + skip
+        xc = _f32(x).contiguous()   # (the kernels read NCHW: a channels_last map is copied once)
+        p_ws, p_cat = self._folded()
+        tab, rng = ops.gn_relu_table2d(xc)
+        t = ops.conv2d_cat(xc, p_ws, affine1=tab, relu1=True, x1_range=rng)
+        tab, rng = ops.gn_relu_table2d(t)
+        return ops.conv2d_cat(t, p_cat, x2=xc, affine1=tab, relu1=True, x1_range=rng, want_range=True)
+
+
+_EAPP_TRUNK_SLOTS = ("resblock_128", "resblock_256", "resblock_512")
+
+
+def native_eapp_trunk(eapp: nn.Module, enable: bool = True) -> bool:
+    """Swaps every matching ResBlock_Custom among `eapp.resblock_128 / _256 / _512` (this package's Eapp or the reference's,
+    model.py:210-212) for a ResBlockCustomFused over the same children, or puts the very objects it replaced back.  Returns whether
+    anything changed.  Off by default everywhere."""
+    changed = False
+    for name in _EAPP_TRUNK_SLOTS:
+        cur = getattr(eapp, name, None)
+        if enable and ResBlockCustomFused.matches(cur):
+            new = ResBlockCustomFused.from_block(cur)
+            new.__dict__["_replaced"] = cur   # (not a registered child: the module tree and the state-dict keys stay as they were)
+            setattr(eapp, name, new)
+            changed = True
+        elif not enable and isinstance(cur, ResBlockCustomFused) and "_replaced" in cur.__dict__:
+            setattr(eapp, name, cur.__dict__.pop("_replaced"))
+            changed = True
+    return changed
+
+
 class _HotSliceRunner(_ModelDtype):
     """model.py:1151-1171 over `self.warp_generator_s2c`, `self.warp_generator_c2d`, `self.G3d` — shared by
     GbaseHotSlice (the slice alone) and gbase.Gbase (the orchestrator)."""

@@ -1259,6 +1259,81 @@ def conv2d(x: torch.Tensor, pack: PackedConv2d, residual: Optional[torch.Tensor]
     return tag_range(y, out_range)
 
 
+_GN_UNIT = {}   # (device, C) -> (ones, zeros): gamma and beta of a GroupNorm without parameters
+
+
+def gn_relu_table2d(x: torch.Tensor, groups: int = 32, eps: float = 1e-5):
+    """F.group_norm(x, groups) of an [N,C,H,W] map (no affine parameters) as what ops.conv2d_cat folds into its staging:
+    -> (table [N,C,2] = (scale, shift) with group_norm(x) = x * scale + shift, range): mphip_groupnorm_stats, then
+    mphip_groupnorm_affine_table with gamma = 1, beta = 0.  `range` is the data-independent bound of the normalised map (include/mphip.h);
+    a ReLU on top only lowers it."""
+    x = _req(x, "x")
+    if x.dim() != 4:
+        raise RuntimeError(f"gn_relu_table2d: expected an [N,C,H,W] map, got {tuple(x.shape)}")
+    n, c, h, w = x.shape
+    stats = groupnorm_stats(x, groups, eps)
+    key = (str(x.device), c)
+    unit = _GN_UNIT.get(key)
+    if unit is None:
+        unit = _GN_UNIT[key] = (torch.ones(c, dtype=torch.float32, device=x.device), torch.zeros(c, dtype=torch.float32, device=x.device))
+    table = torch.empty((n, c, 2), dtype=torch.float32, device=x.device)
+    rng = new_range(x.device)
+    _lib.check(_lib.load().mphip_groupnorm_affine_table(_ptr(stats), _ptr(unit[0]), _ptr(unit[1]), None, None, _ptr(table), _ptr(rng), n, c,
+                                                        h * w, groups, _stream()), "mphip_groupnorm_affine_table")
+    return table, rng
+
+
+def conv2d_cat_supported(n: int, c1: int, c2: int, co: int, h: int, w: int) -> bool:
+    return bool(_lib.load().mphip_conv2d_cat_supported(int(n), int(c1), int(c2), int(co), int(h), int(w)))
+
+
+def conv2d_cat(x1: torch.Tensor, pack: PackedConv2d, x2: Optional[torch.Tensor] = None, affine1: Optional[torch.Tensor] = None,
+               affine2: Optional[torch.Tensor] = None, relu1: bool = False, relu2: bool = False, x1_range: Optional[torch.Tensor] = None,
+               x2_range: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None, relu: bool = False,
+               want_range: bool = False) -> torch.Tensor:
+    """y = act(conv3x3([s1 ; s2]) + bias (+ residual)), padding 1 (mphip_conv2d_cat_fwd): the conv of the channel concatenation of two
+    NCHW fp32 maps, which is never built; `pack` holds an OIHW weight with Ci = C1 + C2.  s_i = x_i, or with a table affine_i [N,C_i,2]
+    (gn_relu_table2d) x_i * scale + shift, then ReLU if relu_i, applied while the conv stages its input (padding stays zero).  A source
+    with a table needs its descriptor x_i_range (the table's); one without takes x_i_range, else the descriptor tagged on x_i, else the
+    library scans it.  Without x2 and tables: the bits of ops.conv2d."""
+    x1 = _req(x1, "x1")
+    if x1.dim() != 4:
+        raise RuntimeError(f"conv2d_cat: expected an [N,C,H,W] map, got {tuple(x1.shape)}")
+    n, c1, h, w = x1.shape
+    c2 = 0
+    if x2 is not None:
+        x2 = _req(x2, "x2")
+        if x2.dim() != 4 or (x2.shape[0], x2.shape[2], x2.shape[3]) != (n, h, w):
+            raise RuntimeError(f"conv2d_cat: x2 {tuple(x2.shape)} does not match x1 {tuple(x1.shape)}")
+        c2 = int(x2.shape[1])
+    if c1 + c2 != pack.ci:
+        raise RuntimeError(f"conv2d_cat: C1 + C2 = {c1} + {c2} does not match Ci={pack.ci}")
+    if affine1 is not None:
+        affine1 = _req(affine1, "affine1")
+    if affine2 is not None:
+        affine2 = _req(affine2, "affine2")
+    for name, tab, c in (("affine1", affine1, c1), ("affine2", affine2, c2)):
+        if tab is not None and tuple(tab.shape) != (n, c, 2):
+            raise RuntimeError(f"conv2d_cat: {name} {tuple(tab.shape)} is not the [{n},{c},2] table of its source")
+    if residual is not None:
+        residual = _req(residual, "residual")
+        if tuple(residual.shape) != (n, pack.co, h, w):
+            raise RuntimeError(f"conv2d_cat: residual {tuple(residual.shape)} does not match the output {(n, pack.co, h, w)}")
+    lib = _lib.load()
+    # (a table's source keeps the caller's descriptor or none: the one tagged on x_i describes the raw values, and the entry refuses none)
+    r1 = x1_range if (x1_range is not None or affine1 is not None) else current_range(x1)
+    r2 = x2_range if (x2_range is not None or affine2 is not None or x2 is None) else current_range(x2)
+    scan = r1 is None or (x2 is not None and r2 is None)
+    ws_bytes = lib.mphip_conv2d_cat_workspace_bytes(n, c1, c2, pack.co, h, w) if scan else 0
+    ws = torch.empty((ws_bytes + 3) // 4, dtype=torch.float32, device=x1.device) if ws_bytes else None
+    y = torch.empty((n, pack.co, h, w), dtype=torch.float32, device=x1.device)
+    out_range = new_range(x1.device) if want_range else None
+    _lib.check(lib.mphip_conv2d_cat_fwd(_ptr(x1), _ptr(affine1), int(bool(relu1)), _ptr(r1), c1, _ptr(x2), _ptr(affine2), int(bool(relu2)),
+                                        _ptr(r2), c2, _ptr(pack.packed()), _ptr(pack.bias), _ptr(residual), _ptr(y), _ptr(out_range), n,
+                                        pack.co, h, w, int(bool(relu)), _ptr(ws), ws_bytes, _stream()), "mphip_conv2d_cat_fwd")
+    return tag_range(y, out_range)
+
+
 def avgpool2_bwd(dout: torch.Tensor) -> torch.Tensor:
     dout = _req(dout, "dout")
     n, c, d, h, w = dout.shape

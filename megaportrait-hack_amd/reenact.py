@@ -46,6 +46,9 @@ def parse(argv=None):
     ap.add_argument("--native-g2d-body", action="store_true",
                     help="run G2d's ResBlock2D body with BatchNorm folded and its 3x3 convs on the matrix cores "
                          "(gbase.Gbase.native_body; inference only, fp32 models; off by default)")
+    ap.add_argument("--native-eapp-trunk", action="store_true",
+                    help="run the appearance encoder's three 2-D ResBlock_Custom blocks on the matrix cores, GroupNorm, ReLU and the skip "
+                         "conv folded into two conv launches per block (gbase.Gbase.native_trunk; inference only, fp32 models; off by default)")
     ap.add_argument("--fp16", action="store_true",
                     help="run the PyTorch-ROCm 2D modules under torch.autocast(float16) (the reference's policy, train.py:188); "
                          "the HIP hot path stays fp32-class")
@@ -168,6 +171,8 @@ def run(job: dict, args, rank: int, world: int) -> List[str]:
         g.native_final_conv()
     if args.native_g2d_body:
         g.native_body()
+    if args.native_eapp_trunk:
+        g.native_trunk()
     xs = _load_tensor(job["source_tensor"]) if job["source_tensor"] else _load_image(job["source"])
     n = _load_tensor(job["drivers_tensor"]).shape[0] if job["drivers_tensor"] else len(job["drivers"])
     b, e, outputs = shard_plan(job, n, rank, world)
