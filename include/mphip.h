@@ -13,6 +13,8 @@
  *    No torch types.  `stream` is a hipStream_t passed as void* (NULL = default stream).
  *  - Tensors are float32, contiguous, NCDHW (N,C,D,H,W), exactly the layout the reference's
  *    modules exchange (model.py:271 defines the volume layout: channel c*16+d -> (c,d)).
+ *    The *_typed entries (model dtypes, ABI 15; the 2-D convs since ABI 21) read and write
+ *    boundary tensors in fp16 / bf16 as well: void pointers with an MPHIP_DTYPE_* code each.
  *  - Every function returns 0 on success or a negative MPHIP_E* code, never throws, never
  *    allocates device memory, never synchronises the stream (the one diagnostic that does,
  *    mphip_f16x3_saturation_count, says so).  Work is stream-ordered;
@@ -39,7 +41,7 @@ extern "C" {
 
 /* ABI version of this header.  Bumped whenever an exported signature or a packed layout changes; mphip_version() returns the
  * value the LIBRARY was built with — compare the two after dlopen (the ctypes binding does, and refuses a mismatch). */
-#define MPHIP_ABI_VERSION 20
+#define MPHIP_ABI_VERSION 21
 int mphip_version(void);
 /* hipGraph hygiene (ABI 13).  On ROCm 7.x a MEMSET node of a captured hipGraph is not reliably ordered with its neighbouring kernel nodes
  * (observed twice: stale f16x3 pack headers, r03; a training step's loss that kept its previous value, r04-r05 — ATen's multi-block
@@ -586,6 +588,32 @@ int mphip_conv2d_cat_fwd(const float *x1, const float *affine1, int relu1, const
                          const float *affine2, int relu2, const float *x2_range, int C2, const void *w_packed, const float *bias,
                          const float *residual, float *y, float *out_range, int N, int Co, int H, int W, int relu, void *workspace,
                          size_t workspace_bytes, void *stream);
+/* Typed maps and the product count (ABI 21; csrc/conv2d_lp.hip): the half-precision form of both convs above, for the fused 2-D blocks of
+ * a .half() / .bfloat16() model and of an fp32 model inside torch.autocast(float16).  The argument lists are the fp32 entries' plus
+ *   x_dtype, residual_dtype, y_dtype: MPHIP_DTYPE_* of x, residual and y.  A typed x is widened on load (exact); a typed y is the fp32
+ *          epilogue value rounded once at the store (v_cvt_f16_f32; round-to-nearest-even for bf16), and out_range then describes the
+ *          ROUNDED values, so the next conv takes the same scale whether it reads the descriptor or scans y.  residual_dtype is F32 or
+ *          y_dtype.  At most one half dtype per call.  The two-source form reads fp32 sources (x_dtype must be F32: widen a typed block
+ *          input once with mphip_cast_to_f32_range, which also delivers its descriptor).
+ *   products: 3 = the f16x3 arithmetic above; 1 = ONE f16 product per multiply, the arithmetic torch.autocast(float16) gives a conv:
+ *              y = narrow_Y( act( unscale * sum round_f16(w * s_w) * round_f16(x * s_x)  + bias + widen(residual) ) )
+ *          with the same power-of-two scales s_w (pack header) and s_x (range descriptor), fp32 accumulation, one rounding at the store;
+ *          a third of the MFMAs, half the LDS.  round_f16(w * s_w) is the hi plane of the ordinary pack: w_packed is the same buffer.
+ *          0 = follow the calling thread's mphip_conv3d_set_half_products flag.
+ * The fp32 entries above are unchanged: fp32 maps and three products whatever the thread flag says.  With every dtype F32 and three
+ * products the typed entries ARE the fp32 entries.  Not every combination is built: mphip_conv2d_typed_supported(two_source, x_dtype,
+ * residual_dtype, y_dtype, products) returns 1 for those that are — one product: plain form x any / y F32 and x F32 / y any, two-source
+ * form y any; three products: all F32 — and the launch refuses the others (MPHIP_EINVAL), like an unknown dtype code, two different half
+ * dtypes, a typed source of the two-source form and a product count outside {0, 1, 3}, before the first HIP call.
+ * y must not overlap x / x1, x2 or residual.  Workspaces: mphip_conv2d_workspace_bytes / mphip_conv2d_cat_workspace_bytes.            */
+int mphip_conv2d_typed_supported(int two_source, int x_dtype, int residual_dtype, int y_dtype, int products);
+int mphip_conv2d_fwd_typed(const void *x, int x_dtype, const float *x_range, const void *w_packed, const float *bias, const void *residual,
+                           int residual_dtype, void *y, int y_dtype, float *out_range, int N, int Ci, int Co, int H, int W, int relu,
+                           int products, void *workspace, size_t workspace_bytes, void *stream);
+int mphip_conv2d_cat_fwd_typed(const void *x1, int x_dtype, const float *affine1, int relu1, const float *x1_range, int C1, const void *x2,
+                               const float *affine2, int relu2, const float *x2_range, int C2, const void *w_packed, const float *bias,
+                               const void *residual, int residual_dtype, void *y, int y_dtype, float *out_range, int N, int Co, int H,
+                               int W, int relu, int products, void *workspace, size_t workspace_bytes, void *stream);
 
 /* The reference's reduced-precision policy for the convs (train.py:145,188: the generator step runs under torch.cuda.amp.autocast(), its
  * conv3d calls take f16 operands with fp32 accumulation).  mphip_conv3d_set_half_products(1) makes the CALLING THREAD's subsequent precision-1

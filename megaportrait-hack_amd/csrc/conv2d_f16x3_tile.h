@@ -12,6 +12,15 @@
 // relu(shift).  A chunk's 16 (scale, shift) pairs are fetched by 32 lanes with the chunk's global loads, parked in 128 bytes of LDS and
 // read back (two 16-byte reads per thread) when the chunk is written: nothing of them is live across the MFMAs.  Both sources share the
 // accumulator, so they share one power-of-two operand scale: the smaller of the two their range descriptors give.
+//
+// Two more axes, instantiated by conv2d_lp.hip (the two units above are XDT = YDT = fp32, NP = 3):
+//   XDT, YDT  the model dtype (MPHIP_DTYPE_*) of x and of y.  A typed x is loaded with 2-byte loads (any W, any row alignment), kept as it
+//             is across the MFMAs and widened when it is written to LDS: a power-of-two scale-up of a half value is exact, so a typed x
+//             stages the bits of its widened copy.  A typed y is the fp32 epilogue value rounded once at the store (narrow<YDT>); out_range
+//             then describes the ROUNDED values.  The residual is fp32 (`residual`) or in y's dtype (`residual_t`): at most one is set.
+//   NP        products per multiply.  3: Wlo*Xhi + Whi*Xhi + Whi*Xlo.  1: Whi*Xhi alone, the autocast(float16) policy: split_f16 becomes
+//             the one rounding round_f16(v * scale), no lo half is fetched, staged or read, and LDS holds the hi planes only (18432 +
+//             10368 bytes).  The hi plane is [part 0] of every slab of the ordinary pack: the same packed weights serve both.
 #pragma once
 #include <algorithm>
 
@@ -67,17 +76,22 @@ __device__ __forceinline__ float *c2_affine_lds() {
 }
 
 // SAT: the instantiating unit's saturation counter
-template <bool CAT, unsigned long long *SAT>
-__device__ __forceinline__ void conv2d_k3_tile(const float *__restrict__ x, const float *__restrict__ x_range, const C2CatArgs cat,
+template <bool CAT, unsigned long long *SAT, int XDT = MPHIP_DTYPE_F32, int YDT = MPHIP_DTYPE_F32, int NP = 3>
+__device__ __forceinline__ void conv2d_k3_tile(const dtype_t<XDT> *__restrict__ x, const float *__restrict__ x_range, const C2CatArgs cat,
                                                const _Float16 *__restrict__ wslabs, const float *__restrict__ whdr,
-                                               const float *__restrict__ bias, const float *__restrict__ residual, float *__restrict__ y,
-                                               float *__restrict__ out_range, int Ci, int Co, int H, int W, int relu, int tiles_w,
-                                               int tiles_h, unsigned nslots) {
-    __shared__ __attribute__((aligned(16))) _Float16 smem[C2_SLAB_HALFS + 2 * C2_X_PART];
+                                               const float *__restrict__ bias, const float *__restrict__ residual,
+                                               dtype_t<YDT> *__restrict__ y, float *__restrict__ out_range, int Ci, int Co, int H, int W,
+                                               int relu, int tiles_w, int tiles_h, unsigned nslots,
+                                               const dtype_t<YDT> *__restrict__ residual_t = nullptr) {
+    static_assert(NP == 3 || NP == 1, "three products (f16x3) or one (the autocast policy)");
+    static_assert(!CAT || XDT == MPHIP_DTYPE_F32, "the two-source form stages fp32 sources");
+    constexpr int NPART = NP == 3 ? 2 : 1;                   // operand halves in LDS: hi and lo, or hi alone
+    constexpr int W_HALFS = C2_SLAB_HALFS / 2 * NPART;       // of a slab, the planes this kernel fetches
+    __shared__ __attribute__((aligned(16))) _Float16 smem[W_HALFS + NPART * C2_X_PART];
     __shared__ unsigned red[4];
     float *const affs = c2_affine_lds<CAT>();
-    _Float16 *const Ws = smem;                  // [part][tap][kg][co][8]
-    _Float16 *const Xs = smem + C2_SLAB_HALFS;  // [part][kg][pixel][8]
+    _Float16 *const Ws = smem;             // [part][tap][kg][co][8]
+    _Float16 *const Xs = smem + W_HALFS;   // [part][kg][pixel][8]
 
     float x_scale, x_unscale;
     range_scale_block(x_range, x_scale, x_unscale);   // (folds the producer's partial maxima; barriers inside)
@@ -106,24 +120,27 @@ __device__ __forceinline__ void conv2d_k3_tile(const float *__restrict__ x, cons
     const int nchunks = nch1 + (CAT ? cat.C2 / C2_KC : 0);
     const size_t HW = (size_t)H * W;
     const unsigned HWu = (unsigned)HW;   // (a chunk's 16 channels hold fewer than 2^31 elements: 32-bit element offsets)
-    const float *const xn = x + (size_t)n * Ci * HW;
+    const dtype_t<XDT> *const xn = x + (size_t)n * Ci * HW;
     const float *const x2n = CAT && cat.C2 ? cat.x2 + (size_t)n * cat.C2 * HW : nullptr;
 
     // X staging: an item is (channel pair p, halo pixel r): two 4-byte loads (the zero padding and the ragged edge are the mask), scale,
     // split, one b32 write of hi and one of lo.  The four pairs of a 16-byte fragment go to neighbouring lanes: conflict-free writes.
     constexpr int NX = 8 * C2_XV;                        // items per chunk
     constexpr int XI = (NX + C2_NTHR - 1) / C2_NTHR;     // 11 per thread
-    constexpr int WI = C2_SLAB_HALFS * 2 / 16 / C2_NTHR; // 9 16-byte pieces of the weight slab per thread
+    constexpr int WPIECES = W_HALFS * 2 / 16;            // 16-byte pieces of the weight planes fetched
+    constexpr int WI = (WPIECES + C2_NTHR - 1) / C2_NTHR; // 9 per thread; hi plane alone: 4, and a fifth in the lower half of the threads
+    constexpr bool W_WHOLE = WPIECES % C2_NTHR == 0;
+    constexpr int W_LAST = WPIECES - (WI - 1) * C2_NTHR;   // threads that take a piece in the last round
     static_assert(C2_SLAB_HALFS * 2 % (16 * C2_NTHR) == 0, "weight slab / thread count");
     static_assert(C2_NTHR % 4 == 0, "a thread's items all belong to channel pair (tid & 3) of their k group");
-    float xa[XI], xb[XI];
+    dtype_t<XDT> xa[XI], xb[XI];   // as loaded: widened when written to LDS
     float affv = 0.0f;   // CAT: lanes 0-31 carry the next chunk's table entries from its loads to LDS
     typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
     u32x4 wq[WI];
     unsigned sat = 0, okm = 0;
 #define C2_LOAD_CHUNK(c_)                                                                              \
     {                                                                                                  \
-        const float *xc_ = xn + (size_t)(c_) * C2_KC * HW;                                             \
+        const dtype_t<XDT> *xc_ = xn + (size_t)(c_) * C2_KC * HW;                                      \
         if constexpr (CAT) {                                                                           \
             const bool first_ = (c_) < nch1;   /* workgroup-uniform */                                 \
             if (!first_) xc_ = x2n + (size_t)((c_) - nch1) * C2_KC * HW;                               \
@@ -145,8 +162,11 @@ __device__ __forceinline__ void conv2d_k3_tile(const float *__restrict__ x, cons
             xb[i] = xc_[off_ + HWu];                                                                   \
             okm = ok_ ? okm | (1u << i) : okm & ~(1u << i);   /* the select waits until the values are written to LDS */ \
         }                                                                                              \
+        /* opaque: with a third of the MFMAs hipcc else keeps the 11 lane masks in scalar pairs and spills kernel arguments */ \
+        if constexpr (NP == 1) asm volatile("" : "+v"(okm));                                           \
         const u32x4 *const ws_ = reinterpret_cast<const u32x4 *>(wslabs + ((size_t)cot * nchunks + (c_)) * C2_SLAB_HALFS); \
-        _Pragma("unroll") for (int i = 0; i < WI; ++i) wq[i] = ws_[i * C2_NTHR + tid_];                \
+        _Pragma("unroll") for (int i = 0; i < WI; ++i)                                                 \
+            if (W_WHOLE || i < WI - 1 || tid_ < W_LAST) wq[i] = ws_[i * C2_NTHR + tid_];              \
     }
     // CAT: parks the loaded chunk's table entries in LDS; a barrier separates it from C2_WRITE_CHUNK, whose reads of the previous
     // chunk's entries lie before the barrier that closed that write
@@ -174,7 +194,7 @@ __device__ __forceinline__ void conv2d_k3_tile(const float *__restrict__ x, cons
             if (e_ < NX) {                                                                             \
                 const int dst_ = (e_ >> 2) * 8 + (e_ & 3) * 2;   /* e_ >> 2 = kg * C2_XV + pixel */    \
                 const bool ok_ = (okm >> i) & 1u;                                                      \
-                float a_ = xa[i], b_ = xb[i];                                                          \
+                float a_ = widen(xa[i]), b_ = widen(xb[i]);                                            \
                 if constexpr (CAT) {                                                                   \
                     if (aff_on_) {                                                                     \
                         /* the item's k group: known at compile time except for the one i that straddles 4 * C2_XV */ \
@@ -192,15 +212,21 @@ __device__ __forceinline__ void conv2d_k3_tile(const float *__restrict__ x, cons
                 }                                                                                      \
                 const float v0_ = ok_ ? a_ * x_scale : 0.0f, v1_ = ok_ ? b_ * x_scale : 0.0f;          \
                 sat += !(fabsf(v0_) <= F16_CLAMP) + !(fabsf(v1_) <= F16_CLAMP);   /* NaN counts */     \
-                _Float16 hA_, lA_, hB_, lB_;                                                           \
-                split_f16(v0_, hA_, lA_);                                                              \
-                split_f16(v1_, hB_, lB_);                                                              \
-                const half2v hv_ = {hA_, hB_}, lv_ = {lA_, lB_};                                       \
-                *reinterpret_cast<half2v *>(Xs + dst_) = hv_;                                          \
-                *reinterpret_cast<half2v *>(Xs + C2_X_PART + dst_) = lv_;                              \
+                if constexpr (NP == 3) {                                                               \
+                    _Float16 hA_, lA_, hB_, lB_;                                                       \
+                    split_f16(v0_, hA_, lA_);                                                          \
+                    split_f16(v1_, hB_, lB_);                                                          \
+                    const half2v hv_ = {hA_, hB_}, lv_ = {lA_, lB_};                                   \
+                    *reinterpret_cast<half2v *>(Xs + dst_) = hv_;                                      \
+                    *reinterpret_cast<half2v *>(Xs + C2_X_PART + dst_) = lv_;                          \
+                } else {   /* one rounding (|v| > 65504 -> +-Inf, NaN -> NaN, like split_f16's hi) */  \
+                    const half2v hv_ = {(_Float16)v0_, (_Float16)v1_};                                 \
+                    *reinterpret_cast<half2v *>(Xs + dst_) = hv_;                                      \
+                }                                                                                      \
             }                                                                                          \
         }                                                                                              \
-        _Pragma("unroll") for (int i = 0; i < WI; ++i) reinterpret_cast<u32x4 *>(Ws)[i * C2_NTHR + tid_] = wq[i]; \
+        _Pragma("unroll") for (int i = 0; i < WI; ++i)                                                 \
+            if (W_WHOLE || i < WI - 1 || tid_ < W_LAST) reinterpret_cast<u32x4 *>(Ws)[i * C2_NTHR + tid_] = wq[i]; \
     }
 
     // ds_read_b128 is serviced in 16-lane groups {0-3,12-15,20-27} / {4-11,16-19,28-31} per half-wave: slot jv gives each group one
@@ -237,25 +263,29 @@ __device__ __forceinline__ void conv2d_k3_tile(const float *__restrict__ x, cons
 #pragma unroll
             for (int m = 0; m < 2; ++m) {
                 ah[m] = *reinterpret_cast<const half8 *>(Ws + a_base + (tap * 2 * C2_COT + m * 32) * 8);
-                al[m] = *reinterpret_cast<const half8 *>(Ws + C2_SLAB_HALFS / 2 + a_base + (tap * 2 * C2_COT + m * 32) * 8);
+                if constexpr (NP == 3) al[m] = *reinterpret_cast<const half8 *>(Ws + C2_SLAB_HALFS / 2 + a_base + (tap * 2 * C2_COT + m * 32) * 8);
             }
 #pragma unroll
             for (int t = 0; t < 2; ++t) {
                 bh[t] = *reinterpret_cast<const half8 *>(Xs + b_base + t * 2 * C2_HW * 8 + toff);
-                bl[t] = *reinterpret_cast<const half8 *>(Xs + C2_X_PART + b_base + t * 2 * C2_HW * 8 + toff);
+                if constexpr (NP == 3) bl[t] = *reinterpret_cast<const half8 *>(Xs + C2_X_PART + b_base + t * 2 * C2_HW * 8 + toff);
+            }
+            if constexpr (NP == 3) {
+#pragma unroll
+                for (int m = 0; m < 2; ++m)
+#pragma unroll
+                    for (int t = 0; t < 2; ++t) acc[m][t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[m], bh[t], acc[m][t], 0, 0, 0);
             }
 #pragma unroll
             for (int m = 0; m < 2; ++m)
 #pragma unroll
-                for (int t = 0; t < 2; ++t) acc[m][t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[m], bh[t], acc[m][t], 0, 0, 0);
-#pragma unroll
-            for (int m = 0; m < 2; ++m)
-#pragma unroll
                 for (int t = 0; t < 2; ++t) acc[m][t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[m], bh[t], acc[m][t], 0, 0, 0);
+            if constexpr (NP == 3) {
 #pragma unroll
-            for (int m = 0; m < 2; ++m)
+                for (int m = 0; m < 2; ++m)
 #pragma unroll
-                for (int t = 0; t < 2; ++t) acc[m][t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[m], bl[t], acc[m][t], 0, 0, 0);
+                    for (int t = 0; t < 2; ++t) acc[m][t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[m], bl[t], acc[m][t], 0, 0, 0);
+            }
         }
         if (more) {
             C2_PARK_AFFINE()
@@ -287,9 +317,13 @@ __device__ __forceinline__ void conv2d_k3_tile(const float *__restrict__ x, cons
                         const size_t oi = o + (size_t)row * HW;
                         float v = acc[m][t][reg] * unscale + bias[co0 + 4 * kg + row];
                         if (residual) v += residual[oi];
+                        if constexpr (YDT != MPHIP_DTYPE_F32) {
+                            if (residual_t) v += widen(residual_t[oi]);   // (workgroup-uniform; at most one of the two is set)
+                        }
                         if (relu) v = v < 0.0f ? 0.0f : v;   // (keeps NaN, like torch's relu)
-                        y[oi] = v;
-                        ymax = max(ymax, range_bits(v));
+                        const dtype_t<YDT> vy = narrow<YDT>(v);   // the one rounding of a typed y
+                        y[oi] = vy;
+                        ymax = max(ymax, range_bits(widen(vy)));   // of the value the next conv reads
                     }
                 }
             }

@@ -167,6 +167,8 @@ int f16x3_wino_bt_saturation(unsigned long long *count, int reset);
 int conv2d_f16x3_saturation(unsigned long long *count, int reset);
 // conv2d_gn_f16x3.hip: its two-source form (mphip_conv2d_cat_fwd), likewise
 int conv2d_gn_f16x3_saturation(unsigned long long *count, int reset);
+// conv2d_lp.hip: the typed and one-product instantiations of both (mphip_conv2d_fwd_typed, mphip_conv2d_cat_fwd_typed), likewise
+int conv2d_lp_saturation(unsigned long long *count, int reset);
 
 // api.hip: the calling thread's conv arithmetic policy (mphip_conv3d_set_half_products): true inside torch.autocast(float16) regions
 bool conv_half_products();

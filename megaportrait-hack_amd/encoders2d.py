@@ -131,13 +131,15 @@ class Eapp(nn.Module):
         self.custom_resnet50 = CustomResNet50()
         self.fc = nn.Linear(2048, COMPRESS_DIM)
 
-    def native_trunk(self, enable: bool = True) -> "Eapp":
+    def native_trunk(self, enable: bool = True, half_precision: bool = False) -> "Eapp":
         """Opt-in, inference only: run `resblock_128 / _256 / _512` as model.ResBlockCustomFused — two launches per block on the matrix
         cores with fp32-class accuracy (csrc/conv2d_gn_f16x3.hip): GroupNorm + ReLU folded into the convs' input staging, the skip conv
         folded into the last conv — over the blocks' own children: same Parameter objects, same state-dict keys.  `enable=False` puts the
         original blocks back.  Under autograd or on a half model the fused blocks evaluate the original PyTorch expression.  The 7x7
-        stem, the average pools and conv_1 stay on PyTorch."""
-        M.native_eapp_trunk(self, enable)
+        stem, the average pools and conv_1 stay on PyTorch.  half_precision (off by default): inside torch.autocast(float16), and as a
+        .half() / .bfloat16() model, the fused blocks run one f16 product per multiply and return the half dtype
+        (model.ResBlockCustomFused)."""
+        M.native_eapp_trunk(self, enable, half_precision)
         return self
 
     def trunk2d(self, x):
@@ -347,12 +349,14 @@ class G2d(M.G2dHead):
         M.native_final_conv(self, enable)
         return self
 
-    def native_body(self, enable: bool = True) -> "G2d":
+    def native_body(self, enable: bool = True, half_precision: bool = False) -> "G2d":
         """Opt-in, inference only: run every ResBlock2D of the body (`res_blocks`, `upsample1/2/3[1]`) as model.ResBlock2DFused —
         BatchNorm folded, the 3x3 convs on the matrix cores with fp32-class accuracy (csrc/conv2d_f16x3.hip) — over the blocks' own
         children: same Parameter objects, same state-dict keys.  `enable=False` puts the original blocks back.  In train mode, under
-        autograd or on a half model the fused blocks evaluate the original PyTorch expression."""
-        M.native_g2d_body(self, enable)
+        autograd or on a half model the fused blocks evaluate the original PyTorch expression.  half_precision (off by default):
+        inside torch.autocast(float16), and as a .half() / .bfloat16() model, the fused blocks run one f16 product per multiply and
+        return the half dtype (model.ResBlock2DFused)."""
+        M.native_g2d_body(self, enable, half_precision)
         return self
 
     def body(self, x):

@@ -58,17 +58,19 @@ class Gbase(M._HotSliceRunner, nn.Module):
         M.native_final_conv(self.G2d, enable)
         return self
 
-    def native_body(self, enable: bool = True) -> "Gbase":
+    def native_body(self, enable: bool = True, half_precision: bool = False) -> "Gbase":
         """Opt-in (off by default), inference only: G2d's ResBlock2D body as model.ResBlock2DFused — BatchNorm folded, 3x3 convs on the
-        matrix cores (model.native_g2d_body); `enable=False` restores the original blocks.  Same parameters and state-dict keys."""
-        M.native_g2d_body(self.G2d, enable)
+        matrix cores (model.native_g2d_body); `enable=False` restores the original blocks.  Same parameters and state-dict keys.
+        half_precision (off by default): the blocks' one-product form for autocast(float16) regions and half models."""
+        M.native_g2d_body(self.G2d, enable, half_precision)
         return self
 
-    def native_trunk(self, enable: bool = True) -> "Gbase":
+    def native_trunk(self, enable: bool = True, half_precision: bool = False) -> "Gbase":
         """Opt-in (off by default), inference only: the three ResBlock_Custom of the appearance encoder's 2-D trunk as
         model.ResBlockCustomFused — GroupNorm, ReLU and the skip conv folded into two matrix-core conv launches per block
-        (model.native_eapp_trunk); `enable=False` restores the original blocks.  Same parameters and state-dict keys."""
-        M.native_eapp_trunk(self.appearanceEncoder, enable)
+        (model.native_eapp_trunk); `enable=False` restores the original blocks.  Same parameters and state-dict keys.
+        half_precision (off by default): the blocks' one-product form for autocast(float16) regions and half models."""
+        M.native_eapp_trunk(self.appearanceEncoder, enable, half_precision)
         return self
 
     def _nhwc(self, x):

@@ -15,6 +15,7 @@ from __future__ import annotations
 
 import logging
 import os
+from typing import Optional
 
 import torch
 import torch.nn as nn
@@ -724,12 +725,43 @@ def native_final_conv(g2d: nn.Module, enable: bool = True) -> bool:
     return True
 
 
-def fold_batchnorm(conv: nn.Module, bn: nn.Module):
+def fold_batchnorm(conv: nn.Module, bn: nn.Module, dtype: Optional[torch.dtype] = None):
     """Eval-mode `bn(conv(x))` as one conv: s = gamma / sqrt(running_var + eps), w' = w * s[:, None, None, None],
-    b' = (b - running_mean) * s + beta, in the parameters' own dtype (fp32 on the native path) -> (w', b')."""
-    w, b = conv.weight.detach(), conv.bias.detach()
-    s = bn.weight.detach() / torch.sqrt(bn.running_var + bn.eps)
-    return (w * s[:, None, None, None]).contiguous(), ((b - bn.running_mean) * s + bn.bias.detach()).contiguous()
+    b' = (b - running_mean) * s + beta, in the parameters' own dtype (fp32 on the native path) -> (w', b').  dtype: the parameters and
+    running statistics are cast to it first (fp32 for a half block: the fold of its fp32 twin)."""
+    w, b, g, beta, mean, var = (t.detach() if dtype is None else t.detach().to(dtype)
+                                for t in (conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var))
+    s = g / torch.sqrt(var + bn.eps)
+    return (w * s[:, None, None, None]).contiguous(), ((b - mean) * s + beta).contiguous()
+
+
+def _half_mode(block: nn.Module, x, dt: torch.dtype):
+    """For a fused 2-D block built with half_precision=True: the dtype the one-product path writes for this call, or None when the call
+    takes the block's other paths.  dt: the block's parameter dtype.
+      - a .half() / .bfloat16() block fed a map of its own dtype: that dtype;
+      - an fp32 block inside torch.autocast('cuda', float16): float16, what the original block returns there;
+      - an fp32 block while the calling thread's ops.half_products policy is on: float32 (the twin the two contracts are stated with).
+    bf16 autocast regions are left alone."""
+    if not block.__dict__.get("_mphip_half") or not (isinstance(x, torch.Tensor) and x.is_cuda and x.dim() == 4 and x.numel() > 0):
+        return None
+    if dt in _HALF:
+        return dt if x.dtype == dt else None
+    if dt != torch.float32 or x.dtype not in (torch.float32,) + _HALF:
+        return None
+    if ops.autocast_half():
+        return torch.float16
+    return torch.float32 if ops.half_products_active() else None
+
+
+def _set_half(block: nn.Module, half_precision: bool) -> bool:
+    """Records the half_precision keyword on a fused block (nothing is stored when it is off) -> whether it changed."""
+    if bool(block.__dict__.get("_mphip_half", False)) == bool(half_precision):
+        return False
+    if half_precision:
+        block.__dict__["_mphip_half"] = True
+    else:
+        block.__dict__.pop("_mphip_half", None)
+    return True
 
 
 def _is_conv2d(m, k: int) -> bool:
@@ -753,7 +785,14 @@ class ResBlock2DFused(nn.Module):
     NO backward kernels and NO half-model path for this block: training, fine-tuning and .half() / .bfloat16() instances take the
     PyTorch expression.  fp16 / bf16 inputs (torch.autocast upstream) are widened (model._f32) and the result is fp32; channels_last
     inputs are copied to NCHW once.  A 1x1 shortcut runs through the existing k = 1 conv with its BatchNorm folded.  Each conv leaves
-    the range descriptor of its output on the tensor, so a fused block that directly follows does not scan its input again."""
+    the range descriptor of its output on the tensor, so a fused block that directly follows does not scan its input again.
+
+    `from_block(block, half_precision=True)` adds the half-precision form (csrc/conv2d_lp.hip; same conditions: eval mode, no autograd,
+    a supported shape).  Inside torch.autocast('cuda', float16) an fp32 block then runs ONE f16 product per multiply in both 3x3
+    launches, reads its input in the dtype it arrives in and returns float16, bitwise `.half()` of what it computes from `x.float()`
+    under ops.half_products(True) outside the region.  A .half() / .bfloat16() block folds its BatchNorms in fp32 from the widened
+    parameters, runs one product, reads input and residual and writes the output in the model dtype (y1 stays fp32): bitwise its fp32
+    twin under ops.half_products(True), rounded once.  Everything else takes the paths above."""
 
     def __init__(self, in_channels: int, out_channels: int):
         super().__init__()
@@ -785,7 +824,7 @@ class ResBlock2DFused(nn.Module):
                 and sc[0].out_channels == co and _is_bn2d(sc[1], co))
 
     @classmethod
-    def from_block(cls, block: nn.Module) -> "ResBlock2DFused":
+    def from_block(cls, block: nn.Module, half_precision: bool = False) -> "ResBlock2DFused":
         if not cls.matches(block):
             raise TypeError(f"ResBlock2DFused.from_block: expected a ResBlock2D without downsampling (3x3 stride-1 convs with bias, "
                             f"BatchNorm2d with running statistics, Identity or Conv2d 1x1 + BatchNorm2d shortcut), got {block}")
@@ -795,6 +834,7 @@ class ResBlock2DFused(nn.Module):
         for name in ("conv1", "bn1", "conv2", "bn2", "shortcut"):
             setattr(new, name, getattr(block, name))
         new.training = block.training   # (the children keep their own flags: they are the block's)
+        _set_half(new, half_precision)
         return new
 
     def _native_ok(self, x) -> bool:
@@ -814,18 +854,50 @@ class ResBlock2DFused(nn.Module):
         key = tuple((t.data_ptr(), t._version) for t in ts) + (str(ts[0].device), ops.weight_epoch())
         hit = self.__dict__.get("_mphip_fold")
         if hit is None or hit[0] != key or ops.repacking():
+            wide = torch.float32 if ts[0].dtype in _HALF else None   # a half block: the fold of its fp32 twin
             with torch.no_grad():
-                p1 = ops.PackedConv2d(*fold_batchnorm(self.conv1, self.bn1))
-                p2 = ops.PackedConv2d(*fold_batchnorm(self.conv2, self.bn2))
+                p1 = ops.PackedConv2d(*fold_batchnorm(self.conv1, self.bn1, wide))
+                p2 = ops.PackedConv2d(*fold_batchnorm(self.conv2, self.bn2, wide))
                 ps = None
                 if len(mods) > 4:
-                    ws, bs = fold_batchnorm(mods[4], mods[5])
+                    ws, bs = fold_batchnorm(mods[4], mods[5], wide)
                     ps = ops.PackedConv(ws.view(ws.shape[0], ws.shape[1], 1, 1, 1), bs)
             hit = (key, (p1, p2, ps))
             self.__dict__["_mphip_fold"] = hit
         return hit[1]
 
+    def _half_out(self, x):
+        """half_precision=True: the output dtype of the one-product path for this call (_half_mode), or None."""
+        if "_mphip_half" not in self.__dict__ or self.training:
+            return None
+        dt = _half_mode(self, x, self.conv1.weight.dtype)
+        if dt is None or x.shape[1] != self.conv1.in_channels or ag.needs_grad(self, x):
+            return None
+        if self.conv1.weight.dtype in _HALF and any(t.dtype != dt for t in self.state_dict().values() if t.is_floating_point()):
+            return None
+        n, ci, h, w = x.shape
+        co = self.conv1.out_channels
+        return dt if ops.conv2d_supported(n, ci, co, h, w) and ops.conv2d_supported(n, co, co, h, w) else None
+
+    def _forward_half(self, x, out_dtype):
+        if x.dtype in _HALF and x.dtype != out_dtype:   # (a bf16 map inside a float16 region: one half dtype per launch)
+            x = x.float()
+        xc = x.contiguous()   # (the kernels read NCHW: a channels_last map is copied once)
+        p1, p2, ps = self._folded()
+        with ops.half_products(True):
+            if ps is not None:   # the 1x1 shortcut reads fp32: one widening pass, which also delivers the descriptor conv1 needs
+                xc = ops.cast_to_f32_range(xc)
+                n, c, h, w = xc.shape
+                idt = ops.conv3d(xc.reshape(n, c, 1, h, w), ps, x_range=ops.current_range(xc)).reshape(n, ps.co, h, w)
+            else:
+                idt = xc
+            y1 = ops.conv2d(xc, p1, relu=True, want_range=True, products=0)
+            return ops.conv2d(y1, p2, residual=idt, relu=True, want_range=True, out_dtype=out_dtype, products=0)
+
     def forward(self, x):
+        half = self._half_out(x)
+        if half is not None:
+            return self._forward_half(x, half)
         if not self._native_ok(x):
             y = F.relu(self.bn1(self.conv1(x)))
             y = self.bn2(self.conv2(y))
@@ -844,10 +916,11 @@ class ResBlock2DFused(nn.Module):
 _G2D_BODY_SLOTS = (("upsample1", 1), ("upsample2", 1), ("upsample3", 1))
 
 
-def native_g2d_body(g2d: nn.Module, enable: bool = True) -> bool:
+def native_g2d_body(g2d: nn.Module, enable: bool = True, half_precision: bool = False) -> bool:
     """Swaps every matching ResBlock2D of `g2d.res_blocks`, `g2d.upsample1[1]`, `upsample2[1]`, `upsample3[1]` (this package's G2d or
     the reference's, model.py:720-746) for a ResBlock2DFused over the same children, or puts the very objects it replaced back.
-    Returns whether anything changed.  Off by default everywhere."""
+    Returns whether anything changed.  Off by default everywhere.  half_precision: the blocks' half-precision form (ResBlock2DFused);
+    blocks that are fused already take the keyword's value."""
     seqs = [(getattr(g2d, "res_blocks", None), None)] + [(getattr(g2d, name, None), idx) for name, idx in _G2D_BODY_SLOTS]
     changed = False
     for seq, only in seqs:
@@ -855,8 +928,10 @@ def native_g2d_body(g2d: nn.Module, enable: bool = True) -> bool:
             continue
         for i in (range(len(seq)) if only is None else [only] if len(seq) > only else []):
             cur = seq[i]
-            if enable and ResBlock2DFused.matches(cur):
-                new = ResBlock2DFused.from_block(cur)
+            if enable and isinstance(cur, ResBlock2DFused):
+                changed |= _set_half(cur, half_precision)
+            elif enable and ResBlock2DFused.matches(cur):
+                new = ResBlock2DFused.from_block(cur, half_precision)
                 new.__dict__["_replaced"] = cur   # (not a registered child: the module tree and the state-dict keys stay as they were)
                 seq[i] = new
                 changed = True
@@ -872,13 +947,14 @@ def standardise_weight(w: torch.Tensor) -> torch.Tensor:
     return w / (w.flatten(1).std(dim=1).view(-1, 1, 1, 1) + 1e-5)
 
 
-def fold_resblock_custom(conv_res: nn.Module, conv_ws: nn.Module, conv: nn.Module):
+def fold_resblock_custom(conv_res: nn.Module, conv_ws: nn.Module, conv: nn.Module, dtype: Optional[torch.dtype] = None):
     """ResBlock_Custom as two convs -> ((w_ws', b_ws), (w_cat, b_cat)) in the parameters' own dtype: conv_ws with its weight
     standardised, and conv(a) + conv_res(x) as ONE conv over the channel concatenation [a ; x]: w_cat = [W_conv | W_res] along dim 1,
-    b_cat = b_conv + b_res."""
-    w_ws = standardise_weight(conv_ws.weight.detach()).contiguous()
-    w_cat = torch.cat([conv.weight.detach(), conv_res.weight.detach()], dim=1).contiguous()
-    return (w_ws, conv_ws.bias.detach().contiguous()), (w_cat, (conv.bias.detach() + conv_res.bias.detach()).contiguous())
+    b_cat = b_conv + b_res.  dtype: the parameters are cast to it first (fp32 for a half block: the fold of its fp32 twin)."""
+    cast = (lambda t: t.detach()) if dtype is None else (lambda t: t.detach().to(dtype))
+    w_ws = standardise_weight(cast(conv_ws.weight)).contiguous()
+    w_cat = torch.cat([cast(conv.weight), cast(conv_res.weight)], dim=1).contiguous()
+    return (w_ws, cast(conv_ws.bias).contiguous()), (w_cat, (cast(conv.bias) + cast(conv_res.bias)).contiguous())
 
 
 class ResBlockCustomFused(nn.Module):
@@ -892,7 +968,13 @@ class ResBlockCustomFused(nn.Module):
     The native path runs without autograd (ag.needs_grad false) on an fp32 module, a CUDA input and a supported shape, in train and in
     eval mode alike (the block has no mode-dependent layer); otherwise forward evaluates the original block's expression in PyTorch.
     There are NO backward kernels and NO half-model path: training, fine-tuning and .half() / .bfloat16() instances take the PyTorch
-    expression.  fp16 / bf16 inputs are widened (model._f32) and the result is fp32; channels_last inputs are copied to NCHW once."""
+    expression.  fp16 / bf16 inputs are widened (model._f32) and the result is fp32; channels_last inputs are copied to NCHW once.
+
+    `from_block(block, half_precision=True)` adds the half-precision form (csrc/conv2d_lp.hip), with the contracts stated on
+    ResBlock2DFused: inside torch.autocast('cuda', float16) an fp32 block runs one f16 product per multiply in both launches and returns
+    float16; a .half() / .bfloat16() block folds its weights in fp32 from the widened parameters, runs one product and writes the
+    model dtype.  A typed input is widened once (ops.cast_to_f32_range: the pass also delivers the descriptor of x the second launch
+    needs); GroupNorm statistics and tables are taken on fp32 maps by their existing kernels, and `t` stays fp32."""
 
     def __init__(self, dimension: int, in_channels: int, out_channels: int):
         super().__init__()
@@ -917,7 +999,7 @@ class ResBlockCustomFused(nn.Module):
         return (ws.in_channels, ws.out_channels, conv.in_channels, conv.out_channels) == (ci, co, co, co)
 
     @classmethod
-    def from_block(cls, block: nn.Module) -> "ResBlockCustomFused":
+    def from_block(cls, block: nn.Module, half_precision: bool = False) -> "ResBlockCustomFused":
         if not cls.matches(block):
             raise TypeError(f"ResBlockCustomFused.from_block: expected a 2-D ResBlock_Custom (conv_res, conv_ws (Conv2d_WS), conv: 3x3 "
                             f"stride-1 padding-1 convs with bias), got {block}")
@@ -927,6 +1009,7 @@ class ResBlockCustomFused(nn.Module):
         for name in ("conv_res", "conv_ws", "conv"):
             setattr(new, name, getattr(block, name))
         new.training = block.training
+        _set_half(new, half_precision)
         return new
 
     def _native_ok(self, x) -> bool:
@@ -946,12 +1029,36 @@ class ResBlockCustomFused(nn.Module):
         hit = self.__dict__.get("_mphip_fold")
         if hit is None or hit[0] != key or ops.repacking():
             with torch.no_grad():
-                ws, cat = fold_resblock_custom(self.conv_res, self.conv_ws, self.conv)
+                ws, cat = fold_resblock_custom(self.conv_res, self.conv_ws, self.conv, torch.float32 if ts[0].dtype in _HALF else None)
                 hit = (key, (ops.PackedConv2d(*ws), ops.PackedConv2d(*cat)))
             self.__dict__["_mphip_fold"] = hit
         return hit[1]
 
+    def _half_out(self, x):
+        """half_precision=True: the output dtype of the one-product path for this call (_half_mode), or None."""
+        if "_mphip_half" not in self.__dict__:
+            return None
+        dts = {p.dtype for p in self.parameters()}
+        dt = _half_mode(self, x, dts.pop()) if len(dts) == 1 else None
+        if dt is None or x.shape[1] != self.in_channels or ag.needs_grad(self, x):
+            return None
+        n, ci, h, w = x.shape
+        co = self.out_channels
+        return dt if ops.conv2d_cat_supported(n, ci, 0, co, h, w) and ops.conv2d_cat_supported(n, co, ci, co, h, w) else None
+
+    def _forward_half(self, x, out_dtype):
+        xc = ops.cast_to_f32_range(x.contiguous())   # (an fp32 map is returned as it is; NCHW: a channels_last map is copied once)
+        p_ws, p_cat = self._folded()
+        with ops.half_products(True):
+            tab, rng = ops.gn_relu_table2d(xc)
+            t = ops.conv2d_cat(xc, p_ws, affine1=tab, relu1=True, x1_range=rng, products=0)
+            tab, rng = ops.gn_relu_table2d(t)
+            return ops.conv2d_cat(t, p_cat, x2=xc, affine1=tab, relu1=True, x1_range=rng, want_range=True, out_dtype=out_dtype, products=0)
+
     def forward(self, x):
+        half = self._half_out(x)
+        if half is not None:
+            return self._forward_half(x, half)
         if not self._native_ok(x):
             skip = self.conv_res(x)
             y = self.conv_ws(F.relu(F.group_norm(x, 32)))
@@ -968,15 +1075,18 @@ class ResBlockCustomFused(nn.Module):
 _EAPP_TRUNK_SLOTS = ("resblock_128", "resblock_256", "resblock_512")
 
 
-def native_eapp_trunk(eapp: nn.Module, enable: bool = True) -> bool:
+def native_eapp_trunk(eapp: nn.Module, enable: bool = True, half_precision: bool = False) -> bool:
     """Swaps every matching ResBlock_Custom among `eapp.resblock_128 / _256 / _512` (this package's Eapp or the reference's,
     model.py:210-212) for a ResBlockCustomFused over the same children, or puts the very objects it replaced back.  Returns whether
-    anything changed.  Off by default everywhere."""
+    anything changed.  Off by default everywhere.  half_precision: the blocks' half-precision form (ResBlockCustomFused); blocks that
+    are fused already take the keyword's value."""
     changed = False
     for name in _EAPP_TRUNK_SLOTS:
         cur = getattr(eapp, name, None)
-        if enable and ResBlockCustomFused.matches(cur):
-            new = ResBlockCustomFused.from_block(cur)
+        if enable and isinstance(cur, ResBlockCustomFused):
+            changed |= _set_half(cur, half_precision)
+        elif enable and ResBlockCustomFused.matches(cur):
+            new = ResBlockCustomFused.from_block(cur, half_precision)
             new.__dict__["_replaced"] = cur   # (not a registered child: the module tree and the state-dict keys stay as they were)
             setattr(eapp, name, new)
             changed = True

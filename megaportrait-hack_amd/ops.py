@@ -1232,12 +1232,30 @@ def conv2d_supported(n: int, ci: int, co: int, h: int, w: int) -> bool:
     return bool(_lib.load().mphip_conv2d_supported(int(n), int(ci), int(co), int(h), int(w)))
 
 
+def _conv2d_products(products: Optional[int], who: str) -> int:
+    if products not in (None, 0, 1, 3):
+        raise RuntimeError(f"{who}: products = {products!r} (3, 1, or 0: follow ops.half_products)")
+    return 3 if products is None else int(products)
+
+
+def conv2d_typed_supported(two_source: bool, x_dtype: torch.dtype, residual_dtype: torch.dtype, y_dtype: torch.dtype, products: int) -> bool:
+    """Is this combination of map dtypes and product count (3, 1, or 0: the thread's current policy) built (mphip_conv2d_typed_supported)?"""
+    return bool(_lib.load().mphip_conv2d_typed_supported(int(bool(two_source)), dtype_code(x_dtype), dtype_code(residual_dtype),
+                                                         dtype_code(y_dtype), int(products)))
+
+
 def conv2d(x: torch.Tensor, pack: PackedConv2d, residual: Optional[torch.Tensor] = None, relu: bool = False,
-           x_range: Optional[torch.Tensor] = None, want_range: bool = False) -> torch.Tensor:
+           x_range: Optional[torch.Tensor] = None, want_range: bool = False, out_dtype: Optional[torch.dtype] = None,
+           products: Optional[int] = None) -> torch.Tensor:
     """y = act(conv3x3(x) + bias (+ residual)) on NCHW fp32, padding 1 (mphip_conv2d_fwd): the f16x3 arithmetic, fp32-class accuracy.
     x_range: the input's range descriptor; without one the descriptor its producer tagged on x is used, else the library scans x.
-    want_range: y comes back tagged with the descriptor of its exact max|y| (ops.tensor_range(y)), which the next conv2d picks up."""
-    x = _req(x, "x")
+    want_range: y comes back tagged with the descriptor of its exact max|y| (ops.tensor_range(y)), which the next conv2d picks up.
+    out_dtype / products (mphip_conv2d_fwd_typed): x may be fp16 / bf16 (widened on load), y is written in out_dtype (default fp32; the
+    fp32 value rounded once, the descriptor then is that of the rounded values), the residual is fp32 or in out_dtype.  products: 3 (the
+    default), 1 = one f16 product per multiply (the autocast arithmetic), 0 = follow ops.half_products.  With neither keyword and an fp32
+    x this is the fp32 entry, whatever the policy flag says.  Not every combination is built (conv2d_typed_supported)."""
+    typed = out_dtype is not None or products is not None or (isinstance(x, torch.Tensor) and x.dtype != torch.float32)
+    x = _req_typed(x, "x") if typed else _req(x, "x")
     if x.dim() != 4 or x.shape[1] != pack.ci:
         raise RuntimeError(f"conv2d: input {tuple(x.shape)} does not match Ci={pack.ci}")
     n, ci, h, w = x.shape
@@ -1245,17 +1263,25 @@ def conv2d(x: torch.Tensor, pack: PackedConv2d, residual: Optional[torch.Tensor]
     if not lib.mphip_conv2d_supported(n, ci, pack.co, h, w):
         raise RuntimeError(f"conv2d: unsupported shape N={n} Ci={ci} Co={pack.co} H={h} W={w} (there is no fallback)")
     if residual is not None:
-        residual = _req(residual, "residual")
+        residual = _req_typed(residual, "residual") if typed else _req(residual, "residual")
         if tuple(residual.shape) != (n, pack.co, h, w):
             raise RuntimeError(f"conv2d: residual {tuple(residual.shape)} does not match the output {(n, pack.co, h, w)}")
     xr = x_range if x_range is not None else current_range(x)   # None: the library scans x
     ws_bytes = lib.mphip_conv2d_workspace_bytes(n, ci, pack.co, h, w)
     ws = torch.empty((ws_bytes + 3) // 4, dtype=torch.float32, device=x.device) if xr is None else None
-    y = torch.empty((n, pack.co, h, w), dtype=torch.float32, device=x.device)
+    ydt = torch.float32 if out_dtype is None else out_dtype
+    y = torch.empty((n, pack.co, h, w), dtype=ydt, device=x.device)
     out_range = new_range(x.device) if want_range else None
-    _lib.check(lib.mphip_conv2d_fwd(_ptr(x), _ptr(xr), _ptr(pack.packed()), _ptr(pack.bias), _ptr(residual), _ptr(y), _ptr(out_range),
-                                    n, ci, pack.co, h, w, int(bool(relu)), _ptr(ws), ws_bytes if ws is not None else 0, _stream()),
-               "mphip_conv2d_fwd")
+    if not typed:
+        _lib.check(lib.mphip_conv2d_fwd(_ptr(x), _ptr(xr), _ptr(pack.packed()), _ptr(pack.bias), _ptr(residual), _ptr(y), _ptr(out_range),
+                                        n, ci, pack.co, h, w, int(bool(relu)), _ptr(ws), ws_bytes if ws is not None else 0, _stream()),
+                   "mphip_conv2d_fwd")
+        return tag_range(y, out_range)
+    rdt = torch.float32 if residual is None else residual.dtype
+    _lib.check(lib.mphip_conv2d_fwd_typed(_ptr(x), dtype_code(x.dtype), _ptr(xr), _ptr(pack.packed()), _ptr(pack.bias), _ptr(residual),
+                                          dtype_code(rdt), _ptr(y), dtype_code(ydt), _ptr(out_range), n, ci, pack.co, h, w,
+                                          int(bool(relu)), _conv2d_products(products, "conv2d"), _ptr(ws),
+                                          ws_bytes if ws is not None else 0, _stream()), "mphip_conv2d_fwd_typed")
     return tag_range(y, out_range)
 
 
@@ -1290,19 +1316,24 @@ def conv2d_cat_supported(n: int, c1: int, c2: int, co: int, h: int, w: int) -> b
 def conv2d_cat(x1: torch.Tensor, pack: PackedConv2d, x2: Optional[torch.Tensor] = None, affine1: Optional[torch.Tensor] = None,
                affine2: Optional[torch.Tensor] = None, relu1: bool = False, relu2: bool = False, x1_range: Optional[torch.Tensor] = None,
                x2_range: Optional[torch.Tensor] = None, residual: Optional[torch.Tensor] = None, relu: bool = False,
-               want_range: bool = False) -> torch.Tensor:
+               want_range: bool = False, out_dtype: Optional[torch.dtype] = None, products: Optional[int] = None) -> torch.Tensor:
     """y = act(conv3x3([s1 ; s2]) + bias (+ residual)), padding 1 (mphip_conv2d_cat_fwd): the conv of the channel concatenation of two
     NCHW fp32 maps, which is never built; `pack` holds an OIHW weight with Ci = C1 + C2.  s_i = x_i, or with a table affine_i [N,C_i,2]
     (gn_relu_table2d) x_i * scale + shift, then ReLU if relu_i, applied while the conv stages its input (padding stays zero).  A source
     with a table needs its descriptor x_i_range (the table's); one without takes x_i_range, else the descriptor tagged on x_i, else the
-    library scans it.  Without x2 and tables: the bits of ops.conv2d."""
-    x1 = _req(x1, "x1")
+    library scans it.  Without x2 and tables: the bits of ops.conv2d.
+    out_dtype / products (mphip_conv2d_cat_fwd_typed): as in ops.conv2d; the sources stay fp32 (a typed one is refused by the library:
+    widen it once with ops.cast_to_f32_range, which also delivers its descriptor)."""
+    typed = out_dtype is not None or products is not None or any(isinstance(t, torch.Tensor) and t.dtype != torch.float32 for t in (x1, x2))
+    if typed and isinstance(x2, torch.Tensor) and isinstance(x1, torch.Tensor) and x2.dtype != x1.dtype:
+        raise RuntimeError(f"conv2d_cat: x1 is {x1.dtype} and x2 {x2.dtype}: both sources are fp32")
+    x1 = _req_typed(x1, "x1") if typed else _req(x1, "x1")
     if x1.dim() != 4:
         raise RuntimeError(f"conv2d_cat: expected an [N,C,H,W] map, got {tuple(x1.shape)}")
     n, c1, h, w = x1.shape
     c2 = 0
     if x2 is not None:
-        x2 = _req(x2, "x2")
+        x2 = _req_typed(x2, "x2") if typed else _req(x2, "x2")
         if x2.dim() != 4 or (x2.shape[0], x2.shape[2], x2.shape[3]) != (n, h, w):
             raise RuntimeError(f"conv2d_cat: x2 {tuple(x2.shape)} does not match x1 {tuple(x1.shape)}")
         c2 = int(x2.shape[1])
@@ -1316,7 +1347,7 @@ def conv2d_cat(x1: torch.Tensor, pack: PackedConv2d, x2: Optional[torch.Tensor] 
         if tab is not None and tuple(tab.shape) != (n, c, 2):
             raise RuntimeError(f"conv2d_cat: {name} {tuple(tab.shape)} is not the [{n},{c},2] table of its source")
     if residual is not None:
-        residual = _req(residual, "residual")
+        residual = _req_typed(residual, "residual") if typed else _req(residual, "residual")
         if tuple(residual.shape) != (n, pack.co, h, w):
             raise RuntimeError(f"conv2d_cat: residual {tuple(residual.shape)} does not match the output {(n, pack.co, h, w)}")
     lib = _lib.load()
@@ -1326,8 +1357,17 @@ def conv2d_cat(x1: torch.Tensor, pack: PackedConv2d, x2: Optional[torch.Tensor] 
     scan = r1 is None or (x2 is not None and r2 is None)
     ws_bytes = lib.mphip_conv2d_cat_workspace_bytes(n, c1, c2, pack.co, h, w) if scan else 0
     ws = torch.empty((ws_bytes + 3) // 4, dtype=torch.float32, device=x1.device) if ws_bytes else None
-    y = torch.empty((n, pack.co, h, w), dtype=torch.float32, device=x1.device)
+    ydt = torch.float32 if out_dtype is None else out_dtype
+    y = torch.empty((n, pack.co, h, w), dtype=ydt, device=x1.device)
     out_range = new_range(x1.device) if want_range else None
+    if typed:
+        rdt = torch.float32 if residual is None else residual.dtype
+        _lib.check(lib.mphip_conv2d_cat_fwd_typed(_ptr(x1), dtype_code(x1.dtype), _ptr(affine1), int(bool(relu1)), _ptr(r1), c1, _ptr(x2),
+                                                  _ptr(affine2), int(bool(relu2)), _ptr(r2), c2, _ptr(pack.packed()), _ptr(pack.bias),
+                                                  _ptr(residual), dtype_code(rdt), _ptr(y), dtype_code(ydt), _ptr(out_range), n, pack.co,
+                                                  h, w, int(bool(relu)), _conv2d_products(products, "conv2d_cat"), _ptr(ws), ws_bytes,
+                                                  _stream()), "mphip_conv2d_cat_fwd_typed")
+        return tag_range(y, out_range)
     _lib.check(lib.mphip_conv2d_cat_fwd(_ptr(x1), _ptr(affine1), int(bool(relu1)), _ptr(r1), c1, _ptr(x2), _ptr(affine2), int(bool(relu2)),
                                         _ptr(r2), c2, _ptr(pack.packed()), _ptr(pack.bias), _ptr(residual), _ptr(y), _ptr(out_range), n,
                                         pack.co, h, w, int(bool(relu)), _ptr(ws), ws_bytes, _stream()), "mphip_conv2d_cat_fwd")

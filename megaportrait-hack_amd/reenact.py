@@ -46,6 +46,9 @@ def parse(argv=None):
     ap.add_argument("--native-g2d-body", action="store_true",
                     help="run G2d's ResBlock2D body with BatchNorm folded and its 3x3 convs on the matrix cores "
                          "(gbase.Gbase.native_body; inference only, fp32 models; off by default)")
+    ap.add_argument("--native-half-precision", action="store_true",
+                    help="with --native-g2d-body / --native-eapp-trunk: the fused blocks' half-precision form, one f16 product per "
+                         "multiply and half outputs under --fp16 (autocast) and with --dtype fp16 / bf16 (off by default)")
     ap.add_argument("--native-eapp-trunk", action="store_true",
                     help="run the appearance encoder's three 2-D ResBlock_Custom blocks on the matrix cores, GroupNorm, ReLU and the skip "
                          "conv folded into two conv launches per block (gbase.Gbase.native_trunk; inference only, fp32 models; off by default)")
@@ -169,10 +172,11 @@ def run(job: dict, args, rank: int, world: int) -> List[str]:
         g.channels_last_2d()
     if args.native_final_conv:
         g.native_final_conv()
+    half = {"half_precision": True} if args.native_half_precision else {}   # (the keyword is passed only when the flag is given)
     if args.native_g2d_body:
-        g.native_body()
+        g.native_body(**half)
     if args.native_eapp_trunk:
-        g.native_trunk()
+        g.native_trunk(**half)
     xs = _load_tensor(job["source_tensor"]) if job["source_tensor"] else _load_image(job["source"])
     n = _load_tensor(job["drivers_tensor"]).shape[0] if job["drivers_tensor"] else len(job["drivers"])
     b, e, outputs = shard_plan(job, n, rank, world)

@@ -1,8 +1,9 @@
 """Informational: G2d's ResBlock2D body, [B,512,64,64] -> [B,64,512,512] (8 x ResBlock2D(512) + three bilinear x2 + ResBlock2D stages) —
 model.ResBlock2DFused (BatchNorm folded, 3x3 convs of csrc/conv2d_f16x3.hip) against torch's own modules on the same box and commit, in the
 same run: torch fp32 with cudnn.benchmark off and on, NCHW and channels_last, torch under autocast-fp16 (for information: a different
-arithmetic), the native body, and one 512->512 conv launch at 64x64 (19.3 GFLOP per frame) with its TFLOP/s.  HIP events over `steps` calls
-after `warmup`.  Prints one JSON line; --out also writes it to a file.
+arithmetic), the native body, and one 512->512 conv launch at 64x64 (19.3 GFLOP per frame) with its TFLOP/s — in three and in one product.
+Half-precision legs (half_precision=True): torch under autocast-fp16 against the native body under autocast-fp16, and a .half() body,
+native against torch.  HIP events over `steps` calls after `warmup`.  Prints one JSON line; --out also writes it to a file.
 usage: python tools/bench_g2d_body.py [--b 8] [--warmup 20] [--steps 50] [--out profiles/g2d_body_timing.json]"""
 import argparse, copy, json, os, subprocess, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -78,11 +79,25 @@ def main():
             legs["torch_autocast_fp16_channels_last_benchmark_on"] = step_ms(lambda: body_cl(x_cl), a.warmup, a.steps)
         legs["native_fp32"] = step_ms(lambda: native(x), a.warmup, a.steps)
         err = (native(x) - body(x)).abs().max().item()
+        # the half-precision form: the same process, torch's leg first, then the native one, for each of the two modes
+        native_hp = copy.deepcopy(body)
+        assert M.native_g2d_body(native_hp, True, half_precision=True)
+        with torch.autocast(device_type="cuda", dtype=torch.float16):
+            legs["torch_autocast_fp16_nchw_again"] = step_ms(lambda: body(x), a.warmup, a.steps)
+            legs["native_half_precision_autocast_fp16"] = step_ms(lambda: native_hp(x), a.warmup, a.steps)
+            err_autocast = (native_hp(x).float() - body(x).float()).abs().max().item()
+        body_h, xh = copy.deepcopy(body).half(), x.half()
+        native_h = copy.deepcopy(body_h)
+        assert M.native_g2d_body(native_h, True, half_precision=True)
+        legs["torch_half_module_nchw"] = step_ms(lambda: body_h(xh), a.warmup, a.steps)
+        legs["native_half_precision_half_module"] = step_ms(lambda: native_h(xh), a.warmup, a.steps)
+        err_half = (native_h(xh).float() - body_h(xh).float()).abs().max().item()
         # one launch of the dominant conv: 512 -> 512 at 64x64, bias + ReLU epilogue, the input's descriptor at hand
         blk = native.res_blocks[0]
         p1 = blk._folded()[0]
         rng = ops.absmax_range(x)
         conv_ms = step_ms(lambda: ops.conv2d(x, p1, relu=True, x_range=rng, want_range=True), a.warmup, a.steps)
+        conv1_ms = step_ms(lambda: ops.conv2d(x, p1, relu=True, x_range=rng, want_range=True, products=1), a.warmup, a.steps)
         conv_torch_ms = step_ms(lambda: torch.relu_(nn.functional.conv2d(x, p1.weight, p1.bias, padding=1)), a.warmup, a.steps)
     flop = 2.0 * 9 * 512 * 512 * a.hw * a.hw * a.b
     best_torch = min(v for k, v in legs.items() if k.startswith("torch_fp32"))
@@ -92,7 +107,11 @@ def main():
            "body_ms": {k: round(v, 4) for k, v in legs.items()},
            "best_torch_fp32_over_native": round(best_torch / legs["native_fp32"], 3),
            "native_vs_torch_fp32_max_abs": err,
+           "torch_autocast_fp16_over_native_half_precision": round(legs["torch_autocast_fp16_nchw_again"] / legs["native_half_precision_autocast_fp16"], 3),
+           "torch_half_module_over_native_half_precision": round(legs["torch_half_module_nchw"] / legs["native_half_precision_half_module"], 3),
+           "native_half_precision_vs_torch_max_abs": {"autocast_fp16": err_autocast, "half_module": err_half},
            "conv_512_512_64x64": {"native_ms": round(conv_ms, 4), "native_tflops": round(flop / conv_ms * 1e-9, 1),
+                                  "native_one_product_ms": round(conv1_ms, 4), "native_one_product_tflops": round(flop / conv1_ms * 1e-9, 1),
                                   "torch_fp32_ms": round(conv_torch_ms, 4), "torch_fp32_tflops": round(flop / conv_torch_ms * 1e-9, 1),
                                   "gflop_per_frame": round(flop / a.b * 1e-9, 2)}}
     print(json.dumps(out))
