@@ -558,7 +558,9 @@ int mphip_g2d_final_bwd(const float *x, const float *y, const float *dy, const f
  *   mphip_pack_conv2d_weight: w_oihw [Co,Ci,3,3] fp32 -> w_packed (mphip_conv2d_packed_weight_bytes, 16-byte aligned): a 16-byte header
  *          {1/scale, scale, max|w| bits, -} and the hi/lo f16 LDS image of every (64-channel co tile, 16-channel chunk) slab
  *          [part][tap][kg][co][8].  One reduction and one pack launch; once per weight version.
- *   mphip_conv2d_fwd: x [N,Ci,H,W], bias [Co], residual [N,Co,H,W] or NULL, y [N,Co,H,W] (y must not alias x or residual).
+ *   mphip_conv2d_fwd: x [N,Ci,H,W], bias [Co], residual [N,Co,H,W] or NULL, y [N,Co,H,W].  y must not overlap x or residual: such a call
+ *          is refused (MPHIP_EINVAL, "must not alias"), as by the three entries below; it used to run and race (a workgroup reads the
+ *          halo of tiles other workgroups write).
  *          x_range: a range descriptor of x (see "Range descriptors"), or NULL: the library computes one with one extra read of x in
  *          `workspace` (mphip_conv2d_workspace_bytes; not needed when x_range is given).  out_range (optional, MPHIP_RANGE_FLOATS
  *          floats): receives a descriptor of y in derive mode whose partial maxima fold to the EXACT max|y|, so the next conv takes
@@ -605,7 +607,10 @@ int mphip_conv2d_cat_fwd(const float *x1, const float *affine1, int relu1, const
  * residual_dtype, y_dtype, products) returns 1 for those that are — one product: plain form x any / y F32 and x F32 / y any, two-source
  * form y any; three products: all F32 — and the launch refuses the others (MPHIP_EINVAL), like an unknown dtype code, two different half
  * dtypes, a typed source of the two-source form and a product count outside {0, 1, 3}, before the first HIP call.
- * y must not overlap x / x1, x2 or residual.  Workspaces: mphip_conv2d_workspace_bytes / mphip_conv2d_cat_workspace_bytes.            */
+ * y must not overlap x / x1, x2 or residual.  Workspaces: mphip_conv2d_workspace_bytes / mphip_conv2d_cat_workspace_bytes.
+ * All four entries share one argument check, made before the first HIP call in one order: dtypes and products, null pointers, the second
+ * source, the shape, alignment (every map to its element size), tables and their descriptors, overlap (MPHIP_EINVAL each), then the
+ * workspace (MPHIP_EWORKSPACE).  A message names the entry that was called; an all-F32 three-product call names the fp32 entry.      */
 int mphip_conv2d_typed_supported(int two_source, int x_dtype, int residual_dtype, int y_dtype, int products);
 int mphip_conv2d_fwd_typed(const void *x, int x_dtype, const float *x_range, const void *w_packed, const float *bias, const void *residual,
                            int residual_dtype, void *y, int y_dtype, float *out_range, int N, int Ci, int Co, int H, int W, int relu,

@@ -107,6 +107,12 @@ void conv2d_out_range_init_launch(float *range, unsigned nslots, hipStream_t s) 
     hipLaunchKernelGGL(conv2d_out_range_init_kernel, dim3(cdiv(nslots + 4, 256)), dim3(256), 0, s, range, nslots);
 }
 
+void conv2d_plain_launch(const C2Call &c, const C2Grid &g) {
+    hipLaunchKernelGGL(conv2d_k3_f16x3_kernel, g.grid, dim3(C2_NTHR), 0, c.stream, (const float *)c.x1, c.x1_range,
+                       (const _Float16 *)((const char *)c.w_packed + 16), (const float *)c.w_packed, c.bias, (const float *)c.residual,
+                       (float *)c.y, c.out_range, c.C1, c.Co, c.H, c.W, c.relu, g.tiles_w, g.tiles_h, g.nslots);
+}
+
 int conv2d_f16x3_saturation(unsigned long long *count, int reset) { return f16x3_counter_read(&g_conv2d_saturated, count, reset); }
 
 }  // namespace mphip
@@ -138,37 +144,12 @@ extern "C" int mphip_pack_conv2d_weight(const float *w_oihw, void *w_packed, int
 }
 
 extern "C" size_t mphip_conv2d_workspace_bytes(int N, int Ci, int Co, int H, int W) {
-    if (!c2_supported(N, Ci, Co, H, W)) return 0;
-    return (size_t)MPHIP_RANGE_FLOATS * sizeof(float);   // the library-computed descriptor of x (x_range == NULL)
+    return c2_supported(N, Ci, Co, H, W) ? c2_workspace_bytes(1) : 0;   // the library-computed descriptor of x (x_range == NULL)
 }
 
 extern "C" int mphip_conv2d_fwd(const float *x, const float *x_range, const void *w_packed, const float *bias, const float *residual,
                                 float *y, float *out_range, int N, int Ci, int Co, int H, int W, int relu, void *workspace,
                                 size_t workspace_bytes, void *stream) {
-    MPHIP_REQUIRE(x && w_packed && bias && y, "conv2d_fwd: null pointer");
-    MPHIP_REQUIRE(c2_supported(N, Ci, Co, H, W),
-                  "conv2d_fwd: unsupported shape N=%d Ci=%d Co=%d H=%d W=%d (Ci %% 16 == 0, Co %% 32 == 0, N, H, W >= 1, fewer than 2^31 "
-                  "elements per tensor)", N, Ci, Co, H, W);
-    MPHIP_REQUIRE(((uintptr_t)w_packed & 15) == 0 && ((uintptr_t)x & 3) == 0 && ((uintptr_t)y & 3) == 0,
-                  "conv2d_fwd: w_packed must be 16-byte aligned, x and y 4-byte aligned");
-    hipStream_t s = (hipStream_t)stream;
-    if (!x_range) {
-        const size_t need = (size_t)MPHIP_RANGE_FLOATS * sizeof(float);
-        if (!workspace || workspace_bytes < need) {
-            set_error("conv2d_fwd: workspace %zu bytes < required %zu", workspace_bytes, need);
-            return MPHIP_EWORKSPACE;
-        }
-        MPHIP_REQUIRE(((uintptr_t)workspace & 3) == 0, "conv2d_fwd: the workspace must be 4-byte aligned");
-        conv2d_range_launch(x, (size_t)N * Ci * H * W, (float *)workspace, s);
-        x_range = (const float *)workspace;
-    }
-    const int tiles_w = cdiv(W, C2_TW), tiles_h = cdiv(H, C2_TH);
-    const long long tiles = (long long)N * tiles_h * tiles_w;
-    MPHIP_REQUIRE(tiles < (1ll << 31), "conv2d_fwd: %lld tiles do not fit a launch", tiles);
-    const dim3 grid((unsigned)tiles, (unsigned)c2_cots(Co));
-    const unsigned nslots = (unsigned)std::min<long long>(tiles * c2_cots(Co), (long long)RANGE_MAX_PARTS);
-    if (out_range) conv2d_out_range_init_launch(out_range, nslots, s);
-    hipLaunchKernelGGL(conv2d_k3_f16x3_kernel, grid, dim3(C2_NTHR), 0, s, x, x_range, (const _Float16 *)((const char *)w_packed + 16),
-                       (const float *)w_packed, bias, residual, y, out_range, Ci, Co, H, W, relu, tiles_w, tiles_h, nslots);
-    return check_launch("conv2d_fwd");
+    return mphip_conv2d_fwd_typed(x, MPHIP_DTYPE_F32, x_range, w_packed, bias, residual, MPHIP_DTYPE_F32, y, MPHIP_DTYPE_F32, out_range, N, Ci,
+                                  Co, H, W, relu, 3, workspace, workspace_bytes, stream);
 }

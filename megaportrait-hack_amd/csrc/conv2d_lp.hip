@@ -1,6 +1,8 @@
 // The half-precision forms of the 2-D 3x3 conv: the instantiations of conv2d_f16x3_tile.h over the model dtype of the maps (XDT, YDT) and
 // the product count (NP) that the fused 2-D blocks use in half and autocast runs, behind mphip_conv2d_fwd_typed / mphip_conv2d_cat_fwd_typed.
-// conv2d_f16x3.hip and conv2d_gn_f16x3.hip keep the fp32, three-product kernels; an all-fp32 three-product call is handed to their entries.
+// conv2d_f16x3.hip and conv2d_gn_f16x3.hip keep the fp32, three-product kernels.  This unit also holds conv2d_run, the host routine behind all
+// four entries (the fp32 entries are the typed ones with fp32 maps and three products): it knows the dtype rules, and hands an all-fp32
+// three-product call to the launchers of the other two units.
 //
 // One launch with one product computes
 //     y = narrow_Y( act( unscale * sum round_f16(w * s_w) * round_f16(x * s_x)  + bias + widen(residual) ) )
@@ -60,49 +62,120 @@ static bool lp_instantiated(bool cat, int x_dtype, int y_dtype, int np) {
     return x_dtype == MPHIP_DTYPE_F32 || y_dtype == MPHIP_DTYPE_F32;
 }
 
-// The dtype rules of both typed entries, before any HIP call.  np: the resolved product count.
-static int lp_check(const char *who, bool cat, int x_dtype, int residual_dtype, int y_dtype, int products, int &np) {
-    MPHIP_REQUIRE(lp_dtype_known(x_dtype), "%s: unknown x dtype %d", who, x_dtype);
-    MPHIP_REQUIRE(lp_dtype_known(residual_dtype), "%s: unknown residual dtype %d", who, residual_dtype);
-    MPHIP_REQUIRE(lp_dtype_known(y_dtype), "%s: unknown y dtype %d", who, y_dtype);
-    np = lp_products(products);
-    MPHIP_REQUIRE(np > 0, "%s: products = %d (3, 1, or 0: the calling thread's mphip_conv3d_set_half_products flag)", who, products);
+// The dtype and product rules of the typed entries -> what is wrong with a combination, or nullptr.  np: the resolved product count.
+static const char *lp_rule(bool cat, int x_dtype, int residual_dtype, int y_dtype, int products, int &np) {
     const int ds[3] = {x_dtype, residual_dtype, y_dtype};
     bool f16 = false, bf16 = false;
     for (int d : ds) {
+        if (!lp_dtype_known(d)) return "unknown x, residual or y dtype";
         f16 |= d == MPHIP_DTYPE_F16;
         bf16 |= d == MPHIP_DTYPE_BF16;
     }
-    MPHIP_REQUIRE(!(f16 && bf16), "%s: two different half dtypes in one call (x %d, residual %d, y %d)", who, x_dtype, residual_dtype, y_dtype);
-    MPHIP_REQUIRE(!cat || x_dtype == MPHIP_DTYPE_F32,
-                  "%s: a typed source (x_dtype %d): the two-source form reads fp32 sources, widen them with mphip_cast_to_f32_range", who,
-                  x_dtype);
-    MPHIP_REQUIRE(residual_dtype == MPHIP_DTYPE_F32 || residual_dtype == y_dtype, "%s: residual_dtype %d: fp32 or the dtype of y (%d)", who,
-                  residual_dtype, y_dtype);
-    MPHIP_REQUIRE(lp_instantiated(cat, x_dtype, y_dtype, np),
-                  "%s: no kernel for x dtype %d, y dtype %d and %d product(s) (mphip_conv2d_typed_supported)", who, x_dtype, y_dtype, np);
-    return MPHIP_OK;
+    np = lp_products(products);
+    if (np < 0) return "products must be 3, 1, or 0 (the calling thread's mphip_conv3d_set_half_products flag)";
+    if (f16 && bf16) return "two different half dtypes in one call";
+    if (cat && x_dtype != MPHIP_DTYPE_F32) return "a typed source: the two-source form reads fp32 sources, widen them with mphip_cast_to_f32_range";
+    if (residual_dtype != MPHIP_DTYPE_F32 && residual_dtype != y_dtype) return "residual_dtype must be fp32 or the dtype of y";
+    if (!lp_instantiated(cat, x_dtype, y_dtype, np)) return "no kernel for these dtypes and this product count (mphip_conv2d_typed_supported)";
+    return nullptr;
 }
 
 // [p, p + bytes) and [q, q + qbytes) share a byte
-static bool lp_overlap(const void *p, size_t bytes, const void *q, size_t qbytes) {
+static bool c2_overlap(const void *p, size_t bytes, const void *q, size_t qbytes) {
     const uintptr_t a = (uintptr_t)p, b = (uintptr_t)q;
     return q != nullptr && a < b + qbytes && b < a + bytes;
 }
 
-struct LpGrid {
-    dim3 grid;
-    int tiles_w, tiles_h;
-    unsigned nslots;
-};
-static bool lp_grid(int N, int Co, int H, int W, LpGrid &g) {
-    g.tiles_w = cdiv(W, C2_TW);
-    g.tiles_h = cdiv(H, C2_TH);
-    const long long tiles = (long long)N * g.tiles_h * g.tiles_w;
-    if (tiles >= (1ll << 31)) return false;
-    g.grid = dim3((unsigned)tiles, (unsigned)c2_cots(Co));
-    g.nslots = (unsigned)std::min<long long>(tiles * c2_cots(Co), (long long)RANGE_MAX_PARTS);
-    return true;
+void conv2d_lp_launch(const C2Call &c, const C2Grid &g) {
+    const _Float16 *slabs = (const _Float16 *)((const char *)c.w_packed + 16);
+    const int rt = c.residual && c.residual_dtype != MPHIP_DTYPE_F32 ? 1 : 0;
+    const C2CatArgs cat{c.aff1, (const float *)c.x2, c.aff2, c.x2_range, c.C2, c.relu1 ? 1 : 0, c.relu2 ? 1 : 0};
+#define LP_LAUNCH(XD, YD)                                                                                                                \
+    hipLaunchKernelGGL((conv2d_k3_lp_kernel<XD, YD, 1>), g.grid, dim3(C2_NTHR), 0, c.stream, (const dtype_t<XD> *)c.x1, c.x1_range, slabs, \
+                       (const float *)c.w_packed, c.bias, c.residual, rt, (dtype_t<YD> *)c.y, c.out_range, c.C1, c.Co, c.H, c.W, c.relu,   \
+                       g.tiles_w, g.tiles_h, g.nslots)
+#define LP_CAT_LAUNCH(YD)                                                                                                                \
+    hipLaunchKernelGGL((conv2d_k3_cat_lp_kernel<YD, 1>), g.grid, dim3(C2_NTHR), 0, c.stream, (const float *)c.x1, c.x1_range, cat, slabs,  \
+                       (const float *)c.w_packed, c.bias, c.residual, rt, (dtype_t<YD> *)c.y, c.out_range, c.C1, c.Co, c.H, c.W, c.relu,   \
+                       g.tiles_w, g.tiles_h, g.nslots)
+    if (c.cat) {
+        if (c.y_dtype == MPHIP_DTYPE_F32) LP_CAT_LAUNCH(MPHIP_DTYPE_F32);
+        else if (c.y_dtype == MPHIP_DTYPE_F16) LP_CAT_LAUNCH(MPHIP_DTYPE_F16);
+        else LP_CAT_LAUNCH(MPHIP_DTYPE_BF16);
+    } else if (c.y_dtype == MPHIP_DTYPE_F32) {
+        if (c.x_dtype == MPHIP_DTYPE_F32) LP_LAUNCH(MPHIP_DTYPE_F32, MPHIP_DTYPE_F32);
+        else if (c.x_dtype == MPHIP_DTYPE_F16) LP_LAUNCH(MPHIP_DTYPE_F16, MPHIP_DTYPE_F32);
+        else LP_LAUNCH(MPHIP_DTYPE_BF16, MPHIP_DTYPE_F32);
+    } else if (c.y_dtype == MPHIP_DTYPE_F16) {
+        LP_LAUNCH(MPHIP_DTYPE_F32, MPHIP_DTYPE_F16);
+    } else {
+        LP_LAUNCH(MPHIP_DTYPE_F32, MPHIP_DTYPE_BF16);
+    }
+#undef LP_LAUNCH
+#undef LP_CAT_LAUNCH
+}
+
+// The host side of every 2-D 3x3 conv entry.  The rules in the order they are checked, all before the first HIP call: dtypes and
+// products (lp_rule), pointers, the second source, the shape, alignment, tables, aliasing (MPHIP_EINVAL each), then the workspace
+// (MPHIP_EWORKSPACE).  Messages carry the called entry's name; a three-product call (all of its maps are fp32) is the fp32 entry's call
+// under whichever name it came in, and reports under that entry's name.
+int conv2d_run(C2Call c) {
+    int np = 0;
+    const char *why = lp_rule(c.cat, c.x_dtype, c.residual_dtype, c.y_dtype, c.products, np);
+    MPHIP_REQUIRE(!why, "%s: %s (x dtype %d, residual dtype %d, y dtype %d, products %d)", c.who, why, c.x_dtype, c.residual_dtype, c.y_dtype,
+                  c.products);
+    c.products = np;
+    const char *who = c.products == 3 ? (c.cat ? "conv2d_cat_fwd" : "conv2d_fwd") : c.who;
+    MPHIP_REQUIRE(c.x1 && c.w_packed && c.bias && c.y, "%s: null pointer", who);
+    MPHIP_REQUIRE(c.C2 >= 0 && (c.x2 != nullptr) == (c.C2 > 0), "%s: x2 and C2 = %d: a second source needs both, one source neither", who, c.C2);
+    MPHIP_REQUIRE(c.cat ? mphip_conv2d_cat_supported(c.N, c.C1, c.C2, c.Co, c.H, c.W) : mphip_conv2d_supported(c.N, c.C1, c.Co, c.H, c.W),
+                  "%s: unsupported shape N=%d C1=%d C2=%d Co=%d H=%d W=%d (C1 %% 16 == 0, C2 %% 16 == 0, Co %% 32 == 0, N, H, W >= 1, fewer than "
+                  "2^31 elements per tensor)", who, c.N, c.C1, c.C2, c.Co, c.H, c.W);
+    const size_t xb = lp_dtype_bytes(c.x_dtype), yb = lp_dtype_bytes(c.y_dtype), rb = lp_dtype_bytes(c.residual_dtype);
+    MPHIP_REQUIRE(((uintptr_t)c.w_packed & 15) == 0 && ((uintptr_t)c.x1 & (xb - 1)) == 0 && ((uintptr_t)c.x2 & 3) == 0 &&
+                      ((uintptr_t)c.y & (yb - 1)) == 0 && ((uintptr_t)c.residual & (rb - 1)) == 0,
+                  "%s: w_packed must be 16-byte aligned, the sources, y and residual aligned to their element size", who);
+    MPHIP_REQUIRE(((uintptr_t)c.aff1 & 3) == 0 && ((uintptr_t)c.aff2 & 3) == 0, "%s: the affine tables must be 4-byte aligned", who);
+    // the bound of a normalised source is not the maximum of its raw values: a scan of x would give the wrong operand scale
+    MPHIP_REQUIRE(!c.aff1 || c.x1_range, "%s: affine1 without x1_range (mphip_groupnorm_affine_table makes both)", who);
+    MPHIP_REQUIRE(!c.aff2 || (c.x2 && c.x2_range), "%s: affine2 without x2 / x2_range (mphip_groupnorm_affine_table makes both)", who);
+    const size_t hw = (size_t)c.H * c.W, n1 = (size_t)c.N * c.C1 * hw, n2 = (size_t)c.N * c.C2 * hw, ny = (size_t)c.N * c.Co * hw;
+    MPHIP_REQUIRE(!c2_overlap(c.y, ny * yb, c.x1, n1 * xb) && !c2_overlap(c.y, ny * yb, c.x2, n2 * sizeof(float)) &&
+                      !c2_overlap(c.y, ny * yb, c.residual, ny * rb),
+                  "%s: y must not alias a source or residual (a workgroup reads the halo of tiles other workgroups write)", who);
+    const bool scan1 = !c.x1_range, scan2 = c.x2 && !c.x2_range;
+    if (scan1 || scan2) {
+        const size_t need = c2_workspace_bytes((scan1 ? 1 : 0) + (scan2 ? 1 : 0));
+        if (!c.workspace || c.workspace_bytes < need) {
+            set_error("%s: workspace %zu bytes < required %zu", who, c.workspace_bytes, need);
+            return MPHIP_EWORKSPACE;
+        }
+        MPHIP_REQUIRE(((uintptr_t)c.workspace & 3) == 0, "%s: the workspace must be 4-byte aligned", who);
+        float *slot = (float *)c.workspace;
+        if (scan1) {
+            if (c.x_dtype == MPHIP_DTYPE_F32) {
+                conv2d_range_launch((const float *)c.x1, n1, slot, c.stream);
+            } else if (const int rc = cast_range_launch(c.x1, c.x_dtype, n1, nullptr, slot, c.stream)) {
+                return rc;   // (the descriptor of the widened values: widening is exact)
+            }
+            c.x1_range = slot;
+            slot += MPHIP_RANGE_FLOATS;
+        }
+        if (scan2) {
+            conv2d_range_launch((const float *)c.x2, n2, slot, c.stream);
+            c.x2_range = slot;
+        }
+    }
+    C2Grid g;
+    g.tiles_w = cdiv(c.W, C2_TW), g.tiles_h = cdiv(c.H, C2_TH);
+    const long long tiles = (long long)c.N * g.tiles_h * g.tiles_w;   // (N * H * W < 2^31 by the shape rule: they fit grid.x)
+    g.grid = dim3((unsigned)tiles, (unsigned)c2_cots(c.Co));
+    g.nslots = (unsigned)std::min<long long>(tiles * c2_cots(c.Co), (long long)RANGE_MAX_PARTS);
+    if (c.out_range) conv2d_out_range_init_launch(c.out_range, g.nslots, c.stream);
+    if (c.products == 1) conv2d_lp_launch(c, g);
+    else if (c.cat) conv2d_cat_launch(c, g);
+    else conv2d_plain_launch(c, g);
+    return check_launch(who);
 }
 
 }  // namespace mphip
@@ -110,70 +183,21 @@ static bool lp_grid(int N, int Co, int H, int W, LpGrid &g) {
 using namespace mphip;
 
 extern "C" int mphip_conv2d_typed_supported(int two_source, int x_dtype, int residual_dtype, int y_dtype, int products) {
-    if (!lp_dtype_known(x_dtype) || !lp_dtype_known(residual_dtype) || !lp_dtype_known(y_dtype)) return 0;
-    const int np = lp_products(products);
-    if (np < 0) return 0;
-    const bool f16 = x_dtype == MPHIP_DTYPE_F16 || residual_dtype == MPHIP_DTYPE_F16 || y_dtype == MPHIP_DTYPE_F16;
-    const bool bf16 = x_dtype == MPHIP_DTYPE_BF16 || residual_dtype == MPHIP_DTYPE_BF16 || y_dtype == MPHIP_DTYPE_BF16;
-    if (f16 && bf16) return 0;
-    if (residual_dtype != MPHIP_DTYPE_F32 && residual_dtype != y_dtype) return 0;
-    return lp_instantiated(two_source != 0, x_dtype, y_dtype, np) ? 1 : 0;
+    int np;
+    return lp_rule(two_source != 0, x_dtype, residual_dtype, y_dtype, products, np) ? 0 : 1;
 }
 
 extern "C" int mphip_conv2d_fwd_typed(const void *x, int x_dtype, const float *x_range, const void *w_packed, const float *bias,
                                       const void *residual, int residual_dtype, void *y, int y_dtype, float *out_range, int N, int Ci,
                                       int Co, int H, int W, int relu, int products, void *workspace, size_t workspace_bytes, void *stream) {
-    int np = 0;
-    if (const int rc = lp_check("conv2d_fwd_typed", false, x_dtype, residual_dtype, y_dtype, products, np)) return rc;
-    if (np == 3)   // (all fp32 by lp_check) the three-product kernel and every check of its entry
-        return mphip_conv2d_fwd((const float *)x, x_range, w_packed, bias, (const float *)residual, (float *)y, out_range, N, Ci, Co, H, W,
-                                relu, workspace, workspace_bytes, stream);
-    MPHIP_REQUIRE(x && w_packed && bias && y, "conv2d_fwd_typed: null pointer");
-    MPHIP_REQUIRE(c2_supported(N, Ci, Co, H, W),
-                  "conv2d_fwd_typed: unsupported shape N=%d Ci=%d Co=%d H=%d W=%d (Ci %% 16 == 0, Co %% 32 == 0, N, H, W >= 1, fewer than "
-                  "2^31 elements per tensor)", N, Ci, Co, H, W);
-    const size_t xa = lp_dtype_bytes(x_dtype) - 1, ya = lp_dtype_bytes(y_dtype) - 1, ra = lp_dtype_bytes(residual_dtype) - 1;
-    MPHIP_REQUIRE(((uintptr_t)w_packed & 15) == 0 && ((uintptr_t)x & xa) == 0 && ((uintptr_t)y & ya) == 0 && ((uintptr_t)residual & ra) == 0,
-                  "conv2d_fwd_typed: w_packed must be 16-byte aligned, x, y and residual aligned to their element size");
-    const size_t hw = (size_t)H * W, ybytes = (size_t)N * Co * hw * lp_dtype_bytes(y_dtype);
-    MPHIP_REQUIRE(!lp_overlap(y, ybytes, x, (size_t)N * Ci * hw * lp_dtype_bytes(x_dtype)) &&
-                      !lp_overlap(y, ybytes, residual, (size_t)N * Co * hw * lp_dtype_bytes(residual_dtype)),
-                  "conv2d_fwd_typed: y must not alias x or residual (a workgroup reads the halo of tiles other workgroups write)");
-    hipStream_t s = (hipStream_t)stream;
-    if (!x_range) {
-        const size_t need = (size_t)MPHIP_RANGE_FLOATS * sizeof(float);
-        if (!workspace || workspace_bytes < need) {
-            set_error("conv2d_fwd_typed: workspace %zu bytes < required %zu", workspace_bytes, need);
-            return MPHIP_EWORKSPACE;
-        }
-        MPHIP_REQUIRE(((uintptr_t)workspace & 3) == 0, "conv2d_fwd_typed: the workspace must be 4-byte aligned");
-        if (x_dtype == MPHIP_DTYPE_F32) {
-            conv2d_range_launch((const float *)x, (size_t)N * Ci * hw, (float *)workspace, s);
-        } else if (const int rc = cast_range_launch(x, x_dtype, (size_t)N * Ci * hw, nullptr, (float *)workspace, s)) {
-            return rc;   // (the descriptor of the widened values: widening is exact)
-        }
-        x_range = (const float *)workspace;
-    }
-    LpGrid g;
-    MPHIP_REQUIRE(lp_grid(N, Co, H, W, g), "conv2d_fwd_typed: the tiles do not fit a launch");
-    if (out_range) conv2d_out_range_init_launch(out_range, g.nslots, s);
-    const _Float16 *slabs = (const _Float16 *)((const char *)w_packed + 16);
-    const int rt = residual && residual_dtype != MPHIP_DTYPE_F32 ? 1 : 0;
-#define LP_LAUNCH(XD, YD)                                                                                                              \
-    hipLaunchKernelGGL((conv2d_k3_lp_kernel<XD, YD, 1>), g.grid, dim3(C2_NTHR), 0, s, (const dtype_t<XD> *)x, x_range, slabs,            \
-                       (const float *)w_packed, bias, residual, rt, (dtype_t<YD> *)y, out_range, Ci, Co, H, W, relu, g.tiles_w, g.tiles_h, \
-                       g.nslots)
-    if (y_dtype == MPHIP_DTYPE_F32) {
-        if (x_dtype == MPHIP_DTYPE_F32) LP_LAUNCH(MPHIP_DTYPE_F32, MPHIP_DTYPE_F32);
-        else if (x_dtype == MPHIP_DTYPE_F16) LP_LAUNCH(MPHIP_DTYPE_F16, MPHIP_DTYPE_F32);
-        else LP_LAUNCH(MPHIP_DTYPE_BF16, MPHIP_DTYPE_F32);
-    } else if (y_dtype == MPHIP_DTYPE_F16) {
-        LP_LAUNCH(MPHIP_DTYPE_F32, MPHIP_DTYPE_F16);
-    } else {
-        LP_LAUNCH(MPHIP_DTYPE_F32, MPHIP_DTYPE_BF16);
-    }
-#undef LP_LAUNCH
-    return check_launch("conv2d_fwd_typed");
+    C2Call c{};
+    c.who = "conv2d_fwd_typed";
+    c.x1 = x, c.x1_range = x_range, c.C1 = Ci;
+    c.x_dtype = x_dtype, c.residual_dtype = residual_dtype, c.y_dtype = y_dtype, c.products = products;
+    c.w_packed = w_packed, c.bias = bias, c.residual = residual, c.y = y, c.out_range = out_range;
+    c.N = N, c.Co = Co, c.H = H, c.W = W, c.relu = relu;
+    c.workspace = workspace, c.workspace_bytes = workspace_bytes, c.stream = (hipStream_t)stream;
+    return conv2d_run(c);
 }
 
 extern "C" int mphip_conv2d_cat_fwd_typed(const void *x1, int x_dtype, const float *affine1, int relu1, const float *x1_range, int C1,
@@ -181,62 +205,13 @@ extern "C" int mphip_conv2d_cat_fwd_typed(const void *x1, int x_dtype, const flo
                                           const void *w_packed, const float *bias, const void *residual, int residual_dtype, void *y,
                                           int y_dtype, float *out_range, int N, int Co, int H, int W, int relu, int products,
                                           void *workspace, size_t workspace_bytes, void *stream) {
-    int np = 0;
-    if (const int rc = lp_check("conv2d_cat_fwd_typed", true, x_dtype, residual_dtype, y_dtype, products, np)) return rc;
-    if (np == 3)
-        return mphip_conv2d_cat_fwd((const float *)x1, affine1, relu1, x1_range, C1, (const float *)x2, affine2, relu2, x2_range, C2,
-                                    w_packed, bias, (const float *)residual, (float *)y, out_range, N, Co, H, W, relu, workspace,
-                                    workspace_bytes, stream);
-    MPHIP_REQUIRE(x1 && w_packed && bias && y, "conv2d_cat_fwd_typed: null pointer");
-    MPHIP_REQUIRE(C2 >= 0 && (x2 != nullptr) == (C2 > 0), "conv2d_cat_fwd_typed: x2 and C2 = %d: a second source needs both, one source neither",
-                  C2);
-    MPHIP_REQUIRE(mphip_conv2d_cat_supported(N, C1, C2, Co, H, W),
-                  "conv2d_cat_fwd_typed: unsupported shape N=%d C1=%d C2=%d Co=%d H=%d W=%d (C1 %% 16 == 0, C2 %% 16 == 0, Co %% 32 == 0, N, H, "
-                  "W >= 1, fewer than 2^31 elements per tensor)", N, C1, C2, Co, H, W);
-    const size_t ya = lp_dtype_bytes(y_dtype) - 1, ra = lp_dtype_bytes(residual_dtype) - 1;
-    MPHIP_REQUIRE(((uintptr_t)w_packed & 15) == 0 && ((uintptr_t)x1 & 3) == 0 && ((uintptr_t)x2 & 3) == 0 && ((uintptr_t)y & ya) == 0 &&
-                      ((uintptr_t)residual & ra) == 0,
-                  "conv2d_cat_fwd_typed: w_packed must be 16-byte aligned, x1 and x2 4-byte aligned, y and residual aligned to their element size");
-    MPHIP_REQUIRE(((uintptr_t)affine1 & 3) == 0 && ((uintptr_t)affine2 & 3) == 0, "conv2d_cat_fwd_typed: the affine tables must be 4-byte aligned");
-    MPHIP_REQUIRE(!affine1 || x1_range, "conv2d_cat_fwd_typed: affine1 without x1_range (mphip_groupnorm_affine_table makes both)");
-    MPHIP_REQUIRE(!affine2 || (x2 && x2_range), "conv2d_cat_fwd_typed: affine2 without x2 / x2_range (mphip_groupnorm_affine_table makes both)");
-    const size_t hw = (size_t)H * W, ybytes = (size_t)N * Co * hw * lp_dtype_bytes(y_dtype);
-    MPHIP_REQUIRE(!lp_overlap(y, ybytes, x1, (size_t)N * C1 * hw * sizeof(float)) && !lp_overlap(y, ybytes, x2, (size_t)N * C2 * hw * sizeof(float)) &&
-                      !lp_overlap(y, ybytes, residual, (size_t)N * Co * hw * lp_dtype_bytes(residual_dtype)),
-                  "conv2d_cat_fwd_typed: y must not alias x1, x2 or residual (a workgroup reads the halo of tiles other workgroups write)");
-    hipStream_t s = (hipStream_t)stream;
-    const size_t one = (size_t)MPHIP_RANGE_FLOATS * sizeof(float);
-    const size_t need = ((x1_range ? 0 : 1) + (x2 && !x2_range ? 1 : 0)) * one;
-    if (need) {
-        if (!workspace || workspace_bytes < need) {
-            set_error("conv2d_cat_fwd_typed: workspace %zu bytes < required %zu", workspace_bytes, need);
-            return MPHIP_EWORKSPACE;
-        }
-        MPHIP_REQUIRE(((uintptr_t)workspace & 3) == 0, "conv2d_cat_fwd_typed: the workspace must be 4-byte aligned");
-        float *slot = (float *)workspace;
-        if (!x1_range) {
-            conv2d_range_launch((const float *)x1, (size_t)N * C1 * hw, slot, s);
-            x1_range = slot;
-            slot += MPHIP_RANGE_FLOATS;
-        }
-        if (x2 && !x2_range) {
-            conv2d_range_launch((const float *)x2, (size_t)N * C2 * hw, slot, s);
-            x2_range = slot;
-        }
-    }
-    LpGrid g;
-    MPHIP_REQUIRE(lp_grid(N, Co, H, W, g), "conv2d_cat_fwd_typed: the tiles do not fit a launch");
-    if (out_range) conv2d_out_range_init_launch(out_range, g.nslots, s);
-    const C2CatArgs cat{affine1, (const float *)x2, affine2, x2_range, C2, relu1 ? 1 : 0, relu2 ? 1 : 0};
-    const _Float16 *slabs = (const _Float16 *)((const char *)w_packed + 16);
-    const int rt = residual && residual_dtype != MPHIP_DTYPE_F32 ? 1 : 0;
-#define LP_LAUNCH(YD)                                                                                                                   \
-    hipLaunchKernelGGL((conv2d_k3_cat_lp_kernel<YD, 1>), g.grid, dim3(C2_NTHR), 0, s, (const float *)x1, x1_range, cat, slabs,            \
-                       (const float *)w_packed, bias, residual, rt, (dtype_t<YD> *)y, out_range, C1, Co, H, W, relu, g.tiles_w, g.tiles_h, \
-                       g.nslots)
-    if (y_dtype == MPHIP_DTYPE_F32) LP_LAUNCH(MPHIP_DTYPE_F32);
-    else if (y_dtype == MPHIP_DTYPE_F16) LP_LAUNCH(MPHIP_DTYPE_F16);
-    else LP_LAUNCH(MPHIP_DTYPE_BF16);
-#undef LP_LAUNCH
-    return check_launch("conv2d_cat_fwd_typed");
+    C2Call c{};
+    c.who = "conv2d_cat_fwd_typed", c.cat = true;
+    c.x1 = x1, c.aff1 = affine1, c.relu1 = relu1, c.x1_range = x1_range, c.C1 = C1;
+    c.x2 = x2, c.aff2 = affine2, c.relu2 = relu2, c.x2_range = x2_range, c.C2 = C2;
+    c.x_dtype = x_dtype, c.residual_dtype = residual_dtype, c.y_dtype = y_dtype, c.products = products;
+    c.w_packed = w_packed, c.bias = bias, c.residual = residual, c.y = y, c.out_range = out_range;
+    c.N = N, c.Co = Co, c.H = H, c.W = W, c.relu = relu;
+    c.workspace = workspace, c.workspace_bytes = workspace_bytes, c.stream = (hipStream_t)stream;
+    return conv2d_run(c);
 }

@@ -170,6 +170,40 @@ int conv2d_gn_f16x3_saturation(unsigned long long *count, int reset);
 // conv2d_lp.hip: the typed and one-product instantiations of both (mphip_conv2d_fwd_typed, mphip_conv2d_cat_fwd_typed), likewise
 int conv2d_lp_saturation(unsigned long long *count, int reset);
 
+// One call of the 2-D 3x3 conv, as its four C entries describe it to conv2d_run (conv2d_lp.hip).  Zero-initialised it is the plain fp32
+// form: the plain form is one source (C2 = 0, no tables), the fp32 entries are fp32 dtypes with three products.
+struct C2Call {
+    const char *who;        // the entry's name, for messages
+    bool cat;               // the two-source kernels (also with C2 == 0: they are kernels of their own); false: the plain ones
+    const void *x1, *x2;    // sources [N,C1,H,W] and [N,C2,H,W] or NULL; x1 in x_dtype (fp32 when cat), x2 fp32
+    const float *aff1, *aff2, *x1_range, *x2_range;
+    int relu1, relu2, C1, C2;
+    int x_dtype, residual_dtype, y_dtype;
+    int products;           // 3, 1, or 0 = the calling thread's policy flag; conv2d_run resolves it to 3 or 1 for the launchers
+    const void *w_packed;
+    const float *bias;
+    const void *residual;
+    void *y;
+    float *out_range;
+    int N, Co, H, W, relu;
+    void *workspace;
+    size_t workspace_bytes;
+    hipStream_t stream;
+};
+struct C2Grid {
+    dim3 grid;
+    int tiles_w, tiles_h;
+    unsigned nslots;        // partial maxima of out_range
+};
+// the workspace: one library-computed range descriptor per source that comes without one
+inline size_t c2_workspace_bytes(int descriptors) { return (size_t)descriptors * MPHIP_RANGE_FLOATS * sizeof(float); }
+// validate, carve the workspace, scan the ranges, size the grid, initialise out_range, launch: in this order, for every entry
+int conv2d_run(C2Call c);
+// each unit's launcher of its instantiations (c.products resolved, every range in place)
+void conv2d_plain_launch(const C2Call &c, const C2Grid &g);   // conv2d_f16x3.hip: conv2d_k3_f16x3_kernel
+void conv2d_cat_launch(const C2Call &c, const C2Grid &g);     // conv2d_gn_f16x3.hip: conv2d_k3_cat_f16x3_kernel
+void conv2d_lp_launch(const C2Call &c, const C2Grid &g);      // conv2d_lp.hip: the one-product kernels of both forms
+
 // api.hip: the calling thread's conv arithmetic policy (mphip_conv3d_set_half_products): true inside torch.autocast(float16) regions
 bool conv_half_products();
 

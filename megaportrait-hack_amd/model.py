@@ -774,7 +774,72 @@ def _is_bn2d(m, channels: int) -> bool:
             and m.running_mean is not None and m.running_var is not None)
 
 
-class ResBlock2DFused(nn.Module):
+class _FusedBlock2D(nn.Module):
+    """What ResBlock2DFused and ResBlockCustomFused share: adopting the children of an existing block, the fold cache, the decision
+    between the three paths of forward — the one-product path (half_precision=True), the native fp32 path, the original PyTorch
+    expression — and the conditions of the first two.  A subclass says what it stands in for (`matches`, _CHILDREN, _EXPECTED, _adopt), how
+    it folds (_fold_tensors, _fold), which calls it takes (_EVAL_ONLY, _CUDA_FLOAT_INPUT, _dtypes, _shape_ok: the [N,C,H,W] map fits) and what it
+    computes (_reference in PyTorch, _launch on the matrix cores)."""
+
+    _CHILDREN = ()               # the children taken over from the original block, by name
+    _EXPECTED = ""               # from_block's TypeError: what `matches` accepts
+    _EVAL_ONLY = False           # the native paths run in eval mode only
+    _CUDA_FLOAT_INPUT = False    # the fp32 path asks for a floating-point CUDA map itself (else ops refuses what it cannot run)
+
+    @classmethod
+    def from_block(cls, block: nn.Module, half_precision: bool = False):
+        if not cls.matches(block):
+            raise TypeError(f"{cls.__name__}.from_block: expected {cls._EXPECTED}, got {block}")
+        new = cls.__new__(cls)
+        nn.Module.__init__(new)
+        new._adopt(block)
+        for name in cls._CHILDREN:
+            setattr(new, name, getattr(block, name))
+        new.training = block.training   # (the children keep their own flags: they are the block's)
+        _set_half(new, half_precision)
+        return new
+
+    def _native_ok(self, x) -> bool:
+        if (self._EVAL_ONLY and self.training) or ag.needs_grad(self, x) or self._dtypes(False) != {torch.float32}:
+            return False
+        if not (isinstance(x, torch.Tensor) and x.dim() == 4 and x.numel() > 0):
+            return False
+        if self._CUDA_FLOAT_INPUT and not (x.is_cuda and x.is_floating_point()):
+            return False
+        return self._shape_ok(x)
+
+    def _folded(self):
+        """The subclass's packs (_fold), folded in fp32 torch ops (a half block: the fold of its fp32 twin); cached until a parameter or
+        a running buffer changes (their versions are the key)."""
+        ts = self._fold_tensors()
+        key = tuple((t.data_ptr(), t._version) for t in ts) + (str(ts[0].device), ops.weight_epoch())
+        hit = self.__dict__.get("_mphip_fold")
+        if hit is None or hit[0] != key or ops.repacking():
+            with torch.no_grad():
+                hit = (key, self._fold(torch.float32 if ts[0].dtype in _HALF else None))
+            self.__dict__["_mphip_fold"] = hit
+        return hit[1]
+
+    def _half_out(self, x):
+        """half_precision=True: the output dtype of the one-product path for this call (_half_mode), or None."""
+        if "_mphip_half" not in self.__dict__ or (self._EVAL_ONLY and self.training):
+            return None
+        dts = self._dtypes(True)
+        dt = _half_mode(self, x, dts.pop()) if len(dts) == 1 else None
+        return dt if dt is not None and not ag.needs_grad(self, x) and self._shape_ok(x) else None
+
+    def forward(self, x):
+        half = self._half_out(x)
+        if half is not None:
+            packs = self._folded()
+            with ops.half_products(True):
+                return self._launch(x, packs, half, 0)
+        if not self._native_ok(x):
+            return self._reference(x)
+        return self._launch(x, self._folded(), None, None)
+
+
+class ResBlock2DFused(_FusedBlock2D):
     """G2d's ResBlock2D (model.py:600-640, `downsample` off) with an opt-in inference path on the matrix cores: BatchNorm folded into
     the convs, each 3x3 conv one launch of csrc/conv2d_f16x3.hip (f16x3 arithmetic: fp32-class accuracy) with bias, ReLU and the
     residual add in its epilogue.  The children are the original block's own `conv1, bn1, conv2, bn2, shortcut` — the same Parameter
@@ -793,6 +858,11 @@ class ResBlock2DFused(nn.Module):
     under ops.half_products(True) outside the region.  A .half() / .bfloat16() block folds its BatchNorms in fp32 from the widened
     parameters, runs one product, reads input and residual and writes the output in the model dtype (y1 stays fp32): bitwise its fp32
     twin under ops.half_products(True), rounded once.  Everything else takes the paths above."""
+
+    _CHILDREN = ("conv1", "bn1", "conv2", "bn2", "shortcut")
+    _EXPECTED = ("a ResBlock2D without downsampling (3x3 stride-1 convs with bias, BatchNorm2d with running statistics, Identity or "
+                 "Conv2d 1x1 + BatchNorm2d shortcut)")
+    _EVAL_ONLY = True
 
     def __init__(self, in_channels: int, out_channels: int):
         super().__init__()
@@ -823,94 +893,77 @@ class ResBlock2DFused(nn.Module):
         return (isinstance(sc, nn.Sequential) and len(sc) == 2 and _is_conv2d(sc[0], 1) and sc[0].in_channels == conv1.in_channels
                 and sc[0].out_channels == co and _is_bn2d(sc[1], co))
 
-    @classmethod
-    def from_block(cls, block: nn.Module, half_precision: bool = False) -> "ResBlock2DFused":
-        if not cls.matches(block):
-            raise TypeError(f"ResBlock2DFused.from_block: expected a ResBlock2D without downsampling (3x3 stride-1 convs with bias, "
-                            f"BatchNorm2d with running statistics, Identity or Conv2d 1x1 + BatchNorm2d shortcut), got {block}")
-        new = cls.__new__(cls)
-        nn.Module.__init__(new)
-        new.downsample = False
-        for name in ("conv1", "bn1", "conv2", "bn2", "shortcut"):
-            setattr(new, name, getattr(block, name))
-        new.training = block.training   # (the children keep their own flags: they are the block's)
-        _set_half(new, half_precision)
-        return new
+    def _adopt(self, block):
+        self.downsample = False
 
-    def _native_ok(self, x) -> bool:
-        if self.training or ag.needs_grad(self, x) or self.conv1.weight.dtype != torch.float32:
-            return False
-        if not (isinstance(x, torch.Tensor) and x.dim() == 4 and x.shape[1] == self.conv1.in_channels and x.numel() > 0):
-            return False
-        n, ci, h, w = x.shape
-        co = self.conv1.out_channels
-        return ops.conv2d_supported(n, ci, co, h, w) and ops.conv2d_supported(n, co, co, h, w)
+    def _shape_ok(self, x) -> bool:
+        (n, ci, h, w), co = x.shape, self.conv1.out_channels
+        return ci == self.conv1.in_channels and ops.conv2d_supported(n, ci, co, h, w) and ops.conv2d_supported(n, co, co, h, w)
 
-    def _folded(self):
-        """(conv1', conv2', shortcut' or None): BatchNorm folded in fp32 torch ops and packed; cached until a parameter or a running
-        buffer changes (their versions are the key)."""
-        mods = [self.conv1, self.bn1, self.conv2, self.bn2] + (list(self.shortcut) if isinstance(self.shortcut, nn.Sequential) else [])
-        ts = [t for m in mods for t in ((m.weight, m.bias) + ((m.running_mean, m.running_var) if isinstance(m, nn.BatchNorm2d) else ()))]
-        key = tuple((t.data_ptr(), t._version) for t in ts) + (str(ts[0].device), ops.weight_epoch())
-        hit = self.__dict__.get("_mphip_fold")
-        if hit is None or hit[0] != key or ops.repacking():
-            wide = torch.float32 if ts[0].dtype in _HALF else None   # a half block: the fold of its fp32 twin
-            with torch.no_grad():
-                p1 = ops.PackedConv2d(*fold_batchnorm(self.conv1, self.bn1, wide))
-                p2 = ops.PackedConv2d(*fold_batchnorm(self.conv2, self.bn2, wide))
-                ps = None
-                if len(mods) > 4:
-                    ws, bs = fold_batchnorm(mods[4], mods[5], wide)
-                    ps = ops.PackedConv(ws.view(ws.shape[0], ws.shape[1], 1, 1, 1), bs)
-            hit = (key, (p1, p2, ps))
-            self.__dict__["_mphip_fold"] = hit
-        return hit[1]
+    def _dtypes(self, half_path: bool):
+        dt = self.conv1.weight.dtype   # (what the paths look at: conv1 alone, but every parameter and buffer of a half block)
+        return {t.dtype for t in self.state_dict().values() if t.is_floating_point()} if half_path and dt in _HALF else {dt}
 
-    def _half_out(self, x):
-        """half_precision=True: the output dtype of the one-product path for this call (_half_mode), or None."""
-        if "_mphip_half" not in self.__dict__ or self.training:
-            return None
-        dt = _half_mode(self, x, self.conv1.weight.dtype)
-        if dt is None or x.shape[1] != self.conv1.in_channels or ag.needs_grad(self, x):
-            return None
-        if self.conv1.weight.dtype in _HALF and any(t.dtype != dt for t in self.state_dict().values() if t.is_floating_point()):
-            return None
-        n, ci, h, w = x.shape
-        co = self.conv1.out_channels
-        return dt if ops.conv2d_supported(n, ci, co, h, w) and ops.conv2d_supported(n, co, co, h, w) else None
+    def _fold_pairs(self):
+        return [(self.conv1, self.bn1), (self.conv2, self.bn2)] + ([tuple(self.shortcut)] if isinstance(self.shortcut, nn.Sequential) else [])
 
-    def _forward_half(self, x, out_dtype):
-        if x.dtype in _HALF and x.dtype != out_dtype:   # (a bf16 map inside a float16 region: one half dtype per launch)
+    def _fold_tensors(self):
+        return [t for conv, bn in self._fold_pairs() for t in (conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var)]
+
+    def _fold(self, wide):
+        """(conv1', conv2', shortcut' or None): BatchNorm folded and packed."""
+        pairs = self._fold_pairs()
+        p1, p2 = (ops.PackedConv2d(*fold_batchnorm(conv, bn, wide)) for conv, bn in pairs[:2])
+        ps = None
+        if len(pairs) > 2:
+            ws, bs = fold_batchnorm(*pairs[2], wide)
+            ps = ops.PackedConv(ws.view(ws.shape[0], ws.shape[1], 1, 1, 1), bs)
+        return p1, p2, ps
+
+    def _reference(self, x):
+        y = F.relu(self.bn1(self.conv1(x)))
+        y = self.bn2(self.conv2(y))
+        return F.relu(y + self.shortcut(x))
+
+    def _launch(self, x, packs, out_dtype, products):
+        """Both 3x3 launches and the 1x1 shortcut.  products None: the fp32 path (a half input is widened, the fp32 entry); 0: the
+        one-product path, which reads x in its own dtype and writes out_dtype."""
+        p1, p2, ps = packs
+        half = products is not None
+        if not half:
+            x = _f32(x)
+        elif x.dtype in _HALF and x.dtype != out_dtype:   # (a bf16 map inside a float16 region: one half dtype per launch)
             x = x.float()
         xc = x.contiguous()   # (the kernels read NCHW: a channels_last map is copied once)
-        p1, p2, ps = self._folded()
-        with ops.half_products(True):
-            if ps is not None:   # the 1x1 shortcut reads fp32: one widening pass, which also delivers the descriptor conv1 needs
-                xc = ops.cast_to_f32_range(xc)
-                n, c, h, w = xc.shape
-                idt = ops.conv3d(xc.reshape(n, c, 1, h, w), ps, x_range=ops.current_range(xc)).reshape(n, ps.co, h, w)
-            else:
-                idt = xc
-            y1 = ops.conv2d(xc, p1, relu=True, want_range=True, products=0)
-            return ops.conv2d(y1, p2, residual=idt, relu=True, want_range=True, out_dtype=out_dtype, products=0)
+        if half and ps is not None:   # the 1x1 shortcut reads fp32: one widening pass, which also delivers the descriptor conv1 needs
+            xc = ops.cast_to_f32_range(xc)
 
-    def forward(self, x):
-        half = self._half_out(x)
-        if half is not None:
-            return self._forward_half(x, half)
-        if not self._native_ok(x):
-            y = F.relu(self.bn1(self.conv1(x)))
-            y = self.bn2(self.conv2(y))
-            return F.relu(y + self.shortcut(x))
-        xc = _f32(x).contiguous()   # (the kernels read NCHW: a channels_last map is copied once)
-        p1, p2, ps = self._folded()
-        y1 = ops.conv2d(xc, p1, relu=True, want_range=True)
-        if ps is not None:
+        def shortcut():
+            if ps is None:
+                return xc
             n, c, h, w = xc.shape
-            idt = ops.conv3d(xc.reshape(n, c, 1, h, w), ps, x_range=ops.current_range(xc)).reshape(n, ps.co, h, w)
-        else:
-            idt = xc
-        return ops.conv2d(y1, p2, residual=idt, relu=True, want_range=True)
+            return ops.conv3d(xc.reshape(n, c, 1, h, w), ps, x_range=ops.current_range(xc)).reshape(n, ps.co, h, w)
+
+        # (the shortcut is launched before conv1 on the one-product path and after it on the fp32 path)
+        idt = shortcut() if half else None
+        y1 = ops.conv2d(xc, p1, relu=True, want_range=True, products=products)
+        if not half:
+            idt = shortcut()
+        return ops.conv2d(y1, p2, residual=idt, relu=True, want_range=True, out_dtype=out_dtype, products=products)
+
+
+def _swap_slot(cls, cur, enable: bool, half_precision: bool):
+    """One slot of native_g2d_body / native_eapp_trunk -> (the module the slot holds now, whether anything changed): a matching block
+    becomes a `cls` over the same children, a fused one takes the keyword's value, or (enable off) the very object it replaced comes back."""
+    if enable and isinstance(cur, cls):
+        return cur, _set_half(cur, half_precision)
+    if enable and cls.matches(cur):
+        new = cls.from_block(cur, half_precision)
+        new.__dict__["_replaced"] = cur   # (not a registered child: the module tree and the state-dict keys stay as they were)
+        return new, True
+    if not enable and isinstance(cur, cls) and "_replaced" in cur.__dict__:
+        return cur.__dict__.pop("_replaced"), True
+    return cur, False
 
 
 _G2D_BODY_SLOTS = (("upsample1", 1), ("upsample2", 1), ("upsample3", 1))
@@ -927,17 +980,10 @@ def native_g2d_body(g2d: nn.Module, enable: bool = True, half_precision: bool = 
         if not isinstance(seq, nn.Sequential):
             continue
         for i in (range(len(seq)) if only is None else [only] if len(seq) > only else []):
-            cur = seq[i]
-            if enable and isinstance(cur, ResBlock2DFused):
-                changed |= _set_half(cur, half_precision)
-            elif enable and ResBlock2DFused.matches(cur):
-                new = ResBlock2DFused.from_block(cur, half_precision)
-                new.__dict__["_replaced"] = cur   # (not a registered child: the module tree and the state-dict keys stay as they were)
+            new, did = _swap_slot(ResBlock2DFused, seq[i], enable, half_precision)
+            if new is not seq[i]:
                 seq[i] = new
-                changed = True
-            elif not enable and isinstance(cur, ResBlock2DFused) and "_replaced" in cur.__dict__:
-                seq[i] = cur.__dict__.pop("_replaced")
-                changed = True
+            changed |= did
     return changed
 
 
@@ -957,7 +1003,7 @@ def fold_resblock_custom(conv_res: nn.Module, conv_ws: nn.Module, conv: nn.Modul
     return (w_ws, cast(conv_ws.bias).contiguous()), (w_cat, (cast(conv.bias) + cast(conv_res.bias)).contiguous())
 
 
-class ResBlockCustomFused(nn.Module):
+class ResBlockCustomFused(_FusedBlock2D):
     """Eapp's 2-D ResBlock_Custom (model.py:88-130)
         out = conv(relu(GN32(conv_ws(relu(GN32(x)))))) + conv_res(x)          GN32 = F.group_norm(., 32), no parameters
     with an opt-in path on the matrix cores: two launches of csrc/conv2d_gn_f16x3.hip (f16x3 arithmetic: fp32-class accuracy), each
@@ -975,6 +1021,10 @@ class ResBlockCustomFused(nn.Module):
     float16; a .half() / .bfloat16() block folds its weights in fp32 from the widened parameters, runs one product and writes the
     model dtype.  A typed input is widened once (ops.cast_to_f32_range: the pass also delivers the descriptor of x the second launch
     needs); GroupNorm statistics and tables are taken on fp32 maps by their existing kernels, and `t` stays fp32."""
+
+    _CHILDREN = ("conv_res", "conv_ws", "conv")
+    _EXPECTED = "a 2-D ResBlock_Custom (conv_res, conv_ws (Conv2d_WS), conv: 3x3 stride-1 padding-1 convs with bias)"
+    _CUDA_FLOAT_INPUT = True
 
     def __init__(self, dimension: int, in_channels: int, out_channels: int):
         super().__init__()
@@ -998,78 +1048,40 @@ class ResBlockCustomFused(nn.Module):
         ci, co = res.in_channels, res.out_channels
         return (ws.in_channels, ws.out_channels, conv.in_channels, conv.out_channels) == (ci, co, co, co)
 
-    @classmethod
-    def from_block(cls, block: nn.Module, half_precision: bool = False) -> "ResBlockCustomFused":
-        if not cls.matches(block):
-            raise TypeError(f"ResBlockCustomFused.from_block: expected a 2-D ResBlock_Custom (conv_res, conv_ws (Conv2d_WS), conv: 3x3 "
-                            f"stride-1 padding-1 convs with bias), got {block}")
-        new = cls.__new__(cls)
-        nn.Module.__init__(new)
-        new.dimension, new.in_channels, new.out_channels = 2, block.conv_res.in_channels, block.conv_res.out_channels
-        for name in ("conv_res", "conv_ws", "conv"):
-            setattr(new, name, getattr(block, name))
-        new.training = block.training
-        _set_half(new, half_precision)
-        return new
+    def _adopt(self, block):
+        self.dimension, self.in_channels, self.out_channels = 2, block.conv_res.in_channels, block.conv_res.out_channels
 
-    def _native_ok(self, x) -> bool:
-        if ag.needs_grad(self, x) or any(p.dtype != torch.float32 for p in self.parameters()):
-            return False
-        if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dim() == 4 and x.shape[1] == self.in_channels and x.numel() > 0
-                and x.is_floating_point()):
-            return False
-        n, ci, h, w = x.shape
-        co = self.out_channels
-        return ops.conv2d_cat_supported(n, ci, 0, co, h, w) and ops.conv2d_cat_supported(n, co, ci, co, h, w)
+    def _shape_ok(self, x) -> bool:
+        (n, ci, h, w), co = x.shape, self.out_channels
+        return ci == self.in_channels and ops.conv2d_cat_supported(n, ci, 0, co, h, w) and ops.conv2d_cat_supported(n, co, ci, co, h, w)
 
-    def _folded(self):
-        """(conv_ws', [conv | conv_res]) packed; cached until a parameter changes (their versions are the key)."""
-        ts = [t for m in (self.conv_res, self.conv_ws, self.conv) for t in (m.weight, m.bias)]
-        key = tuple((t.data_ptr(), t._version) for t in ts) + (str(ts[0].device), ops.weight_epoch())
-        hit = self.__dict__.get("_mphip_fold")
-        if hit is None or hit[0] != key or ops.repacking():
-            with torch.no_grad():
-                ws, cat = fold_resblock_custom(self.conv_res, self.conv_ws, self.conv, torch.float32 if ts[0].dtype in _HALF else None)
-                hit = (key, (ops.PackedConv2d(*ws), ops.PackedConv2d(*cat)))
-            self.__dict__["_mphip_fold"] = hit
-        return hit[1]
+    def _dtypes(self, half_path: bool):
+        return {p.dtype for p in self.parameters()}
 
-    def _half_out(self, x):
-        """half_precision=True: the output dtype of the one-product path for this call (_half_mode), or None."""
-        if "_mphip_half" not in self.__dict__:
-            return None
-        dts = {p.dtype for p in self.parameters()}
-        dt = _half_mode(self, x, dts.pop()) if len(dts) == 1 else None
-        if dt is None or x.shape[1] != self.in_channels or ag.needs_grad(self, x):
-            return None
-        n, ci, h, w = x.shape
-        co = self.out_channels
-        return dt if ops.conv2d_cat_supported(n, ci, 0, co, h, w) and ops.conv2d_cat_supported(n, co, ci, co, h, w) else None
+    def _fold_tensors(self):
+        return [t for m in (self.conv_res, self.conv_ws, self.conv) for t in (m.weight, m.bias)]
 
-    def _forward_half(self, x, out_dtype):
-        xc = ops.cast_to_f32_range(x.contiguous())   # (an fp32 map is returned as it is; NCHW: a channels_last map is copied once)
-        p_ws, p_cat = self._folded()
-        with ops.half_products(True):
-            tab, rng = ops.gn_relu_table2d(xc)
-            t = ops.conv2d_cat(xc, p_ws, affine1=tab, relu1=True, x1_range=rng, products=0)
-            tab, rng = ops.gn_relu_table2d(t)
-            return ops.conv2d_cat(t, p_cat, x2=xc, affine1=tab, relu1=True, x1_range=rng, want_range=True, out_dtype=out_dtype, products=0)
+    def _fold(self, wide):
+        """(conv_ws', [conv | conv_res]) packed."""
+        ws, cat = fold_resblock_custom(self.conv_res, self.conv_ws, self.conv, wide)
+        return ops.PackedConv2d(*ws), ops.PackedConv2d(*cat)
 
-    def forward(self, x):
-        half = self._half_out(x)
-        if half is not None:
-            return self._forward_half(x, half)
-        if not self._native_ok(x):
-            skip = self.conv_res(x)
-            y = self.conv_ws(F.relu(F.group_norm(x, 32)))
-            y = self.conv(F.relu(F.group_norm(y, 32)))
-            return y + skip
-        xc = _f32(x).contiguous()   # (the kernels read NCHW: a channels_last map is copied once)
-        p_ws, p_cat = self._folded()
+    def _reference(self, x):
+        skip = self.conv_res(x)
+        y = self.conv_ws(F.relu(F.group_norm(x, 32)))
+        y = self.conv(F.relu(F.group_norm(y, 32)))
+        return y + skip
+
+    def _launch(self, x, packs, out_dtype, products):
+        """Both launches, with the GroupNorm tables they stage through.  products None: the fp32 path; 0: the one-product path, whose
+        typed input is widened by the pass that also delivers its descriptor."""
+        p_ws, p_cat = packs
+        # (NCHW: a channels_last map is copied once; an fp32 map is returned as it is by either)
+        xc = _f32(x).contiguous() if products is None else ops.cast_to_f32_range(x.contiguous())
         tab, rng = ops.gn_relu_table2d(xc)
-        t = ops.conv2d_cat(xc, p_ws, affine1=tab, relu1=True, x1_range=rng)
+        t = ops.conv2d_cat(xc, p_ws, affine1=tab, relu1=True, x1_range=rng, products=products)
         tab, rng = ops.gn_relu_table2d(t)
-        return ops.conv2d_cat(t, p_cat, x2=xc, affine1=tab, relu1=True, x1_range=rng, want_range=True)
+        return ops.conv2d_cat(t, p_cat, x2=xc, affine1=tab, relu1=True, x1_range=rng, want_range=True, out_dtype=out_dtype, products=products)
 
 
 _EAPP_TRUNK_SLOTS = ("resblock_128", "resblock_256", "resblock_512")
@@ -1083,16 +1095,10 @@ def native_eapp_trunk(eapp: nn.Module, enable: bool = True, half_precision: bool
     changed = False
     for name in _EAPP_TRUNK_SLOTS:
         cur = getattr(eapp, name, None)
-        if enable and isinstance(cur, ResBlockCustomFused):
-            changed |= _set_half(cur, half_precision)
-        elif enable and ResBlockCustomFused.matches(cur):
-            new = ResBlockCustomFused.from_block(cur, half_precision)
-            new.__dict__["_replaced"] = cur   # (not a registered child: the module tree and the state-dict keys stay as they were)
+        new, did = _swap_slot(ResBlockCustomFused, cur, enable, half_precision)
+        if new is not cur:
             setattr(eapp, name, new)
-            changed = True
-        elif not enable and isinstance(cur, ResBlockCustomFused) and "_replaced" in cur.__dict__:
-            setattr(eapp, name, cur.__dict__.pop("_replaced"))
-            changed = True
+        changed |= did
     return changed
 
 

@@ -1238,6 +1238,11 @@ def _conv2d_products(products: Optional[int], who: str) -> int:
     return 3 if products is None else int(products)
 
 
+def _conv2d_typed(out_dtype, products, *sources) -> bool:
+    """Does a call go to the typed entry?  Only with one of the two keywords or a half source: a plain fp32 call keeps the fp32 entry."""
+    return out_dtype is not None or products is not None or any(isinstance(t, torch.Tensor) and t.dtype != torch.float32 for t in sources)
+
+
 def conv2d_typed_supported(two_source: bool, x_dtype: torch.dtype, residual_dtype: torch.dtype, y_dtype: torch.dtype, products: int) -> bool:
     """Is this combination of map dtypes and product count (3, 1, or 0: the thread's current policy) built (mphip_conv2d_typed_supported)?"""
     return bool(_lib.load().mphip_conv2d_typed_supported(int(bool(two_source)), dtype_code(x_dtype), dtype_code(residual_dtype),
@@ -1254,34 +1259,48 @@ def conv2d(x: torch.Tensor, pack: PackedConv2d, residual: Optional[torch.Tensor]
     fp32 value rounded once, the descriptor then is that of the rounded values), the residual is fp32 or in out_dtype.  products: 3 (the
     default), 1 = one f16 product per multiply (the autocast arithmetic), 0 = follow ops.half_products.  With neither keyword and an fp32
     x this is the fp32 entry, whatever the policy flag says.  Not every combination is built (conv2d_typed_supported)."""
-    typed = out_dtype is not None or products is not None or (isinstance(x, torch.Tensor) and x.dtype != torch.float32)
+    typed = _conv2d_typed(out_dtype, products, x)
     x = _req_typed(x, "x") if typed else _req(x, "x")
     if x.dim() != 4 or x.shape[1] != pack.ci:
         raise RuntimeError(f"conv2d: input {tuple(x.shape)} does not match Ci={pack.ci}")
     n, ci, h, w = x.shape
-    lib = _lib.load()
-    if not lib.mphip_conv2d_supported(n, ci, pack.co, h, w):
+    if not _lib.load().mphip_conv2d_supported(n, ci, pack.co, h, w):
         raise RuntimeError(f"conv2d: unsupported shape N={n} Ci={ci} Co={pack.co} H={h} W={w} (there is no fallback)")
+    xr = x_range if x_range is not None else current_range(x)   # None: the library scans x
+    return _conv2d_launch("conv2d", typed, pack, x, None, xr, False, None, None, None, False, residual, relu, want_range, out_dtype, products)
+
+
+def _conv2d_launch(who, typed, pack, x1, aff1, r1, relu1, x2, aff2, r2, relu2, residual, relu, want_range, out_dtype, products):
+    """What ops.conv2d (who = "conv2d": the plain kernels) and ops.conv2d_cat share once their sources are checked and the descriptors r1 /
+    r2 chosen: the residual check, the workspace, y and out_range, and the call of the fp32 or (`typed`) the typed entry."""
+    cat = who == "conv2d_cat"
+    lib = _lib.load()
+    n, c1, h, w = x1.shape
+    c2 = 0 if x2 is None else int(x2.shape[1])
     if residual is not None:
         residual = _req_typed(residual, "residual") if typed else _req(residual, "residual")
         if tuple(residual.shape) != (n, pack.co, h, w):
-            raise RuntimeError(f"conv2d: residual {tuple(residual.shape)} does not match the output {(n, pack.co, h, w)}")
-    xr = x_range if x_range is not None else current_range(x)   # None: the library scans x
-    ws_bytes = lib.mphip_conv2d_workspace_bytes(n, ci, pack.co, h, w)
-    ws = torch.empty((ws_bytes + 3) // 4, dtype=torch.float32, device=x.device) if xr is None else None
+            raise RuntimeError(f"{who}: residual {tuple(residual.shape)} does not match the output {(n, pack.co, h, w)}")
+    ws_bytes = 0
+    if r1 is None or (x2 is not None and r2 is None):   # a source to scan
+        ws_bytes = lib.mphip_conv2d_cat_workspace_bytes(n, c1, c2, pack.co, h, w) if cat else lib.mphip_conv2d_workspace_bytes(n, c1, pack.co, h, w)
+    ws = torch.empty((ws_bytes + 3) // 4, dtype=torch.float32, device=x1.device) if ws_bytes else None
     ydt = torch.float32 if out_dtype is None else out_dtype
-    y = torch.empty((n, pack.co, h, w), dtype=ydt, device=x.device)
-    out_range = new_range(x.device) if want_range else None
-    if not typed:
-        _lib.check(lib.mphip_conv2d_fwd(_ptr(x), _ptr(xr), _ptr(pack.packed()), _ptr(pack.bias), _ptr(residual), _ptr(y), _ptr(out_range),
-                                        n, ci, pack.co, h, w, int(bool(relu)), _ptr(ws), ws_bytes if ws is not None else 0, _stream()),
-                   "mphip_conv2d_fwd")
-        return tag_range(y, out_range)
+    y = torch.empty((n, pack.co, h, w), dtype=ydt, device=x1.device)
+    out_range = new_range(x1.device) if want_range else None
+    # the entry's arguments in its order: a typed entry takes a dtype code after x1, residual and y, and the product count after relu
     rdt = torch.float32 if residual is None else residual.dtype
-    _lib.check(lib.mphip_conv2d_fwd_typed(_ptr(x), dtype_code(x.dtype), _ptr(xr), _ptr(pack.packed()), _ptr(pack.bias), _ptr(residual),
-                                          dtype_code(rdt), _ptr(y), dtype_code(ydt), _ptr(out_range), n, ci, pack.co, h, w,
-                                          int(bool(relu)), _conv2d_products(products, "conv2d"), _ptr(ws),
-                                          ws_bytes if ws is not None else 0, _stream()), "mphip_conv2d_fwd_typed")
+    xdt, rdt, ydt, np_ = [(v,) if typed else () for v in (dtype_code(x1.dtype), dtype_code(rdt), dtype_code(ydt), _conv2d_products(products, who))]
+    if cat:
+        sources = (_ptr(x1), *xdt, _ptr(aff1), int(bool(relu1)), _ptr(r1), c1, _ptr(x2), _ptr(aff2), int(bool(relu2)), _ptr(r2), c2)
+        shape = (n, pack.co, h, w)
+    else:
+        sources = (_ptr(x1), *xdt, _ptr(r1))
+        shape = (n, c1, pack.co, h, w)
+    args = (*sources, _ptr(pack.packed()), _ptr(pack.bias), _ptr(residual), *rdt, _ptr(y), *ydt, _ptr(out_range), *shape, int(bool(relu)), *np_,
+            _ptr(ws), ws_bytes, _stream())
+    entry = f"mphip_{who}_fwd" + ("_typed" if typed else "")
+    _lib.check(getattr(lib, entry)(*args), entry)
     return tag_range(y, out_range)
 
 
@@ -1324,7 +1343,7 @@ def conv2d_cat(x1: torch.Tensor, pack: PackedConv2d, x2: Optional[torch.Tensor] 
     library scans it.  Without x2 and tables: the bits of ops.conv2d.
     out_dtype / products (mphip_conv2d_cat_fwd_typed): as in ops.conv2d; the sources stay fp32 (a typed one is refused by the library:
     widen it once with ops.cast_to_f32_range, which also delivers its descriptor)."""
-    typed = out_dtype is not None or products is not None or any(isinstance(t, torch.Tensor) and t.dtype != torch.float32 for t in (x1, x2))
+    typed = _conv2d_typed(out_dtype, products, x1, x2)
     if typed and isinstance(x2, torch.Tensor) and isinstance(x1, torch.Tensor) and x2.dtype != x1.dtype:
         raise RuntimeError(f"conv2d_cat: x1 is {x1.dtype} and x2 {x2.dtype}: both sources are fp32")
     x1 = _req_typed(x1, "x1") if typed else _req(x1, "x1")
@@ -1346,32 +1365,10 @@ def conv2d_cat(x1: torch.Tensor, pack: PackedConv2d, x2: Optional[torch.Tensor] 
     for name, tab, c in (("affine1", affine1, c1), ("affine2", affine2, c2)):
         if tab is not None and tuple(tab.shape) != (n, c, 2):
             raise RuntimeError(f"conv2d_cat: {name} {tuple(tab.shape)} is not the [{n},{c},2] table of its source")
-    if residual is not None:
-        residual = _req_typed(residual, "residual") if typed else _req(residual, "residual")
-        if tuple(residual.shape) != (n, pack.co, h, w):
-            raise RuntimeError(f"conv2d_cat: residual {tuple(residual.shape)} does not match the output {(n, pack.co, h, w)}")
-    lib = _lib.load()
     # (a table's source keeps the caller's descriptor or none: the one tagged on x_i describes the raw values, and the entry refuses none)
     r1 = x1_range if (x1_range is not None or affine1 is not None) else current_range(x1)
     r2 = x2_range if (x2_range is not None or affine2 is not None or x2 is None) else current_range(x2)
-    scan = r1 is None or (x2 is not None and r2 is None)
-    ws_bytes = lib.mphip_conv2d_cat_workspace_bytes(n, c1, c2, pack.co, h, w) if scan else 0
-    ws = torch.empty((ws_bytes + 3) // 4, dtype=torch.float32, device=x1.device) if ws_bytes else None
-    ydt = torch.float32 if out_dtype is None else out_dtype
-    y = torch.empty((n, pack.co, h, w), dtype=ydt, device=x1.device)
-    out_range = new_range(x1.device) if want_range else None
-    if typed:
-        rdt = torch.float32 if residual is None else residual.dtype
-        _lib.check(lib.mphip_conv2d_cat_fwd_typed(_ptr(x1), dtype_code(x1.dtype), _ptr(affine1), int(bool(relu1)), _ptr(r1), c1, _ptr(x2),
-                                                  _ptr(affine2), int(bool(relu2)), _ptr(r2), c2, _ptr(pack.packed()), _ptr(pack.bias),
-                                                  _ptr(residual), dtype_code(rdt), _ptr(y), dtype_code(ydt), _ptr(out_range), n, pack.co,
-                                                  h, w, int(bool(relu)), _conv2d_products(products, "conv2d_cat"), _ptr(ws), ws_bytes,
-                                                  _stream()), "mphip_conv2d_cat_fwd_typed")
-        return tag_range(y, out_range)
-    _lib.check(lib.mphip_conv2d_cat_fwd(_ptr(x1), _ptr(affine1), int(bool(relu1)), _ptr(r1), c1, _ptr(x2), _ptr(affine2), int(bool(relu2)),
-                                        _ptr(r2), c2, _ptr(pack.packed()), _ptr(pack.bias), _ptr(residual), _ptr(y), _ptr(out_range), n,
-                                        pack.co, h, w, int(bool(relu)), _ptr(ws), ws_bytes, _stream()), "mphip_conv2d_cat_fwd")
-    return tag_range(y, out_range)
+    return _conv2d_launch("conv2d_cat", typed, pack, x1, affine1, r1, relu1, x2, affine2, r2, relu2, residual, relu, want_range, out_dtype, products)
 
 
 def avgpool2_bwd(dout: torch.Tensor) -> torch.Tensor:

@@ -43,16 +43,19 @@ def test_size_queries_are_monotone():
 def test_arguments_are_refused_without_a_gpu():
     """Every refusal happens before the first HIP call: these pointers are host addresses that are never dereferenced."""
     lib = _lib.load()
-    buf = ctypes.create_string_buffer(128)
-    p = ctypes.c_void_p((ctypes.addressof(buf) + 15) & ~15)
-    fwd = lambda n, ci, co, h, w, x=p, wp=p, b=p, y=p, ws=p, wsb=1 << 20: lib.mphip_conv2d_fwd(x, None, wp, b, None, y, None, n, ci, co, h, w,
-                                                                                          1, ws, wsb, None)
+    buf = ctypes.create_string_buffer(1 << 16)
+    base = (ctypes.addressof(buf) + 15) & ~15
+    p, q, r = (ctypes.c_void_p(base + i * 16384) for i in range(3))                 # three disjoint 16 KiB regions: x, y, workspace
+    fwd = lambda n, ci, co, h, w, x=p, wp=p, b=p, res=None, y=q, ws=r, wsb=1 << 20: lib.mphip_conv2d_fwd(
+        x, None, wp, b, res, y, None, n, ci, co, h, w, 1, ws, wsb, None)
     for bad in [(1, 8, 32, 8, 8), (1, 16, 16, 8, 8), (1, 16, 32, 0, 8)]:
         assert fwd(*bad) == -1 and b"unsupported shape" in lib.mphip_last_error()
     for missing in ("x", "wp", "b", "y"):
         assert fwd(1, 16, 32, 8, 8, **{missing: None}) == -1 and b"null pointer" in lib.mphip_last_error()
     assert fwd(1, 16, 32, 8, 8, wsb=4100 * 4 - 1) == -3 and b"workspace" in lib.mphip_last_error()
     assert fwd(1, 16, 32, 8, 8, ws=None, wsb=0) == -3
+    for alias in (dict(y=p), dict(y=ctypes.c_void_p(p.value + 64)), dict(res=q)):   # y = x, y inside x, residual = y
+        assert fwd(1, 16, 32, 8, 8, **alias) == -1 and b"must not alias" in lib.mphip_last_error(), alias
     assert lib.mphip_pack_conv2d_weight(p, p, 16, 16, None) == -1 and b"pack_conv2d_weight" in lib.mphip_last_error()
     assert lib.mphip_pack_conv2d_weight(p, p, 32, 8, None) == -1
     assert lib.mphip_pack_conv2d_weight(None, p, 32, 16, None) == -1 and b"null pointer" in lib.mphip_last_error()

@@ -218,7 +218,7 @@ def test_refusals():
 
     lib = _lib()
     t = torch.zeros(1 << 16, device=DEV)
-    args = lambda n, ci, co, h, w, x=t, wp=t, b=t, y=t, ws=t, wsb=1 << 18: (
+    args = lambda n, ci, co, h, w, x=t, wp=t, b=t, y=t[1 << 15:], ws=t, wsb=1 << 18: (      # (y apart from x: an in-place call is refused)
         _p(x), None, _p(wp), _p(b), None, _p(y), None, n, ci, co, h, w, 0, _p(ws), wsb, _stream())
     for shape in [(1, 8, 32, 8, 8), (1, 16, 16, 8, 8), (1, 16, 32, 0, 8), (1, 24, 32, 8, 8), (1, 16, 48, 8, 8), (0, 16, 32, 8, 8),
                   (1, 16, 32, 1 << 15, 1 << 15)]:
@@ -228,6 +228,7 @@ def test_refusals():
     assert lib.mphip_conv2d_supported(*ok) == 1
     for missing in ("x", "wp", "b", "y"):
         assert lib.mphip_conv2d_fwd(*args(*ok, **{missing: None})) == EINVAL and b"null" in lib.mphip_last_error()
+    assert lib.mphip_conv2d_fwd(*args(*ok, y=t)) == EINVAL and b"must not alias" in lib.mphip_last_error()
     need = lib.mphip_conv2d_workspace_bytes(*ok)
     assert need >= RANGE_FLOATS * 4
     assert lib.mphip_conv2d_fwd(*args(*ok, wsb=need - 4)) == EWORKSPACE and b"workspace" in lib.mphip_last_error()
