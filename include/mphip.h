@@ -41,7 +41,7 @@ extern "C" {
 
 /* ABI version of this header.  Bumped whenever an exported signature or a packed layout changes; mphip_version() returns the
  * value the LIBRARY was built with — compare the two after dlopen (the ctypes binding does, and refuses a mismatch). */
-#define MPHIP_ABI_VERSION 21
+#define MPHIP_ABI_VERSION 22
 int mphip_version(void);
 /* hipGraph hygiene (ABI 13).  On ROCm 7.x a MEMSET node of a captured hipGraph is not reliably ordered with its neighbouring kernel nodes
  * (observed twice: stale f16x3 pack headers, r03; a training step's loss that kept its previous value, r04-r05 — ATen's multi-block
@@ -619,6 +619,20 @@ int mphip_conv2d_cat_fwd_typed(const void *x1, int x_dtype, const float *affine1
                                const float *affine2, int relu2, const float *x2_range, int C2, const void *w_packed, const float *bias,
                                const void *residual, int residual_dtype, void *y, int y_dtype, float *out_range, int N, int Co, int H,
                                int W, int relu, int products, void *workspace, size_t workspace_bytes, void *stream);
+/* Stride 2 (ABI 22; csrc/conv2d_s2_f16x3.hip): nn.Conv2d(Ci, Co, 3, stride=2, padding=1) with mphip_conv2d_fwd's epilogue, for the
+ * down-sampling BasicBlocks of Emtn's ResNet-18s:
+ *     y[n,co,i,j] = act( sum w[co,ci,dy,dx] * x[n,ci,2i+dy-1,2j+dx-1] + bias[co] (+ residual[n,co,i,j]) )
+ * x is [N,Ci,H,W]; y and residual are [N,Co,Ho,Wo] with Ho = (H+1)/2, Wo = (W+1)/2.  H and W in the three signatures are the INPUT map's.
+ * w_packed is the ordinary pack (mphip_pack_conv2d_weight), x_range / out_range / workspace are mphip_conv2d_fwd's, and so is the
+ * arithmetic, term by term: with the same x, x_range, pack and bias this launch writes the bits mphip_conv2d_fwd writes at the even rows
+ * and columns (a residual being the even sub-sample of that call's).  fp32 maps and three products only: no typed or one-product form.
+ * Shapes: Ci % 16 == 0, Co % 32 == 0, N, H, W >= 1, N*Ci*H*W and N*Co*Ho*Wo below 2^31.  The call goes through the shared argument
+ * check of the four entries above, in the same order, with the extents of y and residual taken from Ho*Wo; messages name conv2d_s2_fwd. */
+int mphip_conv2d_s2_supported(int N, int Ci, int Co, int H, int W);
+size_t mphip_conv2d_s2_workspace_bytes(int N, int Ci, int Co, int H, int W);
+int mphip_conv2d_s2_fwd(const float *x, const float *x_range, const void *w_packed, const float *bias, const float *residual, float *y,
+                        float *out_range, int N, int Ci, int Co, int H, int W, int relu, void *workspace, size_t workspace_bytes,
+                        void *stream);
 
 /* The reference's reduced-precision policy for the convs (train.py:145,188: the generator step runs under torch.cuda.amp.autocast(), its
  * conv3d calls take f16 operands with fp32 accumulation).  mphip_conv3d_set_half_products(1) makes the CALLING THREAD's subsequent precision-1

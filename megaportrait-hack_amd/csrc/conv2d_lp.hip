@@ -115,7 +115,8 @@ void conv2d_lp_launch(const C2Call &c, const C2Grid &g) {
 #undef LP_CAT_LAUNCH
 }
 
-// The host side of every 2-D 3x3 conv entry.  The rules in the order they are checked, all before the first HIP call: dtypes and
+// The host side of every 2-D 3x3 conv entry (the stride-2 entry of conv2d_s2_f16x3.hip included: c.stride == 2, extents of y and
+// residual from the halved map).  The rules in the order they are checked, all before the first HIP call: dtypes and
 // products (lp_rule), pointers, the second source, the shape, alignment, tables, aliasing (MPHIP_EINVAL each), then the workspace
 // (MPHIP_EWORKSPACE).  Messages carry the called entry's name; a three-product call (all of its maps are fp32) is the fp32 entry's call
 // under whichever name it came in, and reports under that entry's name.
@@ -125,10 +126,14 @@ int conv2d_run(C2Call c) {
     MPHIP_REQUIRE(!why, "%s: %s (x dtype %d, residual dtype %d, y dtype %d, products %d)", c.who, why, c.x_dtype, c.residual_dtype, c.y_dtype,
                   c.products);
     c.products = np;
-    const char *who = c.products == 3 ? (c.cat ? "conv2d_cat_fwd" : "conv2d_fwd") : c.who;
+    const bool s2 = c.stride == 2;
+    MPHIP_REQUIRE(!s2 || (!c.cat && np == 3), "%s: the stride-2 conv is the plain fp32 three-product form", c.who);
+    const char *who = s2 ? c.who : c.products == 3 ? (c.cat ? "conv2d_cat_fwd" : "conv2d_fwd") : c.who;
     MPHIP_REQUIRE(c.x1 && c.w_packed && c.bias && c.y, "%s: null pointer", who);
     MPHIP_REQUIRE(c.C2 >= 0 && (c.x2 != nullptr) == (c.C2 > 0), "%s: x2 and C2 = %d: a second source needs both, one source neither", who, c.C2);
-    MPHIP_REQUIRE(c.cat ? mphip_conv2d_cat_supported(c.N, c.C1, c.C2, c.Co, c.H, c.W) : mphip_conv2d_supported(c.N, c.C1, c.Co, c.H, c.W),
+    MPHIP_REQUIRE(s2      ? c2_s2_supported(c.N, c.C1, c.Co, c.H, c.W)
+                  : c.cat ? mphip_conv2d_cat_supported(c.N, c.C1, c.C2, c.Co, c.H, c.W)
+                          : mphip_conv2d_supported(c.N, c.C1, c.Co, c.H, c.W),
                   "%s: unsupported shape N=%d C1=%d C2=%d Co=%d H=%d W=%d (C1 %% 16 == 0, C2 %% 16 == 0, Co %% 32 == 0, N, H, W >= 1, fewer than "
                   "2^31 elements per tensor)", who, c.N, c.C1, c.C2, c.Co, c.H, c.W);
     const size_t xb = lp_dtype_bytes(c.x_dtype), yb = lp_dtype_bytes(c.y_dtype), rb = lp_dtype_bytes(c.residual_dtype);
@@ -139,7 +144,8 @@ int conv2d_run(C2Call c) {
     // the bound of a normalised source is not the maximum of its raw values: a scan of x would give the wrong operand scale
     MPHIP_REQUIRE(!c.aff1 || c.x1_range, "%s: affine1 without x1_range (mphip_groupnorm_affine_table makes both)", who);
     MPHIP_REQUIRE(!c.aff2 || (c.x2 && c.x2_range), "%s: affine2 without x2 / x2_range (mphip_groupnorm_affine_table makes both)", who);
-    const size_t hw = (size_t)c.H * c.W, n1 = (size_t)c.N * c.C1 * hw, n2 = (size_t)c.N * c.C2 * hw, ny = (size_t)c.N * c.Co * hw;
+    const int Ho = s2 ? (c.H + 1) / 2 : c.H, Wo = s2 ? (c.W + 1) / 2 : c.W;   // the map of y and residual
+    const size_t hw = (size_t)c.H * c.W, n1 = (size_t)c.N * c.C1 * hw, n2 = (size_t)c.N * c.C2 * hw, ny = (size_t)c.N * c.Co * Ho * Wo;
     MPHIP_REQUIRE(!c2_overlap(c.y, ny * yb, c.x1, n1 * xb) && !c2_overlap(c.y, ny * yb, c.x2, n2 * sizeof(float)) &&
                       !c2_overlap(c.y, ny * yb, c.residual, ny * rb),
                   "%s: y must not alias a source or residual (a workgroup reads the halo of tiles other workgroups write)", who);
@@ -167,12 +173,13 @@ int conv2d_run(C2Call c) {
         }
     }
     C2Grid g;
-    g.tiles_w = cdiv(c.W, C2_TW), g.tiles_h = cdiv(c.H, C2_TH);
+    g.tiles_w = cdiv(Wo, s2 ? C2S2_TW : C2_TW), g.tiles_h = cdiv(Ho, s2 ? C2S2_TH : C2_TH);
     const long long tiles = (long long)c.N * g.tiles_h * g.tiles_w;   // (N * H * W < 2^31 by the shape rule: they fit grid.x)
     g.grid = dim3((unsigned)tiles, (unsigned)c2_cots(c.Co));
     g.nslots = (unsigned)std::min<long long>(tiles * c2_cots(c.Co), (long long)RANGE_MAX_PARTS);
     if (c.out_range) conv2d_out_range_init_launch(c.out_range, g.nslots, c.stream);
-    if (c.products == 1) conv2d_lp_launch(c, g);
+    if (s2) conv2d_s2_launch(c, g);
+    else if (c.products == 1) conv2d_lp_launch(c, g);
     else if (c.cat) conv2d_cat_launch(c, g);
     else conv2d_plain_launch(c, g);
     return check_launch(who);

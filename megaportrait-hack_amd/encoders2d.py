@@ -295,6 +295,16 @@ class Emtn(nn.Module):
         self.expression_net.adaptive_pool = nn.AdaptiveAvgPool2d(FEATURE_SIZE)  # model.py:881: appended, runs last
         self.fc = nn.Linear(2048, COMPRESS_DIM)
 
+    def native_resnets(self, enable: bool = True) -> "Emtn":
+        """Opt-in, inference only: run the eight BasicBlocks of `head_pose_net` and of `expression_net` as model.BasicBlockFused —
+        BatchNorm folded, the 3x3 convs on the matrix cores with fp32-class accuracy (csrc/conv2d_f16x3.hip, and
+        csrc/conv2d_s2_f16x3.hip for the three stride-2 convs of a net) — over the blocks' own children: same Parameter objects, same
+        state-dict keys.  `enable=False` puts the original blocks back.  In train mode, under autograd or on a half model the fused
+        blocks evaluate the original PyTorch expression; there is no half_precision form.  The 3->64 stem (conv, BatchNorm, ReLU,
+        max-pool), the pools, the `fc`s and the whole 6DRepNet `rotation_net` stay on PyTorch."""
+        M.native_emtn_resnets(self, enable)
+        return self
+
     def forward(self, x):
         rotations, _ = self.rotation_net.predict(x)
         translation = self.head_pose_net(x)[:, 3:]

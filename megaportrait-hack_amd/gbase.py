@@ -73,6 +73,15 @@ class Gbase(M._HotSliceRunner, nn.Module):
         M.native_eapp_trunk(self.appearanceEncoder, enable, half_precision)
         return self
 
+    def native_motion_encoder(self, enable: bool = True) -> "Gbase":
+        """Opt-in (off by default), inference only: the BasicBlocks of the motion encoder's two ResNet-18s (`head_pose_net`,
+        `expression_net`) as model.BasicBlockFused — BatchNorm folded, 3x3 convs on the matrix cores, the stride-2 ones included
+        (model.native_emtn_resnets); `enable=False` restores the original blocks.  Same parameters and state-dict keys.  The 3->64
+        stems, the pools, the `fc`s and the 6DRepNet `rotation_net` stay on PyTorch.  With channels_last_2d() a block's input map is
+        copied to NCHW once."""
+        M.native_emtn_resnets(self.motionEncoder, enable)
+        return self
+
     def _nhwc(self, x):
         return x.contiguous(memory_format=torch.channels_last) if getattr(self, "_cl2d", False) and x.dim() == 4 else x
 

@@ -728,9 +728,11 @@ def native_final_conv(g2d: nn.Module, enable: bool = True) -> bool:
 def fold_batchnorm(conv: nn.Module, bn: nn.Module, dtype: Optional[torch.dtype] = None):
     """Eval-mode `bn(conv(x))` as one conv: s = gamma / sqrt(running_var + eps), w' = w * s[:, None, None, None],
     b' = (b - running_mean) * s + beta, in the parameters' own dtype (fp32 on the native path) -> (w', b').  dtype: the parameters and
-    running statistics are cast to it first (fp32 for a half block: the fold of its fp32 twin)."""
-    w, b, g, beta, mean, var = (t.detach() if dtype is None else t.detach().to(dtype)
-                                for t in (conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var))
+    running statistics are cast to it first (fp32 for a half block: the fold of its fp32 twin).  A conv without bias (torchvision's
+    BasicBlock) folds as one with a zero bias."""
+    w, g, beta, mean, var = (t.detach() if dtype is None else t.detach().to(dtype)
+                             for t in (conv.weight, bn.weight, bn.bias, bn.running_mean, bn.running_var))
+    b = torch.zeros_like(mean) if conv.bias is None else conv.bias.detach() if dtype is None else conv.bias.detach().to(dtype)
     s = g / torch.sqrt(var + bn.eps)
     return (w * s[:, None, None, None]).contiguous(), ((b - mean) * s + beta).contiguous()
 
@@ -952,6 +954,116 @@ class ResBlock2DFused(_FusedBlock2D):
         return ops.conv2d(y1, p2, residual=idt, relu=True, want_range=True, out_dtype=out_dtype, products=products)
 
 
+def _is_conv2d_at(m, k: int, stride: int) -> bool:
+    """_is_conv2d at a given stride, and with or without a bias (BasicBlockFused's convs)."""
+    return (isinstance(m, nn.Conv2d) and m.kernel_size == (k, k) and m.stride == (stride, stride) and m.padding == ((k - 1) // 2,) * 2
+            and m.dilation == (1, 1) and m.groups == 1 and m.padding_mode == "zeros")
+
+
+class BasicBlockFused(_FusedBlock2D):
+    """A torchvision-style ResNet BasicBlock — encoders2d._BasicBlock, the reference's resnet.BasicBlock: 3x3 conv, BatchNorm, ReLU,
+    3x3 conv, BatchNorm, add, ReLU; `downsample` is None or Sequential(1x1 conv at conv1's stride, BatchNorm) — with an opt-in inference
+    path on the matrix cores, as ResBlock2DFused has it: BatchNorm folded into the (bias-less) convs, each 3x3 conv one launch with bias,
+    ReLU and the residual add in its epilogue, f16x3 arithmetic (fp32-class accuracy).  A stride-1 block is ResBlock2DFused's two launches
+    of csrc/conv2d_f16x3.hip.  A stride-2 block runs conv1 on csrc/conv2d_s2_f16x3.hip; its 1x1 stride-2 `downsample` reads a
+    quarter-size torch copy x[:, :, ::2, ::2] through the existing k = 1 conv with the BatchNorm folded (not fused into the stride-2
+    launch).  The children are the original block's own `conv1, bn1, relu, conv2, bn2, downsample`: the same Parameter and buffer
+    objects, the same state-dict keys.
+
+    The native path runs only in eval mode, without autograd, on an fp32 module and a supported shape (Ci % 16, Co % 32); otherwise
+    forward evaluates the original block's expression in PyTorch.  There are NO backward kernels, NO half-model path and NO
+    half_precision form: training and .half() / .bfloat16() instances take the PyTorch expression.  fp16 / bf16 inputs are widened and
+    the result is fp32; channels_last inputs are copied to NCHW once.  Each block leaves the range descriptor of its output on the
+    tensor, so only the first block of a net scans its input."""
+
+    _CHILDREN = ("conv1", "bn1", "relu", "conv2", "bn2", "downsample")
+    _EXPECTED = ("a ResNet BasicBlock (3x3 convs with or without bias, the first at stride 1 or 2, BatchNorm2d with running statistics, "
+                 "downsample None or Conv2d 1x1 at that stride + BatchNorm2d, no `shortcut`)")
+    _EVAL_ONLY = True
+
+    def __init__(self, inplanes: int, planes: int, stride: int = 1):
+        super().__init__()
+        self.conv1 = nn.Conv2d(inplanes, planes, 3, stride=stride, padding=1, bias=False)
+        self.bn1 = nn.BatchNorm2d(planes)
+        self.relu = nn.ReLU(inplace=True)
+        self.conv2 = nn.Conv2d(planes, planes, 3, padding=1, bias=False)
+        self.bn2 = nn.BatchNorm2d(planes)
+        self.downsample = None
+        if stride != 1 or inplanes != planes:
+            self.downsample = nn.Sequential(nn.Conv2d(inplanes, planes, 1, stride=stride, bias=False), nn.BatchNorm2d(planes))
+
+    @classmethod
+    def from_block(cls, block: nn.Module, half_precision: bool = False):
+        if half_precision:
+            raise TypeError("BasicBlockFused has no half_precision form")
+        return super().from_block(block, False)
+
+    @staticmethod
+    def matches(block) -> bool:
+        """Duck-typed: is `block` a BasicBlock the fused path can stand in for?  (Not a ResBlock2D: that one has a `shortcut`.)"""
+        if isinstance(block, _FusedBlock2D) or not isinstance(block, nn.Module) or hasattr(block, "shortcut"):
+            return False
+        conv1, bn1, relu, conv2, bn2 = (getattr(block, n, None) for n in ("conv1", "bn1", "relu", "conv2", "bn2"))
+        if not isinstance(relu, nn.ReLU) or not hasattr(block, "downsample"):
+            return False
+        stride = 2 if isinstance(conv1, nn.Conv2d) and conv1.stride == (2, 2) else 1
+        if not (_is_conv2d_at(conv1, 3, stride) and _is_conv2d_at(conv2, 3, 1)):
+            return False
+        ci, co = conv1.in_channels, conv1.out_channels
+        if conv2.in_channels != co or conv2.out_channels != co or not (_is_bn2d(bn1, co) and _is_bn2d(bn2, co)):
+            return False
+        ds = block.downsample
+        if ds is None:
+            return stride == 1 and ci == co
+        return (isinstance(ds, nn.Sequential) and len(ds) == 2 and _is_conv2d_at(ds[0], 1, stride) and ds[0].in_channels == ci
+                and ds[0].out_channels == co and _is_bn2d(ds[1], co))
+
+    def _adopt(self, block):
+        pass
+
+    def _stride(self) -> int:
+        return self.conv1.stride[0]
+
+    def _shape_ok(self, x) -> bool:
+        (n, ci, h, w), co, s = x.shape, self.conv1.out_channels, self._stride()
+        if ci != self.conv1.in_channels:
+            return False
+        if s == 1:
+            return ops.conv2d_supported(n, ci, co, h, w) and ops.conv2d_supported(n, co, co, h, w)
+        return ops.conv2d_s2_supported(n, ci, co, h, w) and ops.conv2d_supported(n, co, co, (h + 1) // 2, (w + 1) // 2)
+
+    def _dtypes(self, half_path: bool):
+        return {self.conv1.weight.dtype}
+
+    def _fold_pairs(self):
+        return [(self.conv1, self.bn1), (self.conv2, self.bn2)] + ([tuple(self.downsample)] if self.downsample is not None else [])
+
+    def _fold_tensors(self):
+        return [t for conv, bn in self._fold_pairs() for t in (conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var)
+                if t is not None]
+
+    _fold = ResBlock2DFused._fold   # (conv1', conv2', downsample' or None): BatchNorm folded and packed
+
+    def _reference(self, x):
+        idt = x if self.downsample is None else self.downsample(x)
+        y = self.relu(self.bn1(self.conv1(x)))
+        return self.relu(self.bn2(self.conv2(y)) + idt)
+
+    def _launch(self, x, packs, out_dtype, products):
+        """Stride 1: ResBlock2DFused's launches.  Stride 2: the stride-2 conv, the 1x1 conv on the even sub-sample, the second conv."""
+        p1, p2, ps = packs
+        xc = _f32(x).contiguous()   # (the kernels read NCHW: a channels_last map is copied once)
+        s2 = self._stride() == 2
+        y1 = (ops.conv2d_s2 if s2 else ops.conv2d)(xc, p1, relu=True, want_range=True)
+        idt = xc
+        if ps is not None:
+            xr = ops.current_range(xc)   # (of the whole map: a valid bound of its sub-sample)
+            xs = xc[:, :, ::2, ::2].contiguous() if s2 else xc
+            n, c, h, w = xs.shape
+            idt = ops.conv3d(xs.reshape(n, c, 1, h, w), ps, x_range=xr).reshape(n, ps.co, h, w)
+        return ops.conv2d(y1, p2, residual=idt, relu=True, want_range=True)
+
+
 def _swap_slot(cls, cur, enable: bool, half_precision: bool):
     """One slot of native_g2d_body / native_eapp_trunk -> (the module the slot holds now, whether anything changed): a matching block
     becomes a `cls` over the same children, a fused one takes the keyword's value, or (enable off) the very object it replaced comes back."""
@@ -984,6 +1096,27 @@ def native_g2d_body(g2d: nn.Module, enable: bool = True, half_precision: bool = 
             if new is not seq[i]:
                 seq[i] = new
             changed |= did
+    return changed
+
+
+def native_emtn_resnets(emtn: nn.Module, enable: bool = True) -> bool:
+    """Swaps every matching BasicBlock in every nn.Sequential stage of `emtn.head_pose_net` and `emtn.expression_net` (this package's Emtn
+    or the reference's, model.py:869-907; the stages are found by type: `layer1..4` in the first, positional children in the second)
+    for a BasicBlockFused over the same children, or puts the very objects it replaced back.  Returns whether anything changed.  Off by
+    default everywhere; opt-in, inference only.  What stays on PyTorch: each net's 3->64 stem conv + BatchNorm + ReLU + max-pool (Ci = 3
+    does not fit the kernel), the pools and the `fc`s, and the whole 6DRepNet `rotation_net` (grouped convs; not an nn.Module of Gbase)."""
+    changed = False
+    for net in (getattr(emtn, "head_pose_net", None), getattr(emtn, "expression_net", None)):
+        if not isinstance(net, nn.Module):
+            continue
+        for stage in net.children():
+            if not isinstance(stage, nn.Sequential):
+                continue
+            for i in range(len(stage)):
+                new, did = _swap_slot(BasicBlockFused, stage[i], enable, False)
+                if new is not stage[i]:
+                    stage[i] = new
+                changed |= did
     return changed
 
 

@@ -1271,22 +1271,25 @@ def conv2d(x: torch.Tensor, pack: PackedConv2d, residual: Optional[torch.Tensor]
 
 
 def _conv2d_launch(who, typed, pack, x1, aff1, r1, relu1, x2, aff2, r2, relu2, residual, relu, want_range, out_dtype, products):
-    """What ops.conv2d (who = "conv2d": the plain kernels) and ops.conv2d_cat share once their sources are checked and the descriptors r1 /
-    r2 chosen: the residual check, the workspace, y and out_range, and the call of the fp32 or (`typed`) the typed entry."""
+    """What ops.conv2d (who = "conv2d": the plain kernels), ops.conv2d_cat and ops.conv2d_s2 (the stride-2 kernel: y and residual on the
+    halved map) share once their sources are checked and the descriptors r1 / r2 chosen: the residual check, the workspace, y and
+    out_range, and the call of the fp32 or (`typed`) the typed entry."""
     cat = who == "conv2d_cat"
     lib = _lib.load()
     n, c1, h, w = x1.shape
     c2 = 0 if x2 is None else int(x2.shape[1])
+    ho, wo = ((h + 1) // 2, (w + 1) // 2) if who == "conv2d_s2" else (h, w)
     if residual is not None:
         residual = _req_typed(residual, "residual") if typed else _req(residual, "residual")
-        if tuple(residual.shape) != (n, pack.co, h, w):
-            raise RuntimeError(f"{who}: residual {tuple(residual.shape)} does not match the output {(n, pack.co, h, w)}")
+        if tuple(residual.shape) != (n, pack.co, ho, wo):
+            raise RuntimeError(f"{who}: residual {tuple(residual.shape)} does not match the output {(n, pack.co, ho, wo)}")
     ws_bytes = 0
     if r1 is None or (x2 is not None and r2 is None):   # a source to scan
-        ws_bytes = lib.mphip_conv2d_cat_workspace_bytes(n, c1, c2, pack.co, h, w) if cat else lib.mphip_conv2d_workspace_bytes(n, c1, pack.co, h, w)
+        ws_bytes = (lib.mphip_conv2d_cat_workspace_bytes(n, c1, c2, pack.co, h, w) if cat
+                    else getattr(lib, f"mphip_{who}_workspace_bytes")(n, c1, pack.co, h, w))
     ws = torch.empty((ws_bytes + 3) // 4, dtype=torch.float32, device=x1.device) if ws_bytes else None
     ydt = torch.float32 if out_dtype is None else out_dtype
-    y = torch.empty((n, pack.co, h, w), dtype=ydt, device=x1.device)
+    y = torch.empty((n, pack.co, ho, wo), dtype=ydt, device=x1.device)
     out_range = new_range(x1.device) if want_range else None
     # the entry's arguments in its order: a typed entry takes a dtype code after x1, residual and y, and the product count after relu
     rdt = torch.float32 if residual is None else residual.dtype
@@ -1302,6 +1305,26 @@ def _conv2d_launch(who, typed, pack, x1, aff1, r1, relu1, x2, aff2, r2, relu2, r
     entry = f"mphip_{who}_fwd" + ("_typed" if typed else "")
     _lib.check(getattr(lib, entry)(*args), entry)
     return tag_range(y, out_range)
+
+
+def conv2d_s2_supported(n: int, ci: int, co: int, h: int, w: int) -> bool:
+    """Does ops.conv2d_s2 take an [n, ci, h, w] input (h, w: the INPUT map) with co output channels (mphip_conv2d_s2_supported)?"""
+    return bool(_lib.load().mphip_conv2d_s2_supported(int(n), int(ci), int(co), int(h), int(w)))
+
+
+def conv2d_s2(x: torch.Tensor, pack: PackedConv2d, residual: Optional[torch.Tensor] = None, relu: bool = False,
+              x_range: Optional[torch.Tensor] = None, want_range: bool = False) -> torch.Tensor:
+    """y = act(conv3x3(x, stride 2) + bias (+ residual)) on NCHW fp32, padding 1 (mphip_conv2d_s2_fwd): y and residual are
+    [N, Co, (H+1)//2, (W+1)//2].  The pack, the f16x3 arithmetic and the descriptors are ops.conv2d's: with the same x, x_range and pack
+    the result is, bit for bit, conv2d(...)[:, :, ::2, ::2] (a residual being the even sub-sample of that call's).  fp32 only."""
+    x = _req(x, "x")
+    if x.dim() != 4 or x.shape[1] != pack.ci:
+        raise RuntimeError(f"conv2d_s2: input {tuple(x.shape)} does not match Ci={pack.ci}")
+    n, ci, h, w = x.shape
+    if not _lib.load().mphip_conv2d_s2_supported(n, ci, pack.co, h, w):
+        raise RuntimeError(f"conv2d_s2: unsupported shape N={n} Ci={ci} Co={pack.co} H={h} W={w} (there is no fallback)")
+    xr = x_range if x_range is not None else current_range(x)   # None: the library scans x
+    return _conv2d_launch("conv2d_s2", False, pack, x, None, xr, False, None, None, None, False, residual, relu, want_range, None, None)
 
 
 _GN_UNIT = {}   # (device, C) -> (ones, zeros): gamma and beta of a GroupNorm without parameters

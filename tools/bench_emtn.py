@@ -1,0 +1,99 @@
+"""Informational: Emtn.forward, image [B,3,512,512] -> (rotation, translation, expression) — the frozen 6DRepNet and the two CIFAR-stem
+ResNet-18s `head_pose_net` and `expression_net` — with `native_resnets()` on — their sixteen BasicBlocks as model.BasicBlockFused, the 3x3
+convs on csrc/conv2d_f16x3.hip and csrc/conv2d_s2_f16x3.hip — against the same call with the switch off (torch fp32, cudnn.benchmark on) on
+the same box and commit, in the same process.  Each leg: `warmup` calls, then `runs` calls timed one by one with HIP events; the median is
+reported.  The legs run off, on, on, off so that neither side always goes first.  B = 1 and B = 8.  One more leg for context: the unswapped
+module under torch.autocast(float16).  And one 64 -> 128 stride-2 launch at 256 x 256 (layer2's first conv at 512^2 input) with its
+TFLOP/s, counting 2 * 9 * Ci * Co * Ho * Wo.  Prints one JSON line; --out also writes it to a file.
+usage: python tools/bench_emtn.py [--b 1 8] [--warmup 5] [--runs 20] [--out profiles/emtn_timing.json]"""
+import argparse, json, os, statistics, subprocess, sys
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch
+from megaportrait_hack_amd import encoders2d as E, model as M, ops
+
+
+def median_ms(fn, warmup, runs):
+    for _ in range(warmup):
+        fn()
+    times = []
+    for _ in range(runs):
+        start, end = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        start.record()
+        fn()
+        end.record()
+        torch.cuda.synchronize()
+        times.append(start.elapsed_time(end))
+    return statistics.median(times), min(times)
+
+
+def commit():
+    try:
+        root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+        r = subprocess.run(["git", "-C", root, "rev-parse", "--short", "HEAD"], capture_output=True, text=True)
+        return r.stdout.strip() or os.environ.get("MPHIP_COMMIT", "unknown")
+    except OSError:
+        return os.environ.get("MPHIP_COMMIT", "unknown")
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--b", type=int, nargs="+", default=[1, 8])
+    ap.add_argument("--hw", type=int, default=512)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--runs", type=int, default=20)
+    ap.add_argument("--out")
+    a = ap.parse_args()
+    if a.runs < 20:
+        ap.error("--runs: the median of at least 20 runs is reported")
+    dev = torch.device("cuda:0")
+    torch.manual_seed(20241018)
+    torch.backends.cudnn.benchmark = True
+    emtn = E.Emtn().to(dev).eval()
+    out = {"what": "Emtn.forward: 6DRepNet rotation_net, head_pose_net and expression_net (CIFAR-stem ResNet-18s), fc",
+           "commit": commit(), "device": torch.cuda.get_device_name(0), "torch": torch.__version__, "H": a.hw, "W": a.hw, "warmup": a.warmup,
+           "runs": a.runs, "timer": "HIP events around each call after `warmup` calls; median (and minimum) of `runs` calls, ms per call",
+           "order": ["off", "on", "on", "off"], "batches": {}}
+    with torch.no_grad():
+        # one launch of layer2's first conv: 64 -> 128 at stride 2 from a 256 x 256 map (B = 1), and the stride-1 conv that follows it
+        h = a.hw // 2
+        xc = torch.randn(1, 64, h, h, device=dev)
+        pk = ops.PackedConv2d(torch.randn(128, 64, 3, 3, device=dev) * 0.05, torch.zeros(128, device=dev))
+        rng = ops.absmax_range(xc)
+        flop = 2.0 * 9 * 64 * 128 * (h // 2) ** 2
+        s2, _ = median_ms(lambda: ops.conv2d_s2(xc, pk, x_range=rng), a.warmup, a.runs)
+        out["conv_s2_64_128"] = {"H": h, "W": h, "Ho": h // 2, "Wo": h // 2, "ms": round(s2, 4), "tflops": round(flop / s2 * 1e-9, 1)}
+        x1 = torch.randn(1, 128, h // 2, h // 2, device=dev)
+        pk1 = ops.PackedConv2d(torch.randn(128, 128, 3, 3, device=dev) * 0.05, torch.zeros(128, device=dev))
+        rng1 = ops.absmax_range(x1)
+        s1, _ = median_ms(lambda: ops.conv2d(x1, pk1, x_range=rng1), a.warmup, a.runs)
+        out["conv_s1_128_128"] = {"H": h // 2, "W": h // 2, "ms": round(s1, 4), "tflops": round(2.0 * 9 * 128 * 128 * (h // 2) ** 2 / s1 * 1e-9, 1)}
+        del xc, pk, x1, pk1
+        for b in a.b:
+            x = torch.rand(b, 3, a.hw, a.hw, device=dev) * 2 - 1
+            legs = []
+            for on in (False, True, True, False):
+                M.native_emtn_resnets(emtn, on)
+                med, best = median_ms(lambda: emtn(x), a.warmup, a.runs)
+                legs.append({"native_resnets": on, "median_ms": round(med, 4), "min_ms": round(best, 4)})
+            emtn.native_resnets(True)
+            _, t_on, e_on = emtn(x)
+            emtn.native_resnets(False)
+            _, t_off, e_off = emtn(x)
+            with torch.autocast(device_type="cuda", dtype=torch.float16):
+                amp, amp_best = median_ms(lambda: emtn(x), a.warmup, a.runs)
+            off = statistics.mean(l["median_ms"] for l in legs if not l["native_resnets"])
+            on = statistics.mean(l["median_ms"] for l in legs if l["native_resnets"])
+            out["batches"][str(b)] = {"legs": legs, "off_ms": round(off, 4), "on_ms": round(on, 4), "off_over_on": round(off / on, 3),
+                                      "torch_autocast_fp16_ms": round(amp, 4), "torch_autocast_fp16_min_ms": round(amp_best, 4),
+                                      "expression_on_vs_off_max_abs": (e_on - e_off).abs().max().item(), "expression_max_abs_off": e_off.abs().max().item(),
+                                      "translation_on_vs_off_max_abs": (t_on - t_off).abs().max().item(), "translation_max_abs_off": t_off.abs().max().item()}
+            del x
+    print(json.dumps(out))
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(json.dumps(out, indent=1) + "\n")
+
+
+if __name__ == "__main__":
+    main()
