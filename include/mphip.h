@@ -41,7 +41,7 @@ extern "C" {
 
 /* ABI version of this header.  Bumped whenever an exported signature or a packed layout changes; mphip_version() returns the
  * value the LIBRARY was built with — compare the two after dlopen (the ctypes binding does, and refuses a mismatch). */
-#define MPHIP_ABI_VERSION 22
+#define MPHIP_ABI_VERSION 23
 int mphip_version(void);
 /* hipGraph hygiene (ABI 13).  On ROCm 7.x a MEMSET node of a captured hipGraph is not reliably ordered with its neighbouring kernel nodes
  * (observed twice: stale f16x3 pack headers, r03; a training step's loss that kept its previous value, r04-r05 — ATen's multi-block
@@ -633,6 +633,33 @@ size_t mphip_conv2d_s2_workspace_bytes(int N, int Ci, int Co, int H, int W);
 int mphip_conv2d_s2_fwd(const float *x, const float *x_range, const void *w_packed, const float *bias, const float *residual, float *y,
                         float *out_range, int N, int Ci, int Co, int H, int W, int relu, void *workspace, size_t workspace_bytes,
                         void *stream);
+/* A bilinear x2 up-sample folded in (ABI 23; csrc/conv2d_up2_f16x3.hip), for G2d's three Sequential(nn.Upsample(scale_factor=2,
+ * mode="bilinear", align_corners=True), ResBlock2D) stages: the up-sampled map is never written.
+ * up2(x) for x [N,C,h,w] is [N,C,2h,2w].  For output row i:  num = i*(h-1), den = 2h-1 (h == 1: num = 0, den = 1),
+ *     i0 = num div den,   lambda = float(num mod den) / float(den)  (one correctly rounded fp32 division),   i1 = min(i0+1, h-1);
+ * columns get j0, j1, mu the same way from w.  The value is horizontal first,
+ *     top = x[i0,j0]*(1-mu) + x[i0,j1]*mu,   bot = x[i1,j0]*(1-mu) + x[i1,j1]*mu,   u = top*(1-lambda) + bot*lambda,
+ * every product, sum and 1 - . rounded to fp32 on its own (no FMA).  u is a convex blend of four inputs up to rounding, so a range
+ * descriptor of x is a bound of up2(x) (slot [2] of a descriptor may hold an upper bound): no up-sampled map is scanned.
+ *   mphip_conv2d_up2_fwd:    y = act( conv(up2(x), w) + bias (+ residual) ).  x [N,Ci,h,w]; y and residual [N,Co,2h,2w].  h and w in
+ *          the three signatures that take them are the LOW-resolution INPUT map's.  x_range describes x (NULL: the library scans the
+ *          low-resolution x into `workspace`, mphip_conv2d_up2_workspace_bytes).  Zero padding and the ragged edge are zeros of the
+ *          up-sampled map.  Shapes: mphip_conv2d_supported(N, Ci, Co, 2h, 2w), which mphip_conv2d_up2_supported(N, Ci, Co, h, w) returns.
+ *   mphip_conv2d_resup2_fwd: y = act( conv(x, w) + bias + up2(r) ).  x [N,Ci,H,W], y [N,Co,H,W], residual_lowres = r [N,Co,H/2,W/2],
+ *          required; H and W even (odd: MPHIP_EINVAL).  Shapes: mphip_conv2d_supported(N, Ci, Co, H, W); workspace:
+ *          mphip_conv2d_workspace_bytes (= mphip_conv2d_up2_workspace_bytes(N, Ci, Co, H/2, W/2)).
+ * w_packed is the ordinary pack, tile, arithmetic, epilogue, out_range and saturation counting are mphip_conv2d_fwd's: with the same x,
+ * x_range, pack and bias the launches write the bits of mphip_conv2d_fwd(up2(x)) and of mphip_conv2d_fwd(x, residual = up2(r)).  fp32
+ * maps and three products only.  y must not overlap x or the residual.  Both go through the shared argument check of the entries
+ * above, in the same order (the even-extent rule after the shape rule); messages name conv2d_up2_fwd / conv2d_resup2_fwd.             */
+int mphip_conv2d_up2_supported(int N, int Ci, int Co, int h, int w);
+size_t mphip_conv2d_up2_workspace_bytes(int N, int Ci, int Co, int h, int w);
+int mphip_conv2d_up2_fwd(const float *x, const float *x_range, const void *w_packed, const float *bias, const float *residual, float *y,
+                         float *out_range, int N, int Ci, int Co, int h, int w, int relu, void *workspace, size_t workspace_bytes,
+                         void *stream);
+int mphip_conv2d_resup2_fwd(const float *x, const float *x_range, const void *w_packed, const float *bias, const float *residual_lowres,
+                            float *y, float *out_range, int N, int Ci, int Co, int H, int W, int relu, void *workspace,
+                            size_t workspace_bytes, void *stream);
 
 /* The reference's reduced-precision policy for the convs (train.py:145,188: the generator step runs under torch.cuda.amp.autocast(), its
  * conv3d calls take f16 operands with fp32 accumulation).  mphip_conv3d_set_half_products(1) makes the CALLING THREAD's subsequent precision-1

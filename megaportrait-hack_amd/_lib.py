@@ -156,6 +156,11 @@ SIGNATURES = {
     "mphip_conv2d_s2_supported": (_i, [_i] * 5),
     "mphip_conv2d_s2_workspace_bytes": (_sz, [_i] * 5),
     "mphip_conv2d_s2_fwd": (_i, [_p] * 7 + [_i] * 6 + [_p, _sz, _p]),
+    # a bilinear x2 up-sample folded into the source or the residual (ABI 23, csrc/conv2d_up2_f16x3.hip)
+    "mphip_conv2d_up2_supported": (_i, [_i] * 5),
+    "mphip_conv2d_up2_workspace_bytes": (_sz, [_i] * 5),
+    "mphip_conv2d_up2_fwd": (_i, [_p] * 7 + [_i] * 6 + [_p, _sz, _p]),
+    "mphip_conv2d_resup2_fwd": (_i, [_p] * 7 + [_i] * 6 + [_p, _sz, _p]),
     "mphip_build_flags": (_i, []),
     "mphip_graph_memsets_to_kernels": (_i, [_p, ctypes.POINTER(ctypes.c_int)]),
     "mphip_graph_memset_nodes_left": (_i, [_p, ctypes.POINTER(ctypes.c_int)]),
@@ -170,7 +175,7 @@ _lib = None
 # The ABI version the SIGNATURES table above mirrors.  Checked against the library at load time, and against include/mphip.h by
 # tests/test_host.py — NOT read from the header at run time: a relocated / installed package ships libmphip.so without the repository's
 # include/ directory.
-EXPECTED_ABI_VERSION = 22
+EXPECTED_ABI_VERSION = 23
 
 
 def header_abi_version() -> int:

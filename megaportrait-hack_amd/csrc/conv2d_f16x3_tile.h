@@ -21,6 +21,14 @@
 //   NP        products per multiply.  3: Wlo*Xhi + Whi*Xhi + Whi*Xlo.  1: Whi*Xhi alone, the autocast(float16) policy: split_f16 becomes
 //             the one rounding round_f16(v * scale), no lo half is fetched, staged or read, and LDS holds the hi planes only (18432 +
 //             10368 bytes).  The hi plane is [part 0] of every slab of the ordinary pack: the same packed weights serve both.
+//
+// One more axis, instantiated by conv2d_up2_f16x3.hip (every other unit is UP = 0; the arithmetic of up2 is in that unit's header):
+//   UP = 1    the source is up2(x), x [N,Ci,H/2,W/2] (H, W stay the OUTPUT map's): per chunk the 10 x 10 source pixels per channel that
+//             the 18 x 18 halo blends from are loaded (7 loads per thread instead of 22), parked in 6400 bytes of LDS and blended when
+//             the chunk is written; a halo pixel's (offset of row i0, of row i1, lambda, in-image) and the same per column are two
+//             18-entry tables in LDS, computed once per workgroup.  The up-sampled map is never written.
+//   UP = 2    the residual is up2(r), r [N,Co,H/2,W/2] (H, W even): staging is the plain one, the epilogue adds the blend of four loads
+//             of r; a lane's coordinates depend on its pixel only and are computed once, before the channel loops.
 #pragma once
 #include <algorithm>
 
@@ -75,8 +83,48 @@ __device__ __forceinline__ float *c2_affine_lds() {
     }
 }
 
+// UP = 1: the source patch of a tile.  Halo rows 16k-1 .. 16k+16 of the up-sampled map blend from source rows 8k-1 .. 8k+8 (up2_coord).
+constexpr int C2_UP_P = 10;                            // patch rows and columns
+constexpr int C2_UP_CS = C2_UP_P * C2_UP_P;            // floats per channel
+constexpr int C2_UP_PATCH = C2_KC * C2_UP_CS;          // floats per chunk: 6400 B
+constexpr int C2_UP_PI = (C2_UP_PATCH + C2_NTHR - 1) / C2_NTHR;   // 7 loads per thread
+// UP = 1: the patch [channel][row][column], then the row table and the column table [18][4] = (offset of i0, offset of i1, lambda, in-image)
+template <int UP>
+__device__ __forceinline__ float *c2_up2_lds() {
+    if constexpr (UP == 1) {
+        __shared__ __attribute__((aligned(16))) float up[C2_UP_PATCH + 2 * C2_HH * 4];
+        return up;
+    } else {
+        return nullptr;
+    }
+}
+
+// One correctly rounded fp32 division of two fp32 values: the fp64 quotient of two 24-bit significands rounded to 24 bits is the
+// correctly rounded quotient (53 >= 2 * 24 + 2), whatever the compiler's fp32 division expands to.
+__device__ __forceinline__ float div_rn_f32(float a, float b) { return (float)((double)a / (double)b); }
+
+// Row (or column) i in [0, 2l) of up2 of a map with l rows: i0 = i(l-1) div (2l-1), lambda = float(i(l-1) mod (2l-1)) / float(2l-1),
+// i1 = min(i0 + 1, l - 1).  Quotient and remainder in closed form (exact integer identities, no wide product and no integer division):
+//   i = 2m+1: (m, l-1-m);   i = 2m, m >= 1: (m-1, 2l-1-m);   i = 0: (0, 0).   l == 1 gives (0, 0) and lambda = 0 / 1.
+__device__ __forceinline__ void up2_coord(int i, int l, int &i0, int &i1, float &lam) {
+    const int m = i >> 1;
+    const bool odd = (i & 1) != 0;
+    i0 = odd ? m : max(m - 1, 0);
+    const int rem = odd ? l - 1 - m : (m ? 2 * l - 1 - m : 0);
+    lam = div_rn_f32((float)rem, (float)(2 * l - 1));
+    i1 = min(i0 + 1, l - 1);
+}
+// The blend of up2, every product, sum and 1 - x rounded to fp32 on its own (-ffp-contract=off): horizontal first.
+__device__ __forceinline__ float up2_blend(float x00, float x01, float x10, float x11, float mu, float lam) {
+    const float om = 1.0f - mu, ol = 1.0f - lam;
+    const float ta = x00 * om, tb = x01 * mu, ba = x10 * om, bb = x11 * mu;
+    const float top = ta + tb, bot = ba + bb;
+    const float ua = top * ol, ub = bot * lam;
+    return ua + ub;
+}
+
 // SAT: the instantiating unit's saturation counter
-template <bool CAT, unsigned long long *SAT, int XDT = MPHIP_DTYPE_F32, int YDT = MPHIP_DTYPE_F32, int NP = 3>
+template <bool CAT, unsigned long long *SAT, int XDT = MPHIP_DTYPE_F32, int YDT = MPHIP_DTYPE_F32, int NP = 3, int UP = 0>
 __device__ __forceinline__ void conv2d_k3_tile(const dtype_t<XDT> *__restrict__ x, const float *__restrict__ x_range, const C2CatArgs cat,
                                                const _Float16 *__restrict__ wslabs, const float *__restrict__ whdr,
                                                const float *__restrict__ bias, const float *__restrict__ residual,
@@ -85,11 +133,13 @@ __device__ __forceinline__ void conv2d_k3_tile(const dtype_t<XDT> *__restrict__ 
                                                const dtype_t<YDT> *__restrict__ residual_t = nullptr) {
     static_assert(NP == 3 || NP == 1, "three products (f16x3) or one (the autocast policy)");
     static_assert(!CAT || XDT == MPHIP_DTYPE_F32, "the two-source form stages fp32 sources");
+    static_assert(UP == 0 || (!CAT && XDT == MPHIP_DTYPE_F32 && YDT == MPHIP_DTYPE_F32 && NP == 3), "the up2 forms: one fp32 source, three products");
     constexpr int NPART = NP == 3 ? 2 : 1;                   // operand halves in LDS: hi and lo, or hi alone
     constexpr int W_HALFS = C2_SLAB_HALFS / 2 * NPART;       // of a slab, the planes this kernel fetches
     __shared__ __attribute__((aligned(16))) _Float16 smem[W_HALFS + NPART * C2_X_PART];
     __shared__ unsigned red[4];
     float *const affs = c2_affine_lds<CAT>();
+    float *const ups = c2_up2_lds<UP>();   // UP = 1: patch, row table, column table
     _Float16 *const Ws = smem;             // [part][tap][kg][co][8]
     _Float16 *const Xs = smem + W_HALFS;   // [part][kg][pixel][8]
 
@@ -120,7 +170,10 @@ __device__ __forceinline__ void conv2d_k3_tile(const dtype_t<XDT> *__restrict__ 
     const int nchunks = nch1 + (CAT ? cat.C2 / C2_KC : 0);
     const size_t HW = (size_t)H * W;
     const unsigned HWu = (unsigned)HW;   // (a chunk's 16 channels hold fewer than 2^31 elements: 32-bit element offsets)
-    const dtype_t<XDT> *const xn = x + (size_t)n * Ci * HW;
+    const int xh = H >> 1, xw = W >> 1;                                 // UP = 1: the source map ...
+    const size_t XHW = UP == 1 ? (size_t)xh * xw : HW;                  // ... and a channel of it (else the map itself)
+    const int pr0 = h0 ? (h0 >> 1) - 1 : 0, pc0 = w0 ? (w0 >> 1) - 1 : 0;   // UP = 1: the patch's first row and column (i0 of the halo's first)
+    const dtype_t<XDT> *const xn = x + (size_t)n * Ci * XHW;
     const float *const x2n = CAT && cat.C2 ? cat.x2 + (size_t)n * cat.C2 * HW : nullptr;
 
     // X staging: an item is (channel pair p, halo pixel r): two 4-byte loads (the zero padding and the ragged edge are the mask), scale,
@@ -134,13 +187,14 @@ __device__ __forceinline__ void conv2d_k3_tile(const dtype_t<XDT> *__restrict__ 
     static_assert(C2_SLAB_HALFS * 2 % (16 * C2_NTHR) == 0, "weight slab / thread count");
     static_assert(C2_NTHR % 4 == 0, "a thread's items all belong to channel pair (tid & 3) of their k group");
     dtype_t<XDT> xa[XI], xb[XI];   // as loaded: widened when written to LDS
+    float pv[UP == 1 ? C2_UP_PI : 1];   // UP = 1: the chunk's patch, from its loads to LDS, instead of xa / xb
     float affv = 0.0f;   // CAT: lanes 0-31 carry the next chunk's table entries from its loads to LDS
     typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
     u32x4 wq[WI];
     unsigned sat = 0, okm = 0;
 #define C2_LOAD_CHUNK(c_)                                                                              \
     {                                                                                                  \
-        const dtype_t<XDT> *xc_ = xn + (size_t)(c_) * C2_KC * HW;                                      \
+        const dtype_t<XDT> *xc_ = xn + (size_t)(c_) * C2_KC * XHW;                                     \
         if constexpr (CAT) {                                                                           \
             const bool first_ = (c_) < nch1;   /* workgroup-uniform */                                 \
             if (!first_) xc_ = x2n + (size_t)((c_) - nch1) * C2_KC * HW;                               \
@@ -150,6 +204,14 @@ __device__ __forceinline__ void conv2d_k3_tile(const dtype_t<XDT> *__restrict__ 
         }                                                                                              \
         int tid_ = tid;                                                                                \
         asm volatile("" : "+v"(tid_)); /* opaque: keeps the per-item offsets out of registers across the K loop */ \
+        if constexpr (UP == 1) {   /* the patch: rows and columns clamped at the source map's last */  \
+            _Pragma("unroll") for (int i = 0; i < C2_UP_PI; ++i) {                                     \
+                const int e_ = min(i * C2_NTHR + tid_, C2_UP_PATCH - 1), q_ = e_ % C2_UP_CS;           \
+                const unsigned off_ = (unsigned)(e_ / C2_UP_CS) * (unsigned)XHW + (unsigned)min(pr0 + q_ / C2_UP_P, xh - 1) * xw + \
+                                      min(pc0 + q_ % C2_UP_P, xw - 1);                                 \
+                pv[i] = xc_[off_];                                                                     \
+            }                                                                                          \
+        } else {                                                                                       \
         _Pragma("unroll") for (int i = 0; i < XI; ++i) {                                               \
             const int e_ = i * C2_NTHR + tid_, ec_ = min(e_, NX - 1);                                  \
             const int rest_ = ec_ >> 2;                                                                \
@@ -162,6 +224,7 @@ __device__ __forceinline__ void conv2d_k3_tile(const dtype_t<XDT> *__restrict__ 
             xb[i] = xc_[off_ + HWu];                                                                   \
             okm = ok_ ? okm | (1u << i) : okm & ~(1u << i);   /* the select waits until the values are written to LDS */ \
         }                                                                                              \
+        }                                                                                              \
         /* opaque: with a third of the MFMAs hipcc else keeps the 11 lane masks in scalar pairs and spills kernel arguments */ \
         if constexpr (NP == 1) asm volatile("" : "+v"(okm));                                           \
         const u32x4 *const ws_ = reinterpret_cast<const u32x4 *>(wslabs + ((size_t)cot * nchunks + (c_)) * C2_SLAB_HALFS); \
@@ -173,6 +236,10 @@ __device__ __forceinline__ void conv2d_k3_tile(const dtype_t<XDT> *__restrict__ 
 #define C2_PARK_AFFINE()                                                                               \
     if constexpr (CAT) {                                                                               \
         if (tid < 2 * C2_KC) affs[tid] = affv;                                                         \
+    }                                                                                                  \
+    if constexpr (UP == 1) {   /* the loaded chunk's patch, under the same two barriers */             \
+        _Pragma("unroll") for (int i = 0; i < C2_UP_PI; ++i)                                           \
+            if (i * C2_NTHR + tid < C2_UP_PATCH) ups[i * C2_NTHR + tid] = pv[i];                       \
     }
 #define C2_WRITE_CHUNK(c_)                                                                             \
     {                                                                                                  \
@@ -193,8 +260,22 @@ __device__ __forceinline__ void conv2d_k3_tile(const dtype_t<XDT> *__restrict__ 
             const int e_ = i * C2_NTHR + tid_;                                                         \
             if (e_ < NX) {                                                                             \
                 const int dst_ = (e_ >> 2) * 8 + (e_ & 3) * 2;   /* e_ >> 2 = kg * C2_XV + pixel */    \
-                const bool ok_ = (okm >> i) & 1u;                                                      \
-                float a_ = widen(xa[i]), b_ = widen(xb[i]);                                            \
+                bool ok_;                                                                              \
+                float a_, b_;                                                                          \
+                if constexpr (UP == 1) {   /* the halo pixel's two table entries, four patch values per channel */ \
+                    const int rest_ = e_ >> 2, r_ = rest_ % C2_XV;                                     \
+                    const u32x4 rt_ = *reinterpret_cast<const u32x4 *>(ups + C2_UP_PATCH + (r_ / C2_HW) * 4);           \
+                    const u32x4 ct_ = *reinterpret_cast<const u32x4 *>(ups + C2_UP_PATCH + (C2_HH + r_ % C2_HW) * 4);   \
+                    const float *const pa_ = ups + (2 * ((rest_ / C2_XV) * 4 + (e_ & 3))) * C2_UP_CS;  \
+                    const float lam_ = __uint_as_float(rt_[2]), mu_ = __uint_as_float(ct_[2]);         \
+                    const unsigned o00_ = rt_[0] + ct_[0], o01_ = rt_[0] + ct_[1], o10_ = rt_[1] + ct_[0], o11_ = rt_[1] + ct_[1]; \
+                    a_ = up2_blend(pa_[o00_], pa_[o01_], pa_[o10_], pa_[o11_], mu_, lam_);             \
+                    b_ = up2_blend(pa_[C2_UP_CS + o00_], pa_[C2_UP_CS + o01_], pa_[C2_UP_CS + o10_], pa_[C2_UP_CS + o11_], mu_, lam_); \
+                    ok_ = (rt_[3] & ct_[3]) != 0;   /* outside the up-sampled map: a zero of that map */ \
+                } else {                                                                               \
+                    ok_ = (okm >> i) & 1u;                                                             \
+                    a_ = widen(xa[i]), b_ = widen(xb[i]);                                              \
+                }                                                                                      \
                 if constexpr (CAT) {                                                                   \
                     if (aff_on_) {                                                                     \
                         /* the item's k group: known at compile time except for the one i that straddles 4 * C2_XV */ \
@@ -246,8 +327,22 @@ __device__ __forceinline__ void conv2d_k3_tile(const dtype_t<XDT> *__restrict__ 
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[m][t][r] = 0.0f;
 
+    if constexpr (UP == 1) {   // the two tables: thread k < 18 halo row k, thread 18 + k halo column k
+        if (tid < 2 * C2_HH) {
+            const bool col = tid >= C2_HH;
+            const int L = col ? W : H, g = (col ? w0 : h0) - 1 + (col ? tid - C2_HH : tid);
+            int i0, i1;
+            float lam;
+            up2_coord(min(max(g, 0), L - 1), L >> 1, i0, i1, lam);
+            // (both rows lie inside the patch, see C2_UP_P; the clamp keeps every offset inside it whatever the arguments)
+            const int base = col ? pc0 : pr0, step = col ? 1 : C2_UP_P;
+            const u32x4 ent = {(unsigned)(min(max(i0 - base, 0), C2_UP_P - 1) * step), (unsigned)(min(max(i1 - base, 0), C2_UP_P - 1) * step),
+                               __float_as_uint(lam), (unsigned)g < (unsigned)L ? 1u : 0u};
+            *reinterpret_cast<u32x4 *>(ups + C2_UP_PATCH + tid * 4) = ent;
+        }
+    }
     C2_LOAD_CHUNK(0)
-    if constexpr (CAT) {
+    if constexpr (CAT || UP == 1) {
         C2_PARK_AFFINE()
         __syncthreads();
     }
@@ -302,6 +397,19 @@ __device__ __forceinline__ void conv2d_k3_tile(const dtype_t<XDT> *__restrict__ 
     // epilogue: unscale (a power of two), bias, residual, ReLU in fp32; stores masked at the ragged edge and past Co
     const float unscale = whdr[0] * x_unscale;
     unsigned ymax = 0;
+    unsigned ro[2][4];          // UP = 2: this lane's four offsets into a channel of r, per column tile, ...
+    float rlam[2], rmu = 0.0f;  // ... and its weights
+    if constexpr (UP == 2) {
+        int j0, j1;
+        up2_coord(min(w0 + pcol, W - 1), xw, j0, j1, rmu);
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+            int i0, i1;
+            up2_coord(min(h0 + prow + 2 * t, H - 1), xh, i0, i1, rlam[t]);
+            ro[t][0] = (unsigned)i0 * xw + j0, ro[t][1] = (unsigned)i0 * xw + j1;
+            ro[t][2] = (unsigned)i1 * xw + j0, ro[t][3] = (unsigned)i1 * xw + j1;
+        }
+    }
 #pragma unroll
     for (int m = 0; m < 2; ++m) {
         const int co0 = cot * C2_COT + m * 32;
@@ -316,7 +424,12 @@ __device__ __forceinline__ void conv2d_k3_tile(const dtype_t<XDT> *__restrict__ 
                         const int row = (reg & 3) + 8 * (reg >> 2);
                         const size_t oi = o + (size_t)row * HW;
                         float v = acc[m][t][reg] * unscale + bias[co0 + 4 * kg + row];
-                        if (residual) v += residual[oi];
+                        if constexpr (UP == 2) {   // + up2(r): the blend, then one add
+                            const float *const rc = residual + ((size_t)n * Co + co0 + 4 * kg + row) * ((size_t)xh * xw);
+                            v += up2_blend(rc[ro[t][0]], rc[ro[t][1]], rc[ro[t][2]], rc[ro[t][3]], rmu, rlam[t]);
+                        } else {
+                            if (residual) v += residual[oi];
+                        }
                         if constexpr (YDT != MPHIP_DTYPE_F32) {
                             if (residual_t) v += widen(residual_t[oi]);   // (workgroup-uniform; at most one of the two is set)
                         }

@@ -116,7 +116,8 @@ void conv2d_lp_launch(const C2Call &c, const C2Grid &g) {
 }
 
 // The host side of every 2-D 3x3 conv entry (the stride-2 entry of conv2d_s2_f16x3.hip included: c.stride == 2, extents of y and
-// residual from the halved map).  The rules in the order they are checked, all before the first HIP call: dtypes and
+// residual from the halved map; and the two of conv2d_up2_f16x3.hip: c.up2 == 1, y and residual on the doubled map, c.up2 == 2, the
+// residual on the halved one).  The rules in the order they are checked, all before the first HIP call: dtypes and
 // products (lp_rule), pointers, the second source, the shape, alignment, tables, aliasing (MPHIP_EINVAL each), then the workspace
 // (MPHIP_EWORKSPACE).  Messages carry the called entry's name; a three-product call (all of its maps are fp32) is the fp32 entry's call
 // under whichever name it came in, and reports under that entry's name.
@@ -128,14 +129,18 @@ int conv2d_run(C2Call c) {
     c.products = np;
     const bool s2 = c.stride == 2;
     MPHIP_REQUIRE(!s2 || (!c.cat && np == 3), "%s: the stride-2 conv is the plain fp32 three-product form", c.who);
-    const char *who = s2 ? c.who : c.products == 3 ? (c.cat ? "conv2d_cat_fwd" : "conv2d_fwd") : c.who;
-    MPHIP_REQUIRE(c.x1 && c.w_packed && c.bias && c.y, "%s: null pointer", who);
+    const int up = c.up2;
+    MPHIP_REQUIRE(up == 0 || ((up == 1 || up == 2) && !s2 && !c.cat && np == 3), "%s: the up2 convs are plain fp32 three-product forms", c.who);
+    const char *who = s2 || up ? c.who : c.products == 3 ? (c.cat ? "conv2d_cat_fwd" : "conv2d_fwd") : c.who;
+    MPHIP_REQUIRE(c.x1 && c.w_packed && c.bias && c.y && (up != 2 || c.residual), "%s: null pointer", who);
     MPHIP_REQUIRE(c.C2 >= 0 && (c.x2 != nullptr) == (c.C2 > 0), "%s: x2 and C2 = %d: a second source needs both, one source neither", who, c.C2);
-    MPHIP_REQUIRE(s2      ? c2_s2_supported(c.N, c.C1, c.Co, c.H, c.W)
-                  : c.cat ? mphip_conv2d_cat_supported(c.N, c.C1, c.C2, c.Co, c.H, c.W)
+    MPHIP_REQUIRE(s2        ? c2_s2_supported(c.N, c.C1, c.Co, c.H, c.W)
+                  : up == 1 ? c2_up2_supported(c.N, c.C1, c.Co, c.H, c.W)
+                  : c.cat   ? mphip_conv2d_cat_supported(c.N, c.C1, c.C2, c.Co, c.H, c.W)
                           : mphip_conv2d_supported(c.N, c.C1, c.Co, c.H, c.W),
                   "%s: unsupported shape N=%d C1=%d C2=%d Co=%d H=%d W=%d (C1 %% 16 == 0, C2 %% 16 == 0, Co %% 32 == 0, N, H, W >= 1, fewer than "
                   "2^31 elements per tensor)", who, c.N, c.C1, c.C2, c.Co, c.H, c.W);
+    MPHIP_REQUIRE(up != 2 || (c.H % 2 == 0 && c.W % 2 == 0), "%s: H = %d, W = %d: the map of an up-sampled residual has even extents", who, c.H, c.W);
     const size_t xb = lp_dtype_bytes(c.x_dtype), yb = lp_dtype_bytes(c.y_dtype), rb = lp_dtype_bytes(c.residual_dtype);
     MPHIP_REQUIRE(((uintptr_t)c.w_packed & 15) == 0 && ((uintptr_t)c.x1 & (xb - 1)) == 0 && ((uintptr_t)c.x2 & 3) == 0 &&
                       ((uintptr_t)c.y & (yb - 1)) == 0 && ((uintptr_t)c.residual & (rb - 1)) == 0,
@@ -144,10 +149,11 @@ int conv2d_run(C2Call c) {
     // the bound of a normalised source is not the maximum of its raw values: a scan of x would give the wrong operand scale
     MPHIP_REQUIRE(!c.aff1 || c.x1_range, "%s: affine1 without x1_range (mphip_groupnorm_affine_table makes both)", who);
     MPHIP_REQUIRE(!c.aff2 || (c.x2 && c.x2_range), "%s: affine2 without x2 / x2_range (mphip_groupnorm_affine_table makes both)", who);
-    const int Ho = s2 ? (c.H + 1) / 2 : c.H, Wo = s2 ? (c.W + 1) / 2 : c.W;   // the map of y and residual
+    const int Ho = s2 ? (c.H + 1) / 2 : up == 1 ? 2 * c.H : c.H, Wo = s2 ? (c.W + 1) / 2 : up == 1 ? 2 * c.W : c.W;   // the map of y and residual
     const size_t hw = (size_t)c.H * c.W, n1 = (size_t)c.N * c.C1 * hw, n2 = (size_t)c.N * c.C2 * hw, ny = (size_t)c.N * c.Co * Ho * Wo;
+    const size_t nr = up == 2 ? ny / 4 : ny;   // (an up-sampled residual lives on the halved map)
     MPHIP_REQUIRE(!c2_overlap(c.y, ny * yb, c.x1, n1 * xb) && !c2_overlap(c.y, ny * yb, c.x2, n2 * sizeof(float)) &&
-                      !c2_overlap(c.y, ny * yb, c.residual, ny * rb),
+                      !c2_overlap(c.y, ny * yb, c.residual, nr * rb),
                   "%s: y must not alias a source or residual (a workgroup reads the halo of tiles other workgroups write)", who);
     const bool scan1 = !c.x1_range, scan2 = c.x2 && !c.x2_range;
     if (scan1 || scan2) {
@@ -179,6 +185,7 @@ int conv2d_run(C2Call c) {
     g.nslots = (unsigned)std::min<long long>(tiles * c2_cots(c.Co), (long long)RANGE_MAX_PARTS);
     if (c.out_range) conv2d_out_range_init_launch(c.out_range, g.nslots, c.stream);
     if (s2) conv2d_s2_launch(c, g);
+    else if (up) conv2d_up2_launch(c, g);
     else if (c.products == 1) conv2d_lp_launch(c, g);
     else if (c.cat) conv2d_cat_launch(c, g);
     else conv2d_plain_launch(c, g);

@@ -76,7 +76,7 @@ def patch_functions(model_module) -> List[str]:
 
 
 def install(gbase: nn.Module, model_module: Optional[object] = None, eapp_tail: bool = True, g2d_final: bool = False,
-            g2d_body: bool = False, eapp_trunk: bool = False, half_precision: bool = False) -> List[str]:
+            g2d_body: bool = False, eapp_trunk: bool = False, half_precision: bool = False, fuse_upsample: bool = False) -> List[str]:
     """swap_hot_path + patch_functions.  `model_module` is the imported reference `model` module (the one that defines
     Gbase); pass it so the two `apply_warping_field` call sites inside Gbase.forward use the HIP kernel too.
     g2d_final (off by default): also swap `gbase.G2d.final_conv` (model.py:747-752) for model.G2dFinalConv, which shares the
@@ -85,11 +85,13 @@ def install(gbase: nn.Module, model_module: Optional[object] = None, eapp_tail: 
     eapp_trunk (off by default): also swap `gbase.appearanceEncoder.resblock_128 / _256 / _512` (model.py:210-212) for
     model.ResBlockCustomFused (inference only; model.native_eapp_trunk).
     half_precision (off by default): g2d_body / eapp_trunk blocks get their half-precision form — one f16 product per multiply and half
-    outputs inside torch.autocast(float16) and as .half() / .bfloat16() modules (model.ResBlock2DFused)."""
+    outputs inside torch.autocast(float16) and as .half() / .bfloat16() modules (model.ResBlock2DFused).
+    fuse_upsample (off by default): with g2d_body, G2d's three `Sequential(Upsample, ResBlock2D)` stages become model.Up2ResBlock2DFused,
+    the bilinear x2 up-sample folded into the block's convs; with half_precision=True they keep the materialised up-sample."""
     done = swap_hot_path(gbase, eapp_tail=eapp_tail)
     if g2d_final and M.native_final_conv(gbase.G2d, True):
         done.append("G2d.final_conv")
-    if g2d_body and M.native_g2d_body(gbase.G2d, True, half_precision):
+    if g2d_body and M.native_g2d_body(gbase.G2d, True, half_precision, fuse_upsample):
         done.append("G2d.body")
     if eapp_trunk and M.native_eapp_trunk(getattr(gbase, "appearanceEncoder", None), True, half_precision):
         done.append("Eapp.trunk2d")

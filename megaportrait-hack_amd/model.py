@@ -954,6 +954,102 @@ class ResBlock2DFused(_FusedBlock2D):
         return ops.conv2d(y1, p2, residual=idt, relu=True, want_range=True, out_dtype=out_dtype, products=products)
 
 
+def _up2_axis(l: int, device):
+    """Rows (or columns) of up2 for a map with l of them -> (i0, i1 int64 [2l], lambda fp32 [2l]): num = i (l - 1), den = 2l - 1 (l == 1:
+    num = 0, den = 1), i0 = num div den, lambda = float(num mod den) / float(den) (one fp32 division, on the host: IEEE), i1 = min(i0 + 1, l - 1)."""
+    i = torch.arange(2 * l, dtype=torch.int64)
+    num, den = i * (l - 1), 2 * l - 1
+    i0 = num // den
+    lam = (num % den).to(torch.float32) / torch.tensor(den, dtype=torch.float32)
+    return i0.to(device), torch.clamp(i0 + 1, max=l - 1).to(device), lam.to(device)
+
+
+def up2_reference(x: torch.Tensor) -> torch.Tensor:
+    """nn.Upsample(scale_factor=2, mode="bilinear", align_corners=True) of x [N,C,h,w] -> [N,C,2h,2w] as the kernels of
+    csrc/conv2d_up2_f16x3.hip compute it: exact integer coordinates (_up2_axis), horizontal first,
+        top = x[i0,j0] (1 - mu) + x[i0,j1] mu,   bot = x[i1,j0] (1 - mu) + x[i1,j1] mu,   u = top (1 - lambda) + bot lambda,
+    every product, sum and 1 - . a torch operation of its own (`*`, `+`, `-`: nothing that may fuse), so each is rounded to fp32 once.
+    ops.conv2d_up2 / ops.conv2d_resup2 reproduce conv2d(up2_reference(x)) / conv2d(x, residual=up2_reference(r)) bit for bit."""
+    if x.dim() != 4 or not x.is_floating_point():
+        raise RuntimeError(f"up2_reference: expected a floating-point [N,C,h,w] map, got {tuple(x.shape)} {x.dtype}")
+    h, w = x.shape[2:]
+    i0, i1, lam = _up2_axis(h, x.device)
+    j0, j1, mu = _up2_axis(w, x.device)
+    lam, mu = lam.to(x.dtype)[:, None], mu.to(x.dtype)
+    ol, om = torch.ones_like(lam) - lam, torch.ones_like(mu) - mu
+    r0, r1 = x[:, :, i0], x[:, :, i1]
+    top = r0[:, :, :, j0] * om + r0[:, :, :, j1] * mu
+    bot = r1[:, :, :, j0] * om + r1[:, :, :, j1] * mu
+    return top * ol + bot * lam
+
+
+def _is_up2(m) -> bool:
+    """Exactly nn.Upsample(scale_factor=2, mode="bilinear", align_corners=True)?"""
+    if not isinstance(m, nn.Upsample) or m.size is not None or m.mode != "bilinear" or m.align_corners is not True:
+        return False
+    if getattr(m, "recompute_scale_factor", None):
+        return False
+    sf = m.scale_factor
+    return sf is not None and all(float(s) == 2.0 for s in (sf if isinstance(sf, (tuple, list)) else (sf, sf))) and (
+        not isinstance(sf, (tuple, list)) or len(sf) == 2)
+
+
+class Up2ResBlock2DFused(nn.Sequential):
+    """A whole `nn.Sequential(nn.Upsample(scale_factor=2, mode="bilinear", align_corners=True), ResBlock2D)` stage of G2d with the
+    up-sample folded into the block's convs (csrc/conv2d_up2_f16x3.hip): the up-sampled map is never written.  Positions 0 and 1 hold
+    the very Upsample object and the block (a ResBlock2DFused over the original block's children, whose fold cache and conditions this
+    class uses): every state-dict key, module name and Parameter object stays.
+
+    Native path (eval mode, no autograd, an fp32 block with a 1x1 shortcut, a supported shape):
+        s   = shortcut'(x)                       at LOW resolution, through the k = 1 conv: a 1x1 conv and a bilinear resample commute
+        y1  = ops.conv2d_up2(x, conv1', relu)    conv1 reads up2(x), blended while it is staged
+        out = ops.conv2d_resup2(y1, conv2', s, relu)     conv2 adds up2(s), blended in its epilogue
+    with x's own range descriptor as the bound of up2(x).  The commuted shortcut changes the rounding order: against the unfused stage
+    this is an accuracy contract (fp32-class, like the block's), not a bitwise one.  Everything else — train mode, autograd, a half
+    model, a block built with half_precision=True — evaluates exactly the two modules in order."""
+
+    @staticmethod
+    def matches(seq) -> bool:
+        if not isinstance(seq, nn.Sequential) or isinstance(seq, Up2ResBlock2DFused) or len(seq) != 2 or not _is_up2(seq[0]):
+            return False
+        blk = seq[1]
+        return (isinstance(blk, ResBlock2DFused) or ResBlock2DFused.matches(blk)) and isinstance(blk.shortcut, nn.Sequential)
+
+    @classmethod
+    def from_sequential(cls, seq: nn.Sequential) -> "Up2ResBlock2DFused":
+        if not cls.matches(seq):
+            raise TypeError(f"{cls.__name__}.from_sequential: expected Sequential(Upsample(scale_factor=2, bilinear, align_corners=True), "
+                            f"a ResBlock2D with a 1x1 shortcut), got {seq}")
+        blk = seq[1] if isinstance(seq[1], ResBlock2DFused) else ResBlock2DFused.from_block(seq[1])
+        new = cls(seq[0], blk)
+        new.training = seq.training
+        return new
+
+    def _native_ok(self, x) -> bool:
+        blk = self[1]
+        if not isinstance(blk, ResBlock2DFused) or "_mphip_half" in blk.__dict__ or not isinstance(blk.shortcut, nn.Sequential):
+            return False
+        if blk.training or ag.needs_grad(blk, x) or blk._dtypes(False) != {torch.float32}:
+            return False
+        if not (isinstance(x, torch.Tensor) and x.dim() == 4 and x.numel() > 0 and x.is_floating_point()):
+            return False
+        (n, ci, h, w), co = x.shape, blk.conv1.out_channels
+        return ci == blk.conv1.in_channels and ops.conv2d_up2_supported(n, ci, co, h, w) and ops.conv2d_up2_supported(n, co, co, h, w)
+
+    def forward(self, x):
+        if not self._native_ok(x):
+            return self[1](self[0](x))
+        p1, p2, ps = self[1]._folded()
+        xc = _f32(x).contiguous()   # (the kernels read NCHW: a channels_last map is copied once)
+        n, c, h, w = xc.shape
+        xr = ops.current_range(xc)
+        if xr is None:
+            xr = ops.absmax_range(xc)   # one scan of the LOW-resolution map serves the shortcut and conv1: a bound of up2(x)
+        s = ops.conv3d(xc.reshape(n, c, 1, h, w), ps, x_range=xr).reshape(n, ps.co, h, w)
+        y1 = ops.conv2d_up2(xc, p1, relu=True, x_range=xr, want_range=True)
+        return ops.conv2d_resup2(y1, p2, s, relu=True, want_range=True)
+
+
 def _is_conv2d_at(m, k: int, stride: int) -> bool:
     """_is_conv2d at a given stride, and with or without a bias (BasicBlockFused's convs)."""
     return (isinstance(m, nn.Conv2d) and m.kernel_size == (k, k) and m.stride == (stride, stride) and m.padding == ((k - 1) // 2,) * 2
@@ -1081,13 +1177,24 @@ def _swap_slot(cls, cur, enable: bool, half_precision: bool):
 _G2D_BODY_SLOTS = (("upsample1", 1), ("upsample2", 1), ("upsample3", 1))
 
 
-def native_g2d_body(g2d: nn.Module, enable: bool = True, half_precision: bool = False) -> bool:
+def native_g2d_body(g2d: nn.Module, enable: bool = True, half_precision: bool = False, fuse_upsample: bool = False) -> bool:
     """Swaps every matching ResBlock2D of `g2d.res_blocks`, `g2d.upsample1[1]`, `upsample2[1]`, `upsample3[1]` (this package's G2d or
     the reference's, model.py:720-746) for a ResBlock2DFused over the same children, or puts the very objects it replaced back.
     Returns whether anything changed.  Off by default everywhere.  half_precision: the blocks' half-precision form (ResBlock2DFused);
-    blocks that are fused already take the keyword's value."""
-    seqs = [(getattr(g2d, "res_blocks", None), None)] + [(getattr(g2d, name, None), idx) for name, idx in _G2D_BODY_SLOTS]
+    blocks that are fused already take the keyword's value.
+    fuse_upsample (off by default): each matching `Sequential(Upsample x2 bilinear align_corners, block)` of `upsample1/2/3` also becomes
+    an Up2ResBlock2DFused over the same two objects, which folds the up-sample into the block's convs; without the keyword (or with
+    enable off) the very Sequential objects come back.  With half_precision=True the three stages keep the materialised up-sample:
+    there is no typed or one-product form of the up2 kernels."""
+    fuse = bool(enable and fuse_upsample and not half_precision)
     changed = False
+    if not fuse:   # (first: the slots below are looked up in the Sequentials that hold them)
+        for name, _ in _G2D_BODY_SLOTS:
+            cur = getattr(g2d, name, None)
+            if isinstance(cur, Up2ResBlock2DFused) and "_replaced" in cur.__dict__:
+                setattr(g2d, name, cur.__dict__.pop("_replaced"))
+                changed = True
+    seqs = [(getattr(g2d, "res_blocks", None), None)] + [(getattr(g2d, name, None), idx) for name, idx in _G2D_BODY_SLOTS]
     for seq, only in seqs:
         if not isinstance(seq, nn.Sequential):
             continue
@@ -1096,6 +1203,14 @@ def native_g2d_body(g2d: nn.Module, enable: bool = True, half_precision: bool = 
             if new is not seq[i]:
                 seq[i] = new
             changed |= did
+    if fuse:
+        for name, _ in _G2D_BODY_SLOTS:
+            cur = getattr(g2d, name, None)
+            if Up2ResBlock2DFused.matches(cur) and isinstance(cur[1], ResBlock2DFused):
+                new = Up2ResBlock2DFused.from_sequential(cur)
+                new.__dict__["_replaced"] = cur   # (not a registered child: the module tree and the state-dict keys stay as they were)
+                setattr(g2d, name, new)
+                changed = True
     return changed
 
 

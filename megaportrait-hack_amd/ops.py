@@ -1271,22 +1271,25 @@ def conv2d(x: torch.Tensor, pack: PackedConv2d, residual: Optional[torch.Tensor]
 
 
 def _conv2d_launch(who, typed, pack, x1, aff1, r1, relu1, x2, aff2, r2, relu2, residual, relu, want_range, out_dtype, products):
-    """What ops.conv2d (who = "conv2d": the plain kernels), ops.conv2d_cat and ops.conv2d_s2 (the stride-2 kernel: y and residual on the
-    halved map) share once their sources are checked and the descriptors r1 / r2 chosen: the residual check, the workspace, y and
-    out_range, and the call of the fp32 or (`typed`) the typed entry."""
+    """What ops.conv2d (who = "conv2d": the plain kernels), ops.conv2d_cat, ops.conv2d_s2 (the stride-2 kernel: y and residual on the
+    halved map), ops.conv2d_up2 (y and residual on the doubled map) and ops.conv2d_resup2 (the residual on the halved map) share once
+    their sources are checked and the descriptors r1 / r2 chosen: the residual check, the workspace, y and out_range, and the call of
+    the fp32 or (`typed`) the typed entry."""
     cat = who == "conv2d_cat"
     lib = _lib.load()
     n, c1, h, w = x1.shape
     c2 = 0 if x2 is None else int(x2.shape[1])
-    ho, wo = ((h + 1) // 2, (w + 1) // 2) if who == "conv2d_s2" else (h, w)
+    ho, wo = ((h + 1) // 2, (w + 1) // 2) if who == "conv2d_s2" else (2 * h, 2 * w) if who == "conv2d_up2" else (h, w)
     if residual is not None:
         residual = _req_typed(residual, "residual") if typed else _req(residual, "residual")
-        if tuple(residual.shape) != (n, pack.co, ho, wo):
-            raise RuntimeError(f"{who}: residual {tuple(residual.shape)} does not match the output {(n, pack.co, ho, wo)}")
+        rshape = (n, pack.co, h // 2, w // 2) if who == "conv2d_resup2" else (n, pack.co, ho, wo)
+        if tuple(residual.shape) != rshape:
+            raise RuntimeError(f"{who}: residual {tuple(residual.shape)} does not match {rshape}, the output{' at half its size' if who == 'conv2d_resup2' else ''}")
     ws_bytes = 0
     if r1 is None or (x2 is not None and r2 is None):   # a source to scan
+        ws_name = "conv2d" if who == "conv2d_resup2" else who
         ws_bytes = (lib.mphip_conv2d_cat_workspace_bytes(n, c1, c2, pack.co, h, w) if cat
-                    else getattr(lib, f"mphip_{who}_workspace_bytes")(n, c1, pack.co, h, w))
+                    else getattr(lib, f"mphip_{ws_name}_workspace_bytes")(n, c1, pack.co, h, w))
     ws = torch.empty((ws_bytes + 3) // 4, dtype=torch.float32, device=x1.device) if ws_bytes else None
     ydt = torch.float32 if out_dtype is None else out_dtype
     y = torch.empty((n, pack.co, ho, wo), dtype=ydt, device=x1.device)
@@ -1325,6 +1328,46 @@ def conv2d_s2(x: torch.Tensor, pack: PackedConv2d, residual: Optional[torch.Tens
         raise RuntimeError(f"conv2d_s2: unsupported shape N={n} Ci={ci} Co={pack.co} H={h} W={w} (there is no fallback)")
     xr = x_range if x_range is not None else current_range(x)   # None: the library scans x
     return _conv2d_launch("conv2d_s2", False, pack, x, None, xr, False, None, None, None, False, residual, relu, want_range, None, None)
+
+
+def conv2d_up2_supported(n: int, ci: int, co: int, h: int, w: int) -> bool:
+    """Does ops.conv2d_up2 take an [n, ci, h, w] input (h, w: the LOW-resolution map) with co output channels, which is also whether
+    ops.conv2d_resup2 takes an [n, ci, 2h, 2w] one (mphip_conv2d_up2_supported: the rule of ops.conv2d on the doubled map)?"""
+    return bool(_lib.load().mphip_conv2d_up2_supported(int(n), int(ci), int(co), int(h), int(w)))
+
+
+def conv2d_up2(x: torch.Tensor, pack: PackedConv2d, residual: Optional[torch.Tensor] = None, relu: bool = False,
+               x_range: Optional[torch.Tensor] = None, want_range: bool = False) -> torch.Tensor:
+    """y = act(conv3x3(up2(x)) + bias (+ residual)) on NCHW fp32, padding 1 (mphip_conv2d_up2_fwd): x is [N, Ci, h, w], y and residual
+    are [N, Co, 2h, 2w], up2 = F.interpolate(scale_factor=2, mode="bilinear", align_corners=True) as model.up2_reference states it,
+    blended while the conv stages its input: the up-sampled map is never written.  x_range: the descriptor of the LOW-resolution x (a
+    bound of up2(x)); without one the descriptor tagged on x is used, else the library scans x.  With the same x_range and pack the
+    result is, bit for bit, conv2d(model.up2_reference(x), ...).  fp32 only."""
+    x = _req(x, "x")
+    if x.dim() != 4 or x.shape[1] != pack.ci:
+        raise RuntimeError(f"conv2d_up2: input {tuple(x.shape)} does not match Ci={pack.ci}")
+    n, ci, h, w = x.shape
+    if not _lib.load().mphip_conv2d_up2_supported(n, ci, pack.co, h, w):
+        raise RuntimeError(f"conv2d_up2: unsupported shape N={n} Ci={ci} Co={pack.co} h={h} w={w} (there is no fallback)")
+    xr = x_range if x_range is not None else current_range(x)   # None: the library scans x
+    return _conv2d_launch("conv2d_up2", False, pack, x, None, xr, False, None, None, None, False, residual, relu, want_range, None, None)
+
+
+def conv2d_resup2(x: torch.Tensor, pack: PackedConv2d, residual_lowres: torch.Tensor, relu: bool = False,
+                  x_range: Optional[torch.Tensor] = None, want_range: bool = False) -> torch.Tensor:
+    """y = act(conv3x3(x) + bias + up2(residual_lowres)) on NCHW fp32, padding 1 (mphip_conv2d_resup2_fwd): x is [N, Ci, H, W] with H
+    and W even, residual_lowres [N, Co, H/2, W/2]; its up-sampled map is blended in the epilogue and never written.  Bit for bit
+    conv2d(x, pack, residual=model.up2_reference(residual_lowres), ...).  fp32 only."""
+    x = _req(x, "x")
+    if x.dim() != 4 or x.shape[1] != pack.ci:
+        raise RuntimeError(f"conv2d_resup2: input {tuple(x.shape)} does not match Ci={pack.ci}")
+    n, ci, h, w = x.shape
+    if h % 2 or w % 2 or not _lib.load().mphip_conv2d_supported(n, ci, pack.co, h, w):
+        raise RuntimeError(f"conv2d_resup2: unsupported shape N={n} Ci={ci} Co={pack.co} H={h} W={w} (H and W even; there is no fallback)")
+    if residual_lowres is None:
+        raise RuntimeError("conv2d_resup2: residual_lowres is required")
+    xr = x_range if x_range is not None else current_range(x)   # None: the library scans x
+    return _conv2d_launch("conv2d_resup2", False, pack, x, None, xr, False, None, None, None, False, residual_lowres, relu, want_range, None, None)
 
 
 _GN_UNIT = {}   # (device, C) -> (ones, zeros): gamma and beta of a GroupNorm without parameters

@@ -46,6 +46,9 @@ def parse(argv=None):
     ap.add_argument("--native-g2d-body", action="store_true",
                     help="run G2d's ResBlock2D body with BatchNorm folded and its 3x3 convs on the matrix cores "
                          "(gbase.Gbase.native_body; inference only, fp32 models; off by default)")
+    ap.add_argument("--native-fuse-upsample", action="store_true",
+                    help="with --native-g2d-body: fold G2d's three bilinear x2 up-samples into the convs that follow them, the up-sampled "
+                         "maps are never written (fp32 only: ignored with --native-half-precision; off by default)")
     ap.add_argument("--native-half-precision", action="store_true",
                     help="with --native-g2d-body / --native-eapp-trunk: the fused blocks' half-precision form, one f16 product per "
                          "multiply and half outputs under --fp16 (autocast) and with --dtype fp16 / bf16 (off by default)")
@@ -174,7 +177,7 @@ def run(job: dict, args, rank: int, world: int) -> List[str]:
         g.native_final_conv()
     half = {"half_precision": True} if args.native_half_precision else {}   # (the keyword is passed only when the flag is given)
     if args.native_g2d_body:
-        g.native_body(**half)
+        g.native_body(**half, **({"fuse_upsample": True} if args.native_fuse_upsample else {}))
     if args.native_eapp_trunk:
         g.native_trunk(**half)
     xs = _load_tensor(job["source_tensor"]) if job["source_tensor"] else _load_image(job["source"])

@@ -3,7 +3,9 @@ model.ResBlock2DFused (BatchNorm folded, 3x3 convs of csrc/conv2d_f16x3.hip) aga
 same run: torch fp32 with cudnn.benchmark off and on, NCHW and channels_last, torch under autocast-fp16 (for information: a different
 arithmetic), the native body, and one 512->512 conv launch at 64x64 (19.3 GFLOP per frame) with its TFLOP/s — in three and in one product.
 Half-precision legs (half_precision=True): torch under autocast-fp16 against the native body under autocast-fp16, and a .half() body,
-native against torch.  HIP events over `steps` calls after `warmup`.  Prints one JSON line; --out also writes it to a file.
+native against torch.  fuse_upsample legs ("fuse_upsample" in the output): at B = 1 and B = --b, the whole body and each of the three
+Sequential(Upsample, ResBlock2D) stages on its own input, as torch fp32, native_body() and native_body(fuse_upsample=True)
+(model.Up2ResBlock2DFused: the up-sample folded into the convs of csrc/conv2d_up2_f16x3.hip), the three legs back to back.  HIP events over `steps` calls after `warmup`.  Prints one JSON line; --out also writes it to a file.
 usage: python tools/bench_g2d_body.py [--b 8] [--warmup 20] [--steps 50] [--out profiles/g2d_body_timing.json]"""
 import argparse, copy, json, os, subprocess, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -92,6 +94,30 @@ def main():
         legs["torch_half_module_nchw"] = step_ms(lambda: body_h(xh), a.warmup, a.steps)
         legs["native_half_precision_half_module"] = step_ms(lambda: native_h(xh), a.warmup, a.steps)
         err_half = (native_h(xh).float() - body_h(xh).float()).abs().max().item()
+        # the up-samples folded into the convs: whole body and the three stages, torch / native / native + fuse_upsample, per batch size
+        fused = copy.deepcopy(body)
+        assert M.native_g2d_body(fused, True, fuse_upsample=True) and all(isinstance(s, M.Up2ResBlock2DFused) for s in (fused.upsample1, fused.upsample2, fused.upsample3))
+        torch.backends.cudnn.benchmark = True
+        up2 = {}
+        for b in sorted({1, a.b}):
+            xb = x[:b].contiguous()
+            rows = {"body": {"torch_fp32_nchw": step_ms(lambda: body(xb), a.warmup, a.steps),
+                             "native": step_ms(lambda: native(xb), a.warmup, a.steps),
+                             "native_fuse_upsample": step_ms(lambda: fused(xb), a.warmup, a.steps),
+                             "fused_vs_native_max_abs": (fused(xb) - native(xb)).abs().max().item()}}
+            xs = native.res_blocks(xb)
+            for name in ("upsample1", "upsample2", "upsample3"):
+                t, n, f = getattr(body, name), getattr(native, name), getattr(fused, name)
+                xin = xs.clone()      # (no descriptor on it: both native legs scan their input, as after a torch producer)
+                rows[name] = {"input": list(xin.shape), "torch_fp32_nchw": step_ms(lambda: t(xin), a.warmup, a.steps),
+                              "native": step_ms(lambda: n(xin), a.warmup, a.steps),
+                              "native_fuse_upsample": step_ms(lambda: f(xin), a.warmup, a.steps)}
+                xs = n(xin)
+            for r in rows.values():
+                r["native_over_native_fuse_upsample"] = round(r["native"] / r["native_fuse_upsample"], 3)
+            up2[f"B{b}"] = {k: {kk: (round(vv, 4) if isinstance(vv, float) and kk != "fused_vs_native_max_abs" else vv) for kk, vv in r.items()}
+                            for k, r in rows.items()}
+            del xs, xin
         # one launch of the dominant conv: 512 -> 512 at 64x64, bias + ReLU epilogue, the input's descriptor at hand
         blk = native.res_blocks[0]
         p1 = blk._folded()[0]
@@ -110,6 +136,7 @@ def main():
            "torch_autocast_fp16_over_native_half_precision": round(legs["torch_autocast_fp16_nchw_again"] / legs["native_half_precision_autocast_fp16"], 3),
            "torch_half_module_over_native_half_precision": round(legs["torch_half_module_nchw"] / legs["native_half_precision_half_module"], 3),
            "native_half_precision_vs_torch_max_abs": {"autocast_fp16": err_autocast, "half_module": err_half},
+           "fuse_upsample": up2,
            "conv_512_512_64x64": {"native_ms": round(conv_ms, 4), "native_tflops": round(flop / conv_ms * 1e-9, 1),
                                   "native_one_product_ms": round(conv1_ms, 4), "native_one_product_tflops": round(flop / conv1_ms * 1e-9, 1),
                                   "torch_fp32_ms": round(conv_torch_ms, 4), "torch_fp32_tflops": round(flop / conv_torch_ms * 1e-9, 1),
