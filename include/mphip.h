@@ -41,7 +41,7 @@ extern "C" {
 
 /* ABI version of this header.  Bumped whenever an exported signature or a packed layout changes; mphip_version() returns the
  * value the LIBRARY was built with — compare the two after dlopen (the ctypes binding does, and refuses a mismatch). */
-#define MPHIP_ABI_VERSION 23
+#define MPHIP_ABI_VERSION 24
 int mphip_version(void);
 /* hipGraph hygiene (ABI 13).  On ROCm 7.x a MEMSET node of a captured hipGraph is not reliably ordered with its neighbouring kernel nodes
  * (observed twice: stale f16x3 pack headers, r03; a training step's loss that kept its previous value, r04-r05 — ATen's multi-block
@@ -660,6 +660,30 @@ int mphip_conv2d_up2_fwd(const float *x, const float *x_range, const void *w_pac
 int mphip_conv2d_resup2_fwd(const float *x, const float *x_range, const void *w_packed, const float *bias, const float *residual_lowres,
                             float *y, float *out_range, int N, int Ci, int Co, int H, int W, int relu, void *workspace,
                             size_t workspace_bytes, void *stream);
+
+/* The ResNet-18 stem in one launch (ABI 24; csrc/conv2d_stem.hip): nn.Conv2d(3, Co, 3, stride=1, padding=1) with a folded BatchNorm,
+ * ReLU and nn.MaxPool2d(3, stride=2, padding=1), for the two CIFAR-stem ResNet-18s of Emtn (`conv1, bn1, relu, maxpool`):
+ *     c[n,co,r,s] = sum_{ci,dy,dx} w[co,ci,dy,dx] * x[n,ci,r+dy-1,s+dx-1]           zero padding 1, Ci = 3
+ *     v           = c + bias[co];   relu != 0: v = ReLU(v)
+ *     pool == 0:  y[n,co,r,s] = v                                                    y is [N,Co,H,W]
+ *     pool != 0:  y[n,co,i,j] = max of v over the positions (2i+a-1, 2j+b-1), a, b in {0,1,2}, that lie inside the map;
+ *                 y is [N,Co,Ho,Wo], Ho = (H+1)/2, Wo = (W+1)/2                      (= max_pool2d(v, 3, 2, 1))
+ * Exact fp32 on the vector units, and the arithmetic is part of the contract: the accumulator starts at +0 and takes fmaf(w, x, acc)
+ * over ci = 0..2, dy = 0..2, dx = 0..2 in that nesting and order, then one rounded + bias.  Padded taps contribute exactly zero.  ReLU
+ * maps negative values and zeros to +0.  NaN propagates through the ReLU and through the max (a pooled NaN is the quiet NaN
+ * 0x7fc00000), as torch's relu and max_pool2d do.  One thing is left open: without ReLU, the sign of a pooled maximum that is a zero
+ * when its window holds both -0 and +0 (-0 arises only from a -0 bias or an underflow).  max is exact, so the result depends neither on the tiling nor on how often a conv
+ * value shared by neighbouring windows is computed.  No matrix cores, no f16 split, no range descriptor of x, no pack (w_oihw is the plain
+ * [Co,3,3,3] fp32 weight), no workspace, no floating-point atomics: results are bitwise reproducible.
+ * out_range (optional, MPHIP_RANGE_FLOATS floats): a derive-mode descriptor whose partial maxima fold to the exact max|y|, written the way
+ * mphip_conv2d_fwd writes its own, so a conv2d launch that follows does not scan y.
+ * Shapes: Ci == 3, Co % 16 == 0, N, H, W >= 1, fewer than 2^31 elements in x and in y (pool: the pooled y).  H and W are the INPUT
+ * map's.  The rules in the order they are checked, as the 2-D conv entries above check theirs, all before the first HIP call and
+ * MPHIP_EINVAL each: "conv2d_stem_fwd: null pointer" (x, w_oihw, bias or y), "conv2d_stem_fwd: unsupported shape", 4-byte alignment of
+ * every pointer (any other base alignment works), "y must not alias x" (y overlapping x, extents from Ho*Wo when pooling).         */
+int mphip_conv2d_stem_supported(int N, int Ci, int Co, int H, int W, int pool);
+int mphip_conv2d_stem_fwd(const float *x, const float *w_oihw, const float *bias, float *y, float *out_range, int N, int Ci, int Co,
+                          int H, int W, int relu, int pool, void *stream);
 
 /* The reference's reduced-precision policy for the convs (train.py:145,188: the generator step runs under torch.cuda.amp.autocast(), its
  * conv3d calls take f16 operands with fp32 accumulation).  mphip_conv3d_set_half_products(1) makes the CALLING THREAD's subsequent precision-1

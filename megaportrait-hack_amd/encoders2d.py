@@ -295,14 +295,17 @@ class Emtn(nn.Module):
         self.expression_net.adaptive_pool = nn.AdaptiveAvgPool2d(FEATURE_SIZE)  # model.py:881: appended, runs last
         self.fc = nn.Linear(2048, COMPRESS_DIM)
 
-    def native_resnets(self, enable: bool = True) -> "Emtn":
+    def native_resnets(self, enable: bool = True, fuse_stem: bool = False) -> "Emtn":
         """Opt-in, inference only: run the eight BasicBlocks of `head_pose_net` and of `expression_net` as model.BasicBlockFused —
         BatchNorm folded, the 3x3 convs on the matrix cores with fp32-class accuracy (csrc/conv2d_f16x3.hip, and
         csrc/conv2d_s2_f16x3.hip for the three stride-2 convs of a net) — over the blocks' own children: same Parameter objects, same
         state-dict keys.  `enable=False` puts the original blocks back.  In train mode, under autograd or on a half model the fused
-        blocks evaluate the original PyTorch expression; there is no half_precision form.  The 3->64 stem (conv, BatchNorm, ReLU,
-        max-pool), the pools, the `fc`s and the whole 6DRepNet `rotation_net` stay on PyTorch."""
+        blocks evaluate the original PyTorch expression; there is no half_precision form.
+        fuse_stem (off by default): each net's 3->64 stem (conv, BatchNorm, ReLU, max-pool) also becomes one launch of
+        csrc/conv2d_stem.hip (model.StemFused, model.native_emtn_stems); without the keyword, or with enable off, the original four
+        modules are put back.  The pools, the `fc`s and the whole 6DRepNet `rotation_net` stay on PyTorch."""
         M.native_emtn_resnets(self, enable)
+        M.native_emtn_stems(self, bool(enable and fuse_stem))
         return self
 
     def forward(self, x):

@@ -76,7 +76,8 @@ def patch_functions(model_module) -> List[str]:
 
 
 def install(gbase: nn.Module, model_module: Optional[object] = None, eapp_tail: bool = True, g2d_final: bool = False,
-            g2d_body: bool = False, eapp_trunk: bool = False, half_precision: bool = False, fuse_upsample: bool = False) -> List[str]:
+            g2d_body: bool = False, eapp_trunk: bool = False, half_precision: bool = False, fuse_upsample: bool = False,
+            motion_encoder: bool = False, fuse_stem: bool = False) -> List[str]:
     """swap_hot_path + patch_functions.  `model_module` is the imported reference `model` module (the one that defines
     Gbase); pass it so the two `apply_warping_field` call sites inside Gbase.forward use the HIP kernel too.
     g2d_final (off by default): also swap `gbase.G2d.final_conv` (model.py:747-752) for model.G2dFinalConv, which shares the
@@ -87,7 +88,14 @@ def install(gbase: nn.Module, model_module: Optional[object] = None, eapp_tail: 
     half_precision (off by default): g2d_body / eapp_trunk blocks get their half-precision form — one f16 product per multiply and half
     outputs inside torch.autocast(float16) and as .half() / .bfloat16() modules (model.ResBlock2DFused).
     fuse_upsample (off by default): with g2d_body, G2d's three `Sequential(Upsample, ResBlock2D)` stages become model.Up2ResBlock2DFused,
-    the bilinear x2 up-sample folded into the block's convs; with half_precision=True they keep the materialised up-sample."""
+    the bilinear x2 up-sample folded into the block's convs; with half_precision=True they keep the materialised up-sample.
+    motion_encoder (off by default): also swap the BasicBlocks of `gbase.motionEncoder`'s two ResNet-18s for model.BasicBlockFused
+    (inference only; model.native_emtn_resnets).
+    fuse_stem (off by default): with motion_encoder, each of the two nets' 3->64 stems (conv, BatchNorm, ReLU, max-pool) becomes one launch
+    (model.StemFused; model.native_emtn_stems).  Without motion_encoder it is a ValueError: the keyword belongs to that switch, as
+    Emtn.native_resnets has it (fuse_upsample without g2d_body is ignored silently; a new keyword does not repeat that)."""
+    if fuse_stem and not motion_encoder:
+        raise ValueError("install: fuse_stem=True needs motion_encoder=True")
     done = swap_hot_path(gbase, eapp_tail=eapp_tail)
     if g2d_final and M.native_final_conv(gbase.G2d, True):
         done.append("G2d.final_conv")
@@ -95,6 +103,11 @@ def install(gbase: nn.Module, model_module: Optional[object] = None, eapp_tail: 
         done.append("G2d.body")
     if eapp_trunk and M.native_eapp_trunk(getattr(gbase, "appearanceEncoder", None), True, half_precision):
         done.append("Eapp.trunk2d")
+    emtn = getattr(gbase, "motionEncoder", None)
+    if motion_encoder and M.native_emtn_resnets(emtn, True):
+        done.append("Emtn.resnets")
+    if motion_encoder and fuse_stem and M.native_emtn_stems(emtn, True):
+        done.append("Emtn.stems")
     if model_module is not None:
         done += [f"{getattr(model_module, '__name__', 'model')}.{n}" for n in patch_functions(model_module)]
     return done

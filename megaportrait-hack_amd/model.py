@@ -1219,7 +1219,8 @@ def native_emtn_resnets(emtn: nn.Module, enable: bool = True) -> bool:
     or the reference's, model.py:869-907; the stages are found by type: `layer1..4` in the first, positional children in the second)
     for a BasicBlockFused over the same children, or puts the very objects it replaced back.  Returns whether anything changed.  Off by
     default everywhere; opt-in, inference only.  What stays on PyTorch: each net's 3->64 stem conv + BatchNorm + ReLU + max-pool (Ci = 3
-    does not fit the kernel), the pools and the `fc`s, and the whole 6DRepNet `rotation_net` (grouped convs; not an nn.Module of Gbase)."""
+    does not fit the kernel; native_emtn_stems fuses it on its own), the pools and the `fc`s, and the whole 6DRepNet `rotation_net`
+    (grouped convs; not an nn.Module of Gbase)."""
     changed = False
     for net in (getattr(emtn, "head_pose_net", None), getattr(emtn, "expression_net", None)):
         if not isinstance(net, nn.Module):
@@ -1232,6 +1233,168 @@ def native_emtn_resnets(emtn: nn.Module, enable: bool = True) -> bool:
                 if new is not stage[i]:
                     stage[i] = new
                 changed |= did
+    return changed
+
+
+class _StemSlot(nn.Module):
+    """One of the four stand-ins StemFused.swap puts into the stem slots `conv1, bn1, relu, maxpool` of a ResNet.  It registers the
+    Parameters and buffers of the module it replaces under their own names — the same objects, so the state-dict keys, their order and
+    `parameters()` stay as they were — and keeps that module itself out of the module tree, in `__dict__` (`named_modules()` keeps its
+    names).  `train()` / `eval()` reach the original through it, and `.to()` / `.half()` hand the converted buffers on to it."""
+
+    def _take(self, orig: nn.Module, head: "StemFused"):
+        self.__dict__["_orig"], self.__dict__["_head"] = orig, head
+        for name, param in orig._parameters.items():
+            self.register_parameter(name, param)
+        for name, buf in orig._buffers.items():
+            self.register_buffer(name, buf, persistent=name not in orig._non_persistent_buffers_set)
+        self.training = orig.training
+        self._version = orig._version   # (state_dict()'s metadata records it per module: BatchNorm's is 2)
+        return self
+
+    def train(self, mode: bool = True):
+        self._orig.train(mode)
+        return super().train(mode)
+
+    def _apply(self, fn, *args, **kwargs):
+        super()._apply(fn, *args, **kwargs)
+        self._orig._parameters.update(self._parameters)   # (torch converts Parameters in place, and replaces buffer objects)
+        self._orig._buffers.update(self._buffers)
+        return self
+
+    def extra_repr(self) -> str:
+        return f"stands in for {self._orig}"
+
+
+class _StemPass(_StemSlot):
+    """The `bn1`, `relu` and `maxpool` slots of a fused stem: a tensor that carries the mark of this stem's StemFused has been through all
+    four modules already and is returned as it is — the same object, untouched (the in-place ReLU would bump its version and drop its
+    range descriptor); the last slot takes the mark off.  Anything else goes through the original module."""
+
+    def __init__(self, orig: nn.Module, head: "StemFused", last: bool):
+        super().__init__()
+        self._take(orig, head)
+        self.__dict__["_last"] = last
+
+    def forward(self, x):
+        if isinstance(x, torch.Tensor) and x.__dict__.get("_mphip_stem") is self._head:
+            if self._last:
+                del x._mphip_stem
+            return x
+        return self._orig(x)
+
+
+class StemFused(_StemSlot):
+    """The stem `conv1 (3 -> Co, 3x3, stride 1, padding 1) -> bn1 -> relu -> maxpool(3, stride 2, padding 1)` of a torchvision-style
+    ResNet with a CIFAR stem — encoders2d.CifarResNet18 (Emtn's `head_pose_net`, whose forward calls the four attributes in turn), the
+    first four positions of the nn.Sequential `expression_net`, the reference's resnet.py — as ONE launch of csrc/conv2d_stem.hip: the
+    BatchNorm folded into the conv (fold_batchnorm), bias, ReLU and the max-pool in the kernel, exact fp32 FMA arithmetic, the full-size
+    64-channel map never written.  Opt-in, inference only; `StemFused.swap(net)` puts a StemFused into the `conv1` slot and pass-through
+    stand-ins (_StemPass) into the other three, `swap(net, False)` puts the very objects back.  State-dict keys, `named_modules()` names and
+    the Parameter and buffer objects are the net's own.
+
+    The native path runs in eval mode, without autograd (ag.needs_grad false), on an fp32 module, a CUDA image and a supported shape
+    (ops.conv2d_stem_supported); an fp16 / bf16 image is widened, a channels_last one copied once, the result is fp32 and carries the
+    range descriptor of its exact max|y|, so the first fused BasicBlock of `layer1` does not scan it.  Otherwise this slot runs the
+    original conv and returns an unmarked tensor, so the originals of the other three slots run: the original expression, bit for bit,
+    on the CPU, in train mode, under autograd and on half modules.  A net whose forward does not call the four slots in turn on one
+    tensor is not one this class stands in for."""
+
+    _SLOTS = ("conv1", "bn1", "relu", "maxpool")
+
+    def __init__(self, conv: nn.Module, bn: nn.Module, relu: nn.Module, pool: nn.Module):
+        super().__init__()
+        self._take(conv, self)
+        self.__dict__["_bn"], self.__dict__["_relu"], self.__dict__["_pool"] = bn, relu, pool
+
+    @classmethod
+    def _find(cls, net):
+        """The four slots of `net` -> (keys, modules): positions 0-3 of an nn.Sequential, else the attributes _SLOTS; None without them."""
+        if isinstance(net, nn.Sequential):
+            return (list(range(4)), [net[i] for i in range(4)]) if len(net) >= 4 else None
+        mods = [getattr(net, name, None) for name in cls._SLOTS] if isinstance(net, nn.Module) else [None]
+        return (list(cls._SLOTS), mods) if all(isinstance(m, nn.Module) for m in mods) else None
+
+    @classmethod
+    def matches(cls, net) -> bool:
+        """Duck-typed: does `net` begin with a stem this class can stand in for (and is it not fused already)?"""
+        from torch.nn.modules.utils import _pair
+
+        found = cls._find(net)
+        if found is None or any(isinstance(m, _StemSlot) for m in found[1]):
+            return False
+        conv, bn, relu, pool = found[1]
+        if not (_is_conv2d_at(conv, 3, 1) and conv.in_channels == 3 and _is_bn2d(bn, conv.out_channels) and isinstance(relu, nn.ReLU)):
+            return False
+        return (isinstance(pool, nn.MaxPool2d) and _pair(pool.kernel_size) == (3, 3) and _pair(pool.stride) == (2, 2)
+                and _pair(pool.padding) == (1, 1) and _pair(pool.dilation) == (1, 1) and not pool.ceil_mode and not pool.return_indices)
+
+    @classmethod
+    def swap(cls, net, enable: bool = True) -> bool:
+        """Fuses the stem of `net` (matches) or, enable off, puts the four original modules back -> whether anything changed."""
+        found = cls._find(net)
+        if found is None:
+            return False
+        keys, mods = found
+        put = net.__setitem__ if isinstance(net, nn.Sequential) else (lambda key, m: setattr(net, key, m))
+        if enable:
+            if not cls.matches(net):
+                return False
+            head = cls(*mods)
+            for i, (key, m) in enumerate(zip(keys, mods)):
+                put(key, head if i == 0 else _StemPass(m, head, last=i == 3))
+            return True
+        changed = False
+        for key, m in zip(keys, mods):
+            if isinstance(m, _StemSlot):
+                put(key, m._orig)
+                changed = True
+        return changed
+
+    def _fold_tensors(self):
+        conv, bn = self._orig, self._bn
+        return [t for t in (conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var) if t is not None]
+
+    def _native_ok(self, x) -> bool:
+        if self.training or self._bn.training or ag.needs_grad(self, x) or ag.needs_grad(self._bn):
+            return False
+        ts = self._fold_tensors()
+        if {t.dtype for t in ts} != {torch.float32}:
+            return False
+        if not (isinstance(x, torch.Tensor) and x.is_cuda and x.is_floating_point() and x.dim() == 4 and x.numel() > 0):
+            return False
+        n, ci, h, w = x.shape
+        return ci == 3 and all(t.device == x.device for t in ts) and ops.conv2d_stem_supported(n, ci, self._orig.out_channels, h, w, True)
+
+    def _folded(self):
+        """(w', b') of fold_batchnorm(conv1, bn1), cached until a parameter or a running buffer changes (_FusedBlock2D._folded's key)."""
+        ts = self._fold_tensors()
+        key = tuple((t.data_ptr(), t._version) for t in ts) + (str(ts[0].device), ops.weight_epoch())
+        hit = self.__dict__.get("_mphip_fold")
+        if hit is None or hit[0] != key or ops.repacking():
+            with torch.no_grad():
+                hit = (key, fold_batchnorm(self._orig, self._bn))
+            self.__dict__["_mphip_fold"] = hit
+        return hit[1]
+
+    def forward(self, x):
+        if not self._native_ok(x):
+            return self._orig(x)   # unmarked: bn1, relu and maxpool run as the modules they are
+        w, b = self._folded()
+        y = ops.conv2d_stem(_f32(x), w, b, relu=True, pool=True, want_range=True)
+        y._mphip_stem = self   # bn1, relu and maxpool hand it through; maxpool takes the mark off
+        return y
+
+
+def native_emtn_stems(emtn: nn.Module, enable: bool = True) -> bool:
+    """Swaps the stem `conv1, bn1, relu, maxpool` of `emtn.head_pose_net` (attributes) and of `emtn.expression_net` (positions 0-3) for a
+    StemFused and its three pass-through stand-ins, or puts the very objects it replaced back.  Returns whether anything changed.  Off
+    by default everywhere; opt-in, inference only.  What stays on PyTorch: the pools after `layer4`, the `fc`s and the whole 6DRepNet
+    `rotation_net`."""
+    changed = False
+    for net in (getattr(emtn, "head_pose_net", None), getattr(emtn, "expression_net", None)):
+        if isinstance(net, nn.Module):
+            changed |= StemFused.swap(net, enable)
     return changed
 
 

@@ -1370,6 +1370,36 @@ def conv2d_resup2(x: torch.Tensor, pack: PackedConv2d, residual_lowres: torch.Te
     return _conv2d_launch("conv2d_resup2", False, pack, x, None, xr, False, None, None, None, False, residual_lowres, relu, want_range, None, None)
 
 
+def conv2d_stem_supported(n: int, ci: int, co: int, h: int, w: int, pool: bool = True) -> bool:
+    """Does ops.conv2d_stem take an [n, ci, h, w] image (h, w: the INPUT map) with co output channels (mphip_conv2d_stem_supported:
+    ci == 3, co % 16 == 0, fewer than 2^31 elements in x and in y, y being the pooled map with pool=True)?"""
+    return bool(_lib.load().mphip_conv2d_stem_supported(int(n), int(ci), int(co), int(h), int(w), int(bool(pool))))
+
+
+def conv2d_stem(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, relu: bool = True, pool: bool = True,
+                want_range: bool = False) -> torch.Tensor:
+    """A ResNet stem in one launch (mphip_conv2d_stem_fwd): y = max_pool2d(act(conv3x3(x, weight, padding=1) + bias), 3, 2, 1) on an NCHW
+    fp32 image with 3 channels; weight is the plain [Co, 3, 3, 3] fp32 tensor (a BatchNorm folded in by the caller), bias [Co].
+    pool=False: the conv, bias and activation alone, [N, Co, H, W].  Exact fp32 with the fixed FMA order of include/mphip.h: bitwise
+    reproducible, NaN propagates as in torch.  A channels_last image is copied to NCHW once.  want_range: y comes back tagged with the
+    descriptor of its exact max|y|, like ops.conv2d's, so a conv2d that follows does not scan it.  fp32 CUDA tensors only."""
+    x, weight, bias = _req(x, "x"), _req(weight.detach(), "conv2d_stem weight"), _req(bias.detach(), "conv2d_stem bias")
+    if weight.dim() != 4 or tuple(weight.shape[1:]) != (3, 3, 3) or tuple(bias.shape) != (weight.shape[0],):
+        raise RuntimeError(f"conv2d_stem: expected a [Co, 3, 3, 3] weight and a [Co] bias, got {tuple(weight.shape)} and {tuple(bias.shape)}")
+    if x.dim() != 4 or x.shape[1] != 3:
+        raise RuntimeError(f"conv2d_stem: input {tuple(x.shape)} is not an [N, 3, H, W] image")
+    lib = _lib.load()
+    (n, ci, h, w), co = x.shape, int(weight.shape[0])
+    if not lib.mphip_conv2d_stem_supported(n, ci, co, h, w, int(bool(pool))):
+        raise RuntimeError(f"conv2d_stem: unsupported shape N={n} Ci={ci} Co={co} H={h} W={w} pool={bool(pool)} (there is no fallback)")
+    ho, wo = ((h + 1) // 2, (w + 1) // 2) if pool else (h, w)
+    y = torch.empty((n, co, ho, wo), dtype=torch.float32, device=x.device)
+    out_range = new_range(x.device) if want_range else None
+    _lib.check(lib.mphip_conv2d_stem_fwd(_ptr(x), _ptr(weight), _ptr(bias), _ptr(y), _ptr(out_range), n, ci, co, h, w, int(bool(relu)),
+                                         int(bool(pool)), _stream()), "mphip_conv2d_stem_fwd")
+    return tag_range(y, out_range)
+
+
 _GN_UNIT = {}   # (device, C) -> (ones, zeros): gamma and beta of a GroupNorm without parameters
 
 

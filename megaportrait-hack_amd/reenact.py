@@ -55,6 +55,12 @@ def parse(argv=None):
     ap.add_argument("--native-eapp-trunk", action="store_true",
                     help="run the appearance encoder's three 2-D ResBlock_Custom blocks on the matrix cores, GroupNorm, ReLU and the skip "
                          "conv folded into two conv launches per block (gbase.Gbase.native_trunk; inference only, fp32 models; off by default)")
+    ap.add_argument("--native-motion-encoder", action="store_true",
+                    help="run the BasicBlocks of the motion encoder's two ResNet-18s with BatchNorm folded and their 3x3 convs on the "
+                         "matrix cores (gbase.Gbase.native_motion_encoder; inference only, fp32 models; off by default)")
+    ap.add_argument("--native-fuse-stem", action="store_true",
+                    help="with --native-motion-encoder: each net's 3->64 stem conv, BatchNorm, ReLU and max-pool as one exact-fp32 launch, "
+                         "the full-size 64-channel map is never written (off by default)")
     ap.add_argument("--fp16", action="store_true",
                     help="run the PyTorch-ROCm 2D modules under torch.autocast(float16) (the reference's policy, train.py:188); "
                          "the HIP hot path stays fp32-class")
@@ -64,7 +70,10 @@ def parse(argv=None):
     ap.add_argument("--any-size", action="store_true", help="skip the reference's 512x512-only assert (model.py:1157)")
     ap.add_argument("--random-init", action="store_true", help="no checkpoint: random weights (plumbing tests)")
     ap.add_argument("--dry-run", action="store_true", help="resolve inputs and the launch plan, print them as JSON, exit")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.native_fuse_stem and not args.native_motion_encoder:   # (--native-fuse-upsample alone is ignored; a new flag does not repeat that)
+        ap.error("--native-fuse-stem needs --native-motion-encoder")
+    return args
 
 
 def resolve(args) -> dict:
@@ -180,6 +189,8 @@ def run(job: dict, args, rank: int, world: int) -> List[str]:
         g.native_body(**half, **({"fuse_upsample": True} if args.native_fuse_upsample else {}))
     if args.native_eapp_trunk:
         g.native_trunk(**half)
+    if args.native_motion_encoder:
+        g.native_motion_encoder(**({"fuse_stem": True} if args.native_fuse_stem else {}))
     xs = _load_tensor(job["source_tensor"]) if job["source_tensor"] else _load_image(job["source"])
     n = _load_tensor(job["drivers_tensor"]).shape[0] if job["drivers_tensor"] else len(job["drivers"])
     b, e, outputs = shard_plan(job, n, rank, world)

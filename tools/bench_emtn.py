@@ -5,7 +5,13 @@ the same box and commit, in the same process.  Each leg: `warmup` calls, then `r
 reported.  The legs run off, on, on, off so that neither side always goes first.  B = 1 and B = 8.  One more leg for context: the unswapped
 module under torch.autocast(float16).  And one 64 -> 128 stride-2 launch at 256 x 256 (layer2's first conv at 512^2 input) with its
 TFLOP/s, counting 2 * 9 * Ci * Co * Ho * Wo.  Prints one JSON line; --out also writes it to a file.
-usage: python tools/bench_emtn.py [--b 1 8] [--warmup 5] [--runs 20] [--out profiles/emtn_timing.json]"""
+--stem measures the fused stem instead (model.StemFused, csrc/conv2d_stem.hip), same timer and rules: (a) one net's stem alone — the one
+fused launch on the folded weights against the four torch fp32 modules conv1, bn1, relu, maxpool, legs torch, fused, fused, torch, and for
+context the four modules under torch.autocast(float16) — in ms and in GB/s counted as 4 * (3 * H * W + Co * Ho * Wo) bytes per frame;
+(b) Emtn.forward with everything off, with the BasicBlocks fused, and with the blocks and the stems fused, legs off, resnets, stem, stem,
+resnets, off.
+usage: python tools/bench_emtn.py [--b 1 8] [--warmup 5] [--runs 20] [--out profiles/emtn_timing.json]
+       python tools/bench_emtn.py --stem [--b 1 8] [--out profiles/emtn_stem_timing.json]"""
 import argparse, json, os, statistics, subprocess, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -36,6 +42,55 @@ def commit():
         return os.environ.get("MPHIP_COMMIT", "unknown")
 
 
+def stem_timing(a, dev, emtn):
+    """--stem: (a) one stem alone, (b) Emtn.forward off / resnets on / resnets and stems on."""
+    net = emtn.head_pose_net
+    co = net.conv1.out_channels
+    ho = wo = (a.hw + 1) // 2
+    out = {"what": "the 3->64 stem of Emtn's ResNet-18s (conv1, bn1, relu, maxpool) as one launch of csrc/conv2d_stem.hip",
+           "commit": commit(), "device": torch.cuda.get_device_name(0), "torch": torch.__version__, "H": a.hw, "W": a.hw, "warmup": a.warmup,
+           "runs": a.runs, "timer": "HIP events around each call after `warmup` calls; median (and minimum) of `runs` calls, ms per call",
+           "bytes_per_frame": 4 * (3 * a.hw * a.hw + co * ho * wo), "stem_order": ["torch", "fused", "fused", "torch"],
+           "forward_order": ["off", "resnets", "resnets+stem", "resnets+stem", "resnets", "off"], "batches": {}}
+    with torch.no_grad():
+        w, bias = M.fold_batchnorm(net.conv1, net.bn1)
+        torch_stem = lambda x: net.maxpool(net.relu(net.bn1(net.conv1(x))))
+        for b in a.b:
+            x = torch.rand(b, 3, a.hw, a.hw, device=dev) * 2 - 1
+            gbs = lambda ms: round(out["bytes_per_frame"] * b / ms * 1e-6, 1)
+            legs = []
+            for fused in (False, True, True, False):
+                fn = (lambda: ops.conv2d_stem(x, w, bias, want_range=True)) if fused else (lambda: torch_stem(x))
+                med, best = median_ms(fn, a.warmup, a.runs)
+                legs.append({"fused": fused, "median_ms": round(med, 4), "min_ms": round(best, 4)})
+            with torch.autocast(device_type="cuda", dtype=torch.float16):
+                amp, amp_best = median_ms(lambda: torch_stem(x), a.warmup, a.runs)
+            t_ms = statistics.mean(l["median_ms"] for l in legs if not l["fused"])
+            f_ms = statistics.mean(l["median_ms"] for l in legs if l["fused"])
+            err = (ops.conv2d_stem(x, w, bias) - torch_stem(x)).abs().max().item()
+            stem = {"legs": legs, "torch_fp32_ms": round(t_ms, 4), "fused_ms": round(f_ms, 4), "torch_over_fused": round(t_ms / f_ms, 2),
+                    "torch_fp32_gbs": gbs(t_ms), "fused_gbs": gbs(f_ms), "torch_autocast_fp16_ms": round(amp, 4),
+                    "torch_autocast_fp16_min_ms": round(amp_best, 4), "fused_vs_torch_max_abs": err}
+            flegs = []
+            for mode in (0, 1, 2, 2, 1, 0):
+                emtn.native_resnets(mode > 0, fuse_stem=mode == 2)
+                med, best = median_ms(lambda: emtn(x), a.warmup, a.runs)
+                flegs.append({"mode": ("off", "resnets", "resnets+stem")[mode], "median_ms": round(med, 4), "min_ms": round(best, 4)})
+            emtn.native_resnets(True, fuse_stem=True)
+            _, t_on, e_on = emtn(x)
+            emtn.native_resnets(False)
+            _, t_off, e_off = emtn(x)
+            mean = lambda m: round(statistics.mean(l["median_ms"] for l in flegs if l["mode"] == m), 4)
+            out["batches"][str(b)] = {"stem": stem, "forward": {"legs": flegs, "off_ms": mean("off"), "resnets_ms": mean("resnets"),
+                                                                 "resnets_stem_ms": mean("resnets+stem"),
+                                                                 "expression_stem_vs_off_max_abs": (e_on - e_off).abs().max().item(),
+                                                                 "expression_max_abs_off": e_off.abs().max().item(),
+                                                                 "translation_stem_vs_off_max_abs": (t_on - t_off).abs().max().item(),
+                                                                 "translation_max_abs_off": t_off.abs().max().item()}}
+            del x
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--b", type=int, nargs="+", default=[1, 8])
@@ -43,6 +98,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--runs", type=int, default=20)
     ap.add_argument("--out")
+    ap.add_argument("--stem", action="store_true", help="measure the fused stem (model.StemFused) instead; see the module docstring")
     a = ap.parse_args()
     if a.runs < 20:
         ap.error("--runs: the median of at least 20 runs is reported")
@@ -50,6 +106,13 @@ def main():
     torch.manual_seed(20241018)
     torch.backends.cudnn.benchmark = True
     emtn = E.Emtn().to(dev).eval()
+    if a.stem:
+        out = stem_timing(a, dev, emtn)
+        print(json.dumps(out))
+        if a.out:
+            with open(a.out, "w") as f:
+                f.write(json.dumps(out, indent=1) + "\n")
+        return
     out = {"what": "Emtn.forward: 6DRepNet rotation_net, head_pose_net and expression_net (CIFAR-stem ResNet-18s), fc",
            "commit": commit(), "device": torch.cuda.get_device_name(0), "torch": torch.__version__, "H": a.hw, "W": a.hw, "warmup": a.warmup,
            "runs": a.runs, "timer": "HIP events around each call after `warmup` calls; median (and minimum) of `runs` calls, ms per call",
