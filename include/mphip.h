@@ -41,7 +41,7 @@ extern "C" {
 
 /* ABI version of this header.  Bumped whenever an exported signature or a packed layout changes; mphip_version() returns the
  * value the LIBRARY was built with — compare the two after dlopen (the ctypes binding does, and refuses a mismatch). */
-#define MPHIP_ABI_VERSION 24
+#define MPHIP_ABI_VERSION 25
 int mphip_version(void);
 /* hipGraph hygiene (ABI 13).  On ROCm 7.x a MEMSET node of a captured hipGraph is not reliably ordered with its neighbouring kernel nodes
  * (observed twice: stale f16x3 pack headers, r03; a training step's loss that kept its previous value, r04-r05 — ATen's multi-block
@@ -684,6 +684,26 @@ int mphip_conv2d_resup2_fwd(const float *x, const float *x_range, const void *w_
 int mphip_conv2d_stem_supported(int N, int Ci, int Co, int H, int W, int pool);
 int mphip_conv2d_stem_fwd(const float *x, const float *w_oihw, const float *bias, float *y, float *out_range, int N, int Ci, int Co,
                           int H, int W, int relu, int pool, void *stream);
+
+/* Groups (ABI 25; csrc/conv2d_grp_f16x3.hip): nn.Conv2d(Ci, Co, 3, stride=1, padding=1, groups=groups) with mphip_conv2d_fwd's epilogue,
+ * for the thirteen groups = 2 blocks of 6DRepNet's RepVGG-B1g2 backbone in deploy form:
+ *     y[n, g*Cog + o, h, w] = act( sum_{c < Cig, dy, dx} wt[g*Cog + o, c, dy, dx] * x[n, g*Cig + c, h+dy-1, w+dx-1] + bias[g*Cog + o]
+ *                                  (+ residual[n, g*Cog + o, h, w]) ),      Cig = Ci / groups,   Cog = Co / groups
+ * x is [N,Ci,H,W], y and residual [N,Co,H,W]; wt is torch's grouped layout [Co,Cig,3,3] and w_packed its ordinary pack,
+ * mphip_pack_conv2d_weight(wt, w_packed, Co, Cig) (mphip_conv2d_packed_weight_bytes(Co, Cig) bytes, one header scale for the whole weight).
+ * x_range / out_range / workspace, tile, arithmetic, epilogue and saturation counting are mphip_conv2d_fwd's.  A workgroup's 64 output
+ * channels lie in one group and its K loop runs over that group's Cig / 16 chunks only: with the same x, x_range and bias, and a dense
+ * [Co,Ci,3,3] weight that holds the group blocks on its diagonal and exact zeros elsewhere (same max|w|: same pack scale), this launch
+ * writes the bits of mphip_conv2d_fwd.  fp32 maps, stride 1, one source and three products only.
+ * Shapes (mphip_conv2d_grouped_supported): groups >= 1 and mphip_conv2d_supported(N, Ci, Co, H, W); above one group also Ci % groups == 0,
+ * Co % groups == 0, Cig % 16 == 0 and Cog % 64 == 0 (a 64-channel output tile never straddles two groups).  groups == 1 launches the plain
+ * kernel: the bits of mphip_conv2d_fwd.  The call goes through the shared argument check of the entries above, in the same order (the
+ * group rule is part of the shape rule); messages name conv2d_grouped_fwd.                                                          */
+int mphip_conv2d_grouped_supported(int N, int Ci, int Co, int H, int W, int groups);
+size_t mphip_conv2d_grouped_workspace_bytes(int N, int Ci, int Co, int H, int W, int groups);
+int mphip_conv2d_grouped_fwd(const float *x, const float *x_range, const void *w_packed, const float *bias, const float *residual, float *y,
+                             float *out_range, int N, int Ci, int Co, int H, int W, int groups, int relu, void *workspace,
+                             size_t workspace_bytes, void *stream);
 
 /* The reference's reduced-precision policy for the convs (train.py:145,188: the generator step runs under torch.cuda.amp.autocast(), its
  * conv3d calls take f16 operands with fp32 accumulation).  mphip_conv3d_set_half_products(1) makes the CALLING THREAD's subsequent precision-1

@@ -164,6 +164,10 @@ SIGNATURES = {
     # the ResNet-18 stem conv + bias + ReLU + max-pool in one launch, exact fp32 (ABI 24, csrc/conv2d_stem.hip)
     "mphip_conv2d_stem_supported": (_i, [_i] * 6),
     "mphip_conv2d_stem_fwd": (_i, [_p] * 5 + [_i] * 7 + [_p]),
+    # the grouped form (ABI 25, csrc/conv2d_grp_f16x3.hip): groups after W
+    "mphip_conv2d_grouped_supported": (_i, [_i] * 6),
+    "mphip_conv2d_grouped_workspace_bytes": (_sz, [_i] * 6),
+    "mphip_conv2d_grouped_fwd": (_i, [_p] * 7 + [_i] * 7 + [_p, _sz, _p]),
     "mphip_build_flags": (_i, []),
     "mphip_graph_memsets_to_kernels": (_i, [_p, ctypes.POINTER(ctypes.c_int)]),
     "mphip_graph_memset_nodes_left": (_i, [_p, ctypes.POINTER(ctypes.c_int)]),
@@ -178,7 +182,7 @@ _lib = None
 # The ABI version the SIGNATURES table above mirrors.  Checked against the library at load time, and against include/mphip.h by
 # tests/test_host.py — NOT read from the header at run time: a relocated / installed package ships libmphip.so without the repository's
 # include/ directory.
-EXPECTED_ABI_VERSION = 24
+EXPECTED_ABI_VERSION = 25
 
 
 def header_abi_version() -> int:

@@ -29,6 +29,11 @@
 //             18-entry tables in LDS, computed once per workgroup.  The up-sampled map is never written.
 //   UP = 2    the residual is up2(r), r [N,Co,H/2,W/2] (H, W even): staging is the plain one, the epilogue adds the blend of four loads
 //             of r; a lane's coordinates depend on its pixel only and are computed once, before the channel loops.
+//
+// And one instantiated by conv2d_grp_f16x3.hip (every other unit is GRP = false; the unit's header has the contract):
+//   GRP       a grouped conv: x is [N,Ci,H,W], the weight [Co,Ci/groups,3,3] in the ordinary pack, and output channel tile `cot` belongs
+//             to group cot / grp_cots (grp_cots = 64-channel tiles per group).  The K loop runs over the grp_cig / 16 chunks that start
+//             at channel group * grp_cig of an image whose stride is Ci channels.  Nothing else differs.
 #pragma once
 #include <algorithm>
 
@@ -124,16 +129,17 @@ __device__ __forceinline__ float up2_blend(float x00, float x01, float x10, floa
 }
 
 // SAT: the instantiating unit's saturation counter
-template <bool CAT, unsigned long long *SAT, int XDT = MPHIP_DTYPE_F32, int YDT = MPHIP_DTYPE_F32, int NP = 3, int UP = 0>
+template <bool CAT, unsigned long long *SAT, int XDT = MPHIP_DTYPE_F32, int YDT = MPHIP_DTYPE_F32, int NP = 3, int UP = 0, bool GRP = false>
 __device__ __forceinline__ void conv2d_k3_tile(const dtype_t<XDT> *__restrict__ x, const float *__restrict__ x_range, const C2CatArgs cat,
                                                const _Float16 *__restrict__ wslabs, const float *__restrict__ whdr,
                                                const float *__restrict__ bias, const float *__restrict__ residual,
                                                dtype_t<YDT> *__restrict__ y, float *__restrict__ out_range, int Ci, int Co, int H, int W,
                                                int relu, int tiles_w, int tiles_h, unsigned nslots,
-                                               const dtype_t<YDT> *__restrict__ residual_t = nullptr) {
+                                               const dtype_t<YDT> *__restrict__ residual_t = nullptr, int grp_cig = 0, int grp_cots = 1) {
     static_assert(NP == 3 || NP == 1, "three products (f16x3) or one (the autocast policy)");
     static_assert(!CAT || XDT == MPHIP_DTYPE_F32, "the two-source form stages fp32 sources");
     static_assert(UP == 0 || (!CAT && XDT == MPHIP_DTYPE_F32 && YDT == MPHIP_DTYPE_F32 && NP == 3), "the up2 forms: one fp32 source, three products");
+    static_assert(!GRP || (!CAT && XDT == MPHIP_DTYPE_F32 && YDT == MPHIP_DTYPE_F32 && NP == 3 && UP == 0), "the grouped form: one fp32 source, three products");
     constexpr int NPART = NP == 3 ? 2 : 1;                   // operand halves in LDS: hi and lo, or hi alone
     constexpr int W_HALFS = C2_SLAB_HALFS / 2 * NPART;       // of a slab, the planes this kernel fetches
     __shared__ __attribute__((aligned(16))) _Float16 smem[W_HALFS + NPART * C2_X_PART];
@@ -166,14 +172,15 @@ __device__ __forceinline__ void conv2d_k3_tile(const dtype_t<XDT> *__restrict__ 
     const int n = bid / tiles_h;
     const int cot = blockIdx.y;
     const int h0 = th * C2_TH, w0 = tw * C2_TW;
-    const int nch1 = Ci / C2_KC;                                // chunks of the first source
+    const int nch1 = (GRP ? grp_cig : Ci) / C2_KC;              // chunks of the first source (GRP: of this tile's group)
     const int nchunks = nch1 + (CAT ? cat.C2 / C2_KC : 0);
     const size_t HW = (size_t)H * W;
     const unsigned HWu = (unsigned)HW;   // (a chunk's 16 channels hold fewer than 2^31 elements: 32-bit element offsets)
     const int xh = H >> 1, xw = W >> 1;                                 // UP = 1: the source map ...
     const size_t XHW = UP == 1 ? (size_t)xh * xw : HW;                  // ... and a channel of it (else the map itself)
     const int pr0 = h0 ? (h0 >> 1) - 1 : 0, pc0 = w0 ? (w0 >> 1) - 1 : 0;   // UP = 1: the patch's first row and column (i0 of the halo's first)
-    const dtype_t<XDT> *const xn = x + (size_t)n * Ci * XHW;
+    const dtype_t<XDT> *xn = x + (size_t)n * Ci * XHW;
+    if constexpr (GRP) xn += (size_t)(cot / grp_cots) * grp_cig * XHW;   // the group's first channel; the image stride stays Ci
     const float *const x2n = CAT && cat.C2 ? cat.x2 + (size_t)n * cat.C2 * HW : nullptr;
 
     // X staging: an item is (channel pair p, halo pixel r): two 4-byte loads (the zero padding and the ragged edge are the mask), scale,

@@ -117,8 +117,8 @@ void conv2d_lp_launch(const C2Call &c, const C2Grid &g) {
 
 // The host side of every 2-D 3x3 conv entry (the stride-2 entry of conv2d_s2_f16x3.hip included: c.stride == 2, extents of y and
 // residual from the halved map; and the two of conv2d_up2_f16x3.hip: c.up2 == 1, y and residual on the doubled map, c.up2 == 2, the
-// residual on the halved one).  The rules in the order they are checked, all before the first HIP call: dtypes and
-// products (lp_rule), pointers, the second source, the shape, alignment, tables, aliasing (MPHIP_EINVAL each), then the workspace
+// residual on the halved one; and the grouped one of conv2d_grp_f16x3.hip: c.groups != 0, the group rule ahead of the plain shape rule).
+// The rules in the order they are checked, all before the first HIP call: dtypes and products (lp_rule), pointers, the second source, the shape, alignment, tables, aliasing (MPHIP_EINVAL each), then the workspace
 // (MPHIP_EWORKSPACE).  Messages carry the called entry's name; a three-product call (all of its maps are fp32) is the fp32 entry's call
 // under whichever name it came in, and reports under that entry's name.
 int conv2d_run(C2Call c) {
@@ -131,9 +131,14 @@ int conv2d_run(C2Call c) {
     MPHIP_REQUIRE(!s2 || (!c.cat && np == 3), "%s: the stride-2 conv is the plain fp32 three-product form", c.who);
     const int up = c.up2;
     MPHIP_REQUIRE(up == 0 || ((up == 1 || up == 2) && !s2 && !c.cat && np == 3), "%s: the up2 convs are plain fp32 three-product forms", c.who);
-    const char *who = s2 || up ? c.who : c.products == 3 ? (c.cat ? "conv2d_cat_fwd" : "conv2d_fwd") : c.who;
+    const int grp = c.groups;
+    MPHIP_REQUIRE(grp == 0 || (!s2 && !up && !c.cat && np == 3), "%s: the grouped conv is the plain fp32 three-product form at stride 1", c.who);
+    const char *who = s2 || up || grp ? c.who : c.products == 3 ? (c.cat ? "conv2d_cat_fwd" : "conv2d_fwd") : c.who;
     MPHIP_REQUIRE(c.x1 && c.w_packed && c.bias && c.y && (up != 2 || c.residual), "%s: null pointer", who);
     MPHIP_REQUIRE(c.C2 >= 0 && (c.x2 != nullptr) == (c.C2 > 0), "%s: x2 and C2 = %d: a second source needs both, one source neither", who, c.C2);
+    MPHIP_REQUIRE(grp == 0 || c2_grouped_supported(c.N, c.C1, c.Co, c.H, c.W, grp),
+                  "%s: unsupported shape N=%d Ci=%d Co=%d H=%d W=%d groups=%d (groups >= 1; above 1: Ci and Co multiples of groups, (Ci / groups) "
+                  "%% 16 == 0, (Co / groups) %% 64 == 0; and the shape rule of conv2d_fwd)", who, c.N, c.C1, c.Co, c.H, c.W, grp);
     MPHIP_REQUIRE(s2        ? c2_s2_supported(c.N, c.C1, c.Co, c.H, c.W)
                   : up == 1 ? c2_up2_supported(c.N, c.C1, c.Co, c.H, c.W)
                   : c.cat   ? mphip_conv2d_cat_supported(c.N, c.C1, c.C2, c.Co, c.H, c.W)
@@ -186,6 +191,7 @@ int conv2d_run(C2Call c) {
     if (c.out_range) conv2d_out_range_init_launch(c.out_range, g.nslots, c.stream);
     if (s2) conv2d_s2_launch(c, g);
     else if (up) conv2d_up2_launch(c, g);
+    else if (grp > 1) conv2d_grouped_launch(c, g);
     else if (c.products == 1) conv2d_lp_launch(c, g);
     else if (c.cat) conv2d_cat_launch(c, g);
     else conv2d_plain_launch(c, g);

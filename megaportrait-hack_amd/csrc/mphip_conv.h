@@ -173,8 +173,10 @@ int conv2d_lp_saturation(unsigned long long *count, int reset);
 int conv2d_s2_saturation(unsigned long long *count, int reset);
 // conv2d_up2_f16x3.hip: the two forms with a bilinear x2 up-sample folded in (mphip_conv2d_up2_fwd, mphip_conv2d_resup2_fwd), likewise
 int conv2d_up2_saturation(unsigned long long *count, int reset);
+// conv2d_grp_f16x3.hip: the grouped form (mphip_conv2d_grouped_fwd), likewise
+int conv2d_grp_saturation(unsigned long long *count, int reset);
 
-// One call of the 2-D 3x3 conv, as its seven C entries describe it to conv2d_run (conv2d_lp.hip).  Zero-initialised it is the plain fp32
+// One call of the 2-D 3x3 conv, as its eight C entries describe it to conv2d_run (conv2d_lp.hip).  Zero-initialised it is the plain fp32
 // form: the plain form is one source (C2 = 0, no tables), the fp32 entries are fp32 dtypes with three products.
 struct C2Call {
     const char *who;        // the entry's name, for messages
@@ -182,6 +184,9 @@ struct C2Call {
                             // [N,Co,(H+1)/2,(W+1)/2]); anything else: stride 1
     int up2;                // conv2d_up2_f16x3.hip (plain form, fp32 maps, three products).  1: the source is up2(x1), x1 and H, W the
                             // LOW-resolution map, y and residual [N,Co,2H,2W].  2: the residual is up2(r), r [N,Co,H/2,W/2], H and W even
+    int groups;             // conv2d_grp_f16x3.hip (plain form, fp32 maps, three products, stride 1, no up2).  0: not that entry's call.
+                            // Otherwise the call reports under its own name; > 1: x1 [N,C1,H,W] in `groups` groups, the pack that of a
+                            // [Co,C1/groups,3,3] weight; 1: the plain kernel; < 0: a group count the shape rule refuses
     bool cat;               // the two-source kernels (also with C2 == 0: they are kernels of their own); false: the plain ones
     const void *x1, *x2;    // sources [N,C1,H,W] and [N,C2,H,W] or NULL; x1 in x_dtype (fp32 when cat), x2 fp32
     const float *aff1, *aff2, *x1_range, *x2_range;
@@ -213,11 +218,15 @@ void conv2d_cat_launch(const C2Call &c, const C2Grid &g);     // conv2d_gn_f16x3
 void conv2d_lp_launch(const C2Call &c, const C2Grid &g);      // conv2d_lp.hip: the one-product kernels of both forms
 void conv2d_s2_launch(const C2Call &c, const C2Grid &g);      // conv2d_s2_f16x3.hip: conv2d_k3s2_f16x3_kernel
 void conv2d_up2_launch(const C2Call &c, const C2Grid &g);     // conv2d_up2_f16x3.hip: conv2d_k3_up2_f16x3_kernel / conv2d_k3_resup2_f16x3_kernel
+void conv2d_grouped_launch(const C2Call &c, const C2Grid &g); // conv2d_grp_f16x3.hip: conv2d_k3_grp_f16x3_kernel (c.groups > 1)
 // conv2d_s2_f16x3.hip: its output tile (64 channels x 8 rows x 16 columns per workgroup) and its shape rule (H, W: the input map)
 constexpr int C2S2_TH = 8, C2S2_TW = 16;
 bool c2_s2_supported(int N, int Ci, int Co, int H, int W);
 // conv2d_up2_f16x3.hip: the shape rule of its up-sampled-source form (h, w: the LOW-resolution input map): c2_supported on [2h, 2w]
 bool c2_up2_supported(int N, int Ci, int Co, int h, int w);
+// conv2d_grp_f16x3.hip: its shape rule: groups >= 1 and c2_supported; groups > 1: Ci and Co multiples of groups, (Ci / groups) % 16 == 0,
+// (Co / groups) % 64 == 0
+bool c2_grouped_supported(int N, int Ci, int Co, int H, int W, int groups);
 
 // api.hip: the calling thread's conv arithmetic policy (mphip_conv3d_set_half_products): true inside torch.autocast(float16) regions
 bool conv_half_products();

@@ -303,9 +303,18 @@ class Emtn(nn.Module):
         blocks evaluate the original PyTorch expression; there is no half_precision form.
         fuse_stem (off by default): each net's 3->64 stem (conv, BatchNorm, ReLU, max-pool) also becomes one launch of
         csrc/conv2d_stem.hip (model.StemFused, model.native_emtn_stems); without the keyword, or with enable off, the original four
-        modules are put back.  The pools, the `fc`s and the whole 6DRepNet `rotation_net` stay on PyTorch."""
+        modules are put back.  The pools and the `fc`s stay on PyTorch; the 6DRepNet has a switch of its own, native_rotation_net."""
         M.native_emtn_resnets(self, enable)
         M.native_emtn_stems(self, bool(enable and fuse_stem))
+        return self
+
+    def native_rotation_net(self, enable: bool = True) -> "Emtn":
+        """Opt-in, inference only: run the 27 deploy-form RepVGG blocks of `rotation_net`'s `layer1..layer4` (3x3 conv + bias + ReLU
+        each) as model.RepVGGBlockFused — one matrix-core launch per block with fp32-class accuracy: csrc/conv2d_f16x3.hip,
+        csrc/conv2d_s2_f16x3.hip for the four stride-2 blocks and csrc/conv2d_grp_f16x3.hip for the thirteen groups = 2 blocks — over
+        the blocks' own children: same Parameter objects, same state-dict keys.  `enable=False` puts the original blocks back.
+        `layer0` (3 -> 64 at stride 2), the pool, `linear_reg` and the Gram-Schmidt step stay on PyTorch.  Independent of native_resnets."""
+        M.native_rotation_net(self, enable)
         return self
 
     def forward(self, x):

@@ -77,7 +77,7 @@ def patch_functions(model_module) -> List[str]:
 
 def install(gbase: nn.Module, model_module: Optional[object] = None, eapp_tail: bool = True, g2d_final: bool = False,
             g2d_body: bool = False, eapp_trunk: bool = False, half_precision: bool = False, fuse_upsample: bool = False,
-            motion_encoder: bool = False, fuse_stem: bool = False) -> List[str]:
+            motion_encoder: bool = False, fuse_stem: bool = False, rotation_net: bool = False) -> List[str]:
     """swap_hot_path + patch_functions.  `model_module` is the imported reference `model` module (the one that defines
     Gbase); pass it so the two `apply_warping_field` call sites inside Gbase.forward use the HIP kernel too.
     g2d_final (off by default): also swap `gbase.G2d.final_conv` (model.py:747-752) for model.G2dFinalConv, which shares the
@@ -93,9 +93,14 @@ def install(gbase: nn.Module, model_module: Optional[object] = None, eapp_tail: 
     (inference only; model.native_emtn_resnets).
     fuse_stem (off by default): with motion_encoder, each of the two nets' 3->64 stems (conv, BatchNorm, ReLU, max-pool) becomes one launch
     (model.StemFused; model.native_emtn_stems).  Without motion_encoder it is a ValueError: the keyword belongs to that switch, as
-    Emtn.native_resnets has it (fuse_upsample without g2d_body is ignored silently; a new keyword does not repeat that)."""
+    Emtn.native_resnets has it (fuse_upsample without g2d_body is ignored silently; a new keyword does not repeat that).
+    rotation_net (off by default): with motion_encoder, the 27 deploy-form RepVGG blocks of the frozen 6DRepNet
+    (`gbase.motionEncoder.rotation_net`) become model.RepVGGBlockFused, one matrix-core launch each (inference only;
+    model.native_rotation_net).  Without motion_encoder it is a ValueError, like fuse_stem."""
     if fuse_stem and not motion_encoder:
         raise ValueError("install: fuse_stem=True needs motion_encoder=True")
+    if rotation_net and not motion_encoder:
+        raise ValueError("install: rotation_net=True needs motion_encoder=True")
     done = swap_hot_path(gbase, eapp_tail=eapp_tail)
     if g2d_final and M.native_final_conv(gbase.G2d, True):
         done.append("G2d.final_conv")
@@ -108,6 +113,8 @@ def install(gbase: nn.Module, model_module: Optional[object] = None, eapp_tail: 
         done.append("Emtn.resnets")
     if motion_encoder and fuse_stem and M.native_emtn_stems(emtn, True):
         done.append("Emtn.stems")
+    if motion_encoder and rotation_net and M.native_rotation_net(emtn, True):
+        done.append("Emtn.rotation_net")
     if model_module is not None:
         done += [f"{getattr(model_module, '__name__', 'model')}.{n}" for n in patch_functions(model_module)]
     return done

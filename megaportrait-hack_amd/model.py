@@ -1219,8 +1219,8 @@ def native_emtn_resnets(emtn: nn.Module, enable: bool = True) -> bool:
     or the reference's, model.py:869-907; the stages are found by type: `layer1..4` in the first, positional children in the second)
     for a BasicBlockFused over the same children, or puts the very objects it replaced back.  Returns whether anything changed.  Off by
     default everywhere; opt-in, inference only.  What stays on PyTorch: each net's 3->64 stem conv + BatchNorm + ReLU + max-pool (Ci = 3
-    does not fit the kernel; native_emtn_stems fuses it on its own), the pools and the `fc`s, and the whole 6DRepNet `rotation_net`
-    (grouped convs; not an nn.Module of Gbase)."""
+    does not fit the kernel; native_emtn_stems fuses it on its own), the pools and the `fc`s.  The third net, the 6DRepNet
+    `rotation_net` (not an nn.Module of Gbase), has a switch of its own: native_rotation_net."""
     changed = False
     for net in (getattr(emtn, "head_pose_net", None), getattr(emtn, "expression_net", None)):
         if not isinstance(net, nn.Module):
@@ -1389,12 +1389,133 @@ class StemFused(_StemSlot):
 def native_emtn_stems(emtn: nn.Module, enable: bool = True) -> bool:
     """Swaps the stem `conv1, bn1, relu, maxpool` of `emtn.head_pose_net` (attributes) and of `emtn.expression_net` (positions 0-3) for a
     StemFused and its three pass-through stand-ins, or puts the very objects it replaced back.  Returns whether anything changed.  Off
-    by default everywhere; opt-in, inference only.  What stays on PyTorch: the pools after `layer4`, the `fc`s and the whole 6DRepNet
-    `rotation_net`."""
+    by default everywhere; opt-in, inference only.  What stays on PyTorch: the pools after `layer4` and the `fc`s (the 6DRepNet
+    `rotation_net` has a switch of its own: native_rotation_net)."""
     changed = False
     for net in (getattr(emtn, "head_pose_net", None), getattr(emtn, "expression_net", None)):
         if isinstance(net, nn.Module):
             changed |= StemFused.swap(net, enable)
+    return changed
+
+
+def _is_repvgg_conv(m) -> bool:
+    """The re-parameterised conv of a deploy-form RepVGG block: 3x3, padding 1, stride 1 or 2, any group count, with a bias."""
+    return (isinstance(m, nn.Conv2d) and m.kernel_size == (3, 3) and m.stride in ((1, 1), (2, 2)) and m.padding == (1, 1)
+            and m.dilation == (1, 1) and m.padding_mode == "zeros" and m.bias is not None)
+
+
+class RepVGGBlockFused(_FusedBlock2D):
+    """A RepVGG block in deploy form — encoders2d._RepVGGDeployBlock, the reference's RepVGGBlock(deploy=True): `rbr_reparam`, one 3x3
+    conv with a bias at stride 1 or 2, then ReLU (where the block has them, `se` is an nn.Identity and `nonlinearity` an nn.ReLU) — with an
+    opt-in inference path on the matrix cores: ONE launch with bias and ReLU in its epilogue, f16x3 arithmetic (fp32-class accuracy):
+    csrc/conv2d_s2_f16x3.hip at stride 2 (groups == 1 only), csrc/conv2d_f16x3.hip at groups == 1, csrc/conv2d_grp_f16x3.hip otherwise.
+    The children are the original block's own, under their own names and in their own order: the same Parameter objects, the same
+    state-dict keys, the same `named_modules()` names.  A block that still has its training branches (`rbr_dense`) is not matched.
+
+    The native path runs only in eval mode, without autograd, on an fp32 module, a CUDA floating-point map and a supported shape
+    (ops.conv2d_grouped_supported / conv2d_supported / conv2d_s2_supported); otherwise forward evaluates the original expression through
+    the block's own children: on the CPU, in train mode, under autograd, on a .half() / .bfloat16() module and on a shape the kernels
+    do not take (four groups at width 128: 32 output channels per group).  There are NO backward kernels and NO half_precision form.
+    fp16 / bf16 inputs are widened and the result is fp32; a channels_last map is copied to NCHW once.  Each launch leaves the range
+    descriptor of its output on the tensor, so only the first fused block of a net scans its input."""
+
+    _EXPECTED = ("a deploy-form RepVGG block (`rbr_reparam`: Conv2d 3x3, padding 1, stride 1 or 2 (groups == 1 there), with a bias; `se` an "
+                 "Identity and `nonlinearity` a ReLU where present; no `rbr_dense`; in_channels % 16 == 0)")
+    _EVAL_ONLY = True
+    _CUDA_FLOAT_INPUT = True
+
+    def __init__(self, in_channels: int, out_channels: int, stride: int = 1, groups: int = 1):
+        super().__init__()
+        self.rbr_reparam = nn.Conv2d(in_channels, out_channels, 3, stride=stride, padding=1, groups=groups, bias=True)
+
+    @classmethod
+    def from_block(cls, block: nn.Module, half_precision: bool = False):
+        if half_precision:
+            raise TypeError("RepVGGBlockFused has no half_precision form")
+        if not cls.matches(block):
+            raise TypeError(f"{cls.__name__}.from_block: expected {cls._EXPECTED}, got {block}")
+        new = cls.__new__(cls)
+        nn.Module.__init__(new)
+        for name, child in block._modules.items():   # (every child, in the block's order: named_modules() and state_dict() keep theirs)
+            setattr(new, name, child)
+        new.training = block.training
+        return new
+
+    @staticmethod
+    def matches(block) -> bool:
+        """Duck-typed: is `block` a deploy-form RepVGG block the fused path can stand in for?"""
+        if isinstance(block, _FusedBlock2D) or not isinstance(block, nn.Module) or hasattr(block, "rbr_dense"):
+            return False
+        conv = getattr(block, "rbr_reparam", None)
+        if not _is_repvgg_conv(conv) or (conv.stride == (2, 2) and conv.groups != 1):
+            return False
+        if conv.in_channels % 16:   # (no shape of such a block fits a kernel: layer0's 3 -> 64 conv stays the module it is)
+            return False
+        if set(block._modules) - {"rbr_reparam", "se", "nonlinearity"}:
+            return False
+        if hasattr(block, "se") and not isinstance(block.se, nn.Identity):
+            return False
+        return not hasattr(block, "nonlinearity") or isinstance(block.nonlinearity, nn.ReLU)
+
+    def _shape_ok(self, x) -> bool:
+        conv = self.rbr_reparam
+        (n, ci, h, w), co, g = x.shape, conv.out_channels, conv.groups
+        if ci != conv.in_channels or conv.weight.device != x.device:
+            return False
+        if conv.stride == (2, 2):
+            return g == 1 and ops.conv2d_s2_supported(n, ci, co, h, w)
+        return ops.conv2d_grouped_supported(n, ci, co, h, w, g)
+
+    def _dtypes(self, half_path: bool):
+        return {self.rbr_reparam.weight.dtype, self.rbr_reparam.bias.dtype}
+
+    def _fold_tensors(self):
+        return [self.rbr_reparam.weight, self.rbr_reparam.bias]
+
+    def _fold(self, wide):
+        return ops.PackedConv2d(self.rbr_reparam.weight, self.rbr_reparam.bias, self.rbr_reparam.groups)
+
+    def _reference(self, x):
+        y = self.rbr_reparam(x)
+        if "nonlinearity" not in self._modules:
+            return F.relu(y)   # encoders2d._RepVGGDeployBlock.forward
+        return self.nonlinearity(self.se(y) if "se" in self._modules else y)
+
+    def _launch(self, x, pack, out_dtype, products):
+        xc = _f32(x).contiguous()   # (the kernels read NCHW: a channels_last map is copied once)
+        if self.rbr_reparam.stride == (2, 2):
+            return ops.conv2d_s2(xc, pack, relu=True, want_range=True)
+        if pack.groups == 1:
+            return ops.conv2d(xc, pack, relu=True, want_range=True)
+        return ops.conv2d_grouped(xc, pack, relu=True, want_range=True)
+
+
+def native_rotation_net(target, enable: bool = True) -> bool:
+    """Swaps every matching deploy-form RepVGG block of the 6DRepNet backbone — `layer0` and the nn.Sequential stages `layer1..layer4` —
+    for a RepVGGBlockFused over the same children, or puts the very objects it replaced back.  `target` is an Emtn (its `rotation_net`
+    is looked up), a detector object with a `.model` (encoders2d.SixDRepNet_Detector, the reference's) or the backbone module itself.
+    Returns whether anything changed.  Off by default everywhere; opt-in, inference only.  With RepVGG-B1g2 the 27 blocks of
+    `layer1..layer4` are swapped; what stays on PyTorch: `layer0` (3 -> 64 at stride 2: Ci = 3 fits neither f16x3 kernel, so the block does not
+    match and is left as it is), the global average pool, `linear_reg` and the Gram-Schmidt step."""
+    net = getattr(target, "rotation_net", target)   # Emtn -> detector
+    if not hasattr(net, "layer1"):
+        net = getattr(net, "model", net)            # detector -> backbone
+    if not isinstance(net, nn.Module):
+        return False
+    changed = False
+    if isinstance(getattr(net, "layer0", None), nn.Module):
+        new, changed = _swap_slot(RepVGGBlockFused, net.layer0, enable, False)
+        if new is not net.layer0:
+            net.layer0 = new
+    for name in ("layer1", "layer2", "layer3", "layer4"):
+        stage = getattr(net, name, None)
+        if not isinstance(stage, nn.Sequential):
+            continue
+        for i in range(len(stage)):
+            new, did = _swap_slot(RepVGGBlockFused, stage[i], enable, False)
+            if new is not stage[i]:
+                stage[i] = new
+            changed |= did
     return changed
 
 

@@ -1195,20 +1195,26 @@ def g2d_final_bwd(x, y, dy, stats, gamma, beta, w, want_params: bool = True):
 class PackedConv2d:
     """One 3x3, stride 1, padding 1 Conv2d for ops.conv2d: OIHW fp32 weight + bias, packed lazily into the f16x3 slabs described in
     include/mphip.h (mphip_pack_conv2d_weight).  `key` = (data_ptr, _version, device, weight_epoch()) of the tensors it was built from,
-    like the other packs: an owner re-creates the object when `PackedConv2d.key_of(weight, bias) != pack.key`."""
+    like the other packs: an owner re-creates the object when `PackedConv2d.key_of(weight, bias) != pack.key`.
+    groups > 1: the weight is torch's grouped [Co, Ci / groups, 3, 3]; `ci` stays the conv's input channel count, the pack is the ordinary
+    one of a [Co, Ci / groups] weight, and only ops.conv2d_grouped takes it."""
 
-    __slots__ = ("weight", "bias", "co", "ci", "key", "_packed")
+    __slots__ = ("weight", "bias", "co", "ci", "groups", "key", "_packed")
 
-    def __init__(self, weight: torch.Tensor, bias: torch.Tensor):
+    def __init__(self, weight: torch.Tensor, bias: torch.Tensor, groups: int = 1):
         self.key = PackedConv2d.key_of(weight, bias)
         weight = _req(weight.detach(), "conv2d weight")
         if weight.dim() != 4 or tuple(weight.shape[2:]) != (3, 3):
             raise RuntimeError(f"PackedConv2d: expected an OIHW 3x3 weight, got {tuple(weight.shape)}")
         if bias is None or tuple(bias.shape) != (weight.shape[0],):
             raise RuntimeError("PackedConv2d: a bias of Co elements is required")
-        self.co, self.ci = int(weight.shape[0]), int(weight.shape[1])
-        if _lib.load().mphip_conv2d_packed_weight_bytes(self.co, self.ci) == 0:
-            raise RuntimeError(f"PackedConv2d: Co={self.co} Ci={self.ci} unsupported (Ci % 16 == 0 and Co % 32 == 0 are required)")
+        self.groups = int(groups)
+        if self.groups < 1:
+            raise RuntimeError(f"PackedConv2d: groups = {groups!r}")
+        self.co, self.ci = int(weight.shape[0]), int(weight.shape[1]) * self.groups
+        if _lib.load().mphip_conv2d_packed_weight_bytes(self.co, self.ci // self.groups) == 0:
+            raise RuntimeError(f"PackedConv2d: Co={self.co} Ci={self.ci} groups={self.groups} unsupported (Ci / groups % 16 == 0 and Co % 32 == 0 "
+                               f"are required)")
         self.weight = weight
         self.bias = _req(bias.detach(), "conv2d bias")
         self._packed = None
@@ -1221,9 +1227,10 @@ class PackedConv2d:
     def packed(self) -> torch.Tensor:
         if self._packed is None:
             lib = _lib.load()
-            nbytes = lib.mphip_conv2d_packed_weight_bytes(self.co, self.ci)
+            cig = self.ci // self.groups
+            nbytes = lib.mphip_conv2d_packed_weight_bytes(self.co, cig)
             wp = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=self.weight.device)
-            _lib.check(lib.mphip_pack_conv2d_weight(_ptr(self.weight), _ptr(wp), self.co, self.ci, _stream()), "mphip_pack_conv2d_weight")
+            _lib.check(lib.mphip_pack_conv2d_weight(_ptr(self.weight), _ptr(wp), self.co, cig, _stream()), "mphip_pack_conv2d_weight")
             self._packed = wp
         return self._packed
 
@@ -1272,10 +1279,14 @@ def conv2d(x: torch.Tensor, pack: PackedConv2d, residual: Optional[torch.Tensor]
 
 def _conv2d_launch(who, typed, pack, x1, aff1, r1, relu1, x2, aff2, r2, relu2, residual, relu, want_range, out_dtype, products):
     """What ops.conv2d (who = "conv2d": the plain kernels), ops.conv2d_cat, ops.conv2d_s2 (the stride-2 kernel: y and residual on the
-    halved map), ops.conv2d_up2 (y and residual on the doubled map) and ops.conv2d_resup2 (the residual on the halved map) share once
+    halved map), ops.conv2d_up2 (y and residual on the doubled map), ops.conv2d_resup2 (the residual on the halved map) and
+    ops.conv2d_grouped (the entry takes the pack's group count after W) share once
     their sources are checked and the descriptors r1 / r2 chosen: the residual check, the workspace, y and out_range, and the call of
     the fp32 or (`typed`) the typed entry."""
     cat = who == "conv2d_cat"
+    grp = (pack.groups,) if who == "conv2d_grouped" else ()
+    if pack.groups != 1 and not grp:   # (its slabs hold Ci / groups channels: any other kernel would read past them)
+        raise RuntimeError(f"{who}: the pack is that of a grouped conv (groups = {pack.groups}): only ops.conv2d_grouped takes it")
     lib = _lib.load()
     n, c1, h, w = x1.shape
     c2 = 0 if x2 is None else int(x2.shape[1])
@@ -1289,7 +1300,7 @@ def _conv2d_launch(who, typed, pack, x1, aff1, r1, relu1, x2, aff2, r2, relu2, r
     if r1 is None or (x2 is not None and r2 is None):   # a source to scan
         ws_name = "conv2d" if who == "conv2d_resup2" else who
         ws_bytes = (lib.mphip_conv2d_cat_workspace_bytes(n, c1, c2, pack.co, h, w) if cat
-                    else getattr(lib, f"mphip_{ws_name}_workspace_bytes")(n, c1, pack.co, h, w))
+                    else getattr(lib, f"mphip_{ws_name}_workspace_bytes")(n, c1, pack.co, h, w, *grp))
     ws = torch.empty((ws_bytes + 3) // 4, dtype=torch.float32, device=x1.device) if ws_bytes else None
     ydt = torch.float32 if out_dtype is None else out_dtype
     y = torch.empty((n, pack.co, ho, wo), dtype=ydt, device=x1.device)
@@ -1302,7 +1313,7 @@ def _conv2d_launch(who, typed, pack, x1, aff1, r1, relu1, x2, aff2, r2, relu2, r
         shape = (n, pack.co, h, w)
     else:
         sources = (_ptr(x1), *xdt, _ptr(r1))
-        shape = (n, c1, pack.co, h, w)
+        shape = (n, c1, pack.co, h, w, *grp)
     args = (*sources, _ptr(pack.packed()), _ptr(pack.bias), _ptr(residual), *rdt, _ptr(y), *ydt, _ptr(out_range), *shape, int(bool(relu)), *np_,
             _ptr(ws), ws_bytes, _stream())
     entry = f"mphip_{who}_fwd" + ("_typed" if typed else "")
@@ -1328,6 +1339,28 @@ def conv2d_s2(x: torch.Tensor, pack: PackedConv2d, residual: Optional[torch.Tens
         raise RuntimeError(f"conv2d_s2: unsupported shape N={n} Ci={ci} Co={pack.co} H={h} W={w} (there is no fallback)")
     xr = x_range if x_range is not None else current_range(x)   # None: the library scans x
     return _conv2d_launch("conv2d_s2", False, pack, x, None, xr, False, None, None, None, False, residual, relu, want_range, None, None)
+
+
+def conv2d_grouped_supported(n: int, ci: int, co: int, h: int, w: int, groups: int) -> bool:
+    """Does ops.conv2d_grouped take an [n, ci, h, w] input with co output channels in `groups` groups (mphip_conv2d_grouped_supported:
+    groups == 1 under ops.conv2d's rule; above 1 also ci and co multiples of groups, ci / groups % 16 == 0, co / groups % 64 == 0)?"""
+    return bool(_lib.load().mphip_conv2d_grouped_supported(int(n), int(ci), int(co), int(h), int(w), int(groups)))
+
+
+def conv2d_grouped(x: torch.Tensor, pack: PackedConv2d, residual: Optional[torch.Tensor] = None, relu: bool = False,
+                   x_range: Optional[torch.Tensor] = None, want_range: bool = False) -> torch.Tensor:
+    """y = act(conv3x3(x, groups = pack.groups) + bias (+ residual)) on NCHW fp32, stride 1, padding 1 (mphip_conv2d_grouped_fwd): the
+    pack is PackedConv2d(weight [Co, Ci / groups, 3, 3], bias, groups).  The f16x3 arithmetic and the descriptors are ops.conv2d's: with
+    the same x_range the result is, bit for bit, conv2d on the dense weight with the group blocks on its diagonal and zeros elsewhere;
+    with groups == 1 it is conv2d.  fp32 only."""
+    x = _req(x, "x")
+    if x.dim() != 4 or x.shape[1] != pack.ci:
+        raise RuntimeError(f"conv2d_grouped: input {tuple(x.shape)} does not match Ci={pack.ci}")
+    n, ci, h, w = x.shape
+    if not _lib.load().mphip_conv2d_grouped_supported(n, ci, pack.co, h, w, pack.groups):
+        raise RuntimeError(f"conv2d_grouped: unsupported shape N={n} Ci={ci} Co={pack.co} H={h} W={w} groups={pack.groups} (there is no fallback)")
+    xr = x_range if x_range is not None else current_range(x)   # None: the library scans x
+    return _conv2d_launch("conv2d_grouped", False, pack, x, None, xr, False, None, None, None, False, residual, relu, want_range, None, None)
 
 
 def conv2d_up2_supported(n: int, ci: int, co: int, h: int, w: int) -> bool:

@@ -10,8 +10,13 @@ fused launch on the folded weights against the four torch fp32 modules conv1, bn
 context the four modules under torch.autocast(float16) — in ms and in GB/s counted as 4 * (3 * H * W + Co * Ho * Wo) bytes per frame;
 (b) Emtn.forward with everything off, with the BasicBlocks fused, and with the blocks and the stems fused, legs off, resnets, stem, stem,
 resnets, off.
+--rotation measures the 6DRepNet switch instead (model.RepVGGBlockFused, model.native_rotation_net; csrc/conv2d_grp_f16x3.hip for its
+thirteen groups = 2 blocks), same timer and rules: (a) `rotation_net.predict` alone, legs off, on, on, off, and for context the unswapped
+net under torch.autocast(float16); (b) Emtn.forward with everything off, with the ResNets and stems fused, and with the ResNets, the
+stems and the rotation net fused, legs off, resnets+stem, all, all, resnets+stem, off, and the all-off call under autocast(float16).
 usage: python tools/bench_emtn.py [--b 1 8] [--warmup 5] [--runs 20] [--out profiles/emtn_timing.json]
-       python tools/bench_emtn.py --stem [--b 1 8] [--out profiles/emtn_stem_timing.json]"""
+       python tools/bench_emtn.py --stem [--b 1 8] [--out profiles/emtn_stem_timing.json]
+       python tools/bench_emtn.py --rotation [--b 1 8] [--out profiles/rotation_net_timing.json]"""
 import argparse, json, os, statistics, subprocess, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -91,6 +96,55 @@ def stem_timing(a, dev, emtn):
     return out
 
 
+def rotation_timing(a, dev, emtn):
+    """--rotation: (a) rotation_net.predict alone, (b) Emtn.forward off / ResNets and stems on / those and the rotation net on."""
+    det = emtn.rotation_net
+    gen = torch.Generator().manual_seed(7)
+    with torch.no_grad():   # He initialisation: activations stay O(1) through the 28 ReLU layers, as a trained net's do
+        for m in det.model.modules():
+            if isinstance(m, torch.nn.Conv2d):
+                torch.nn.init.kaiming_normal_(m.weight, mode="fan_in", nonlinearity="relu", generator=gen)
+                m.bias.normal_(0.0, 0.1, generator=gen)
+    det.model.to(dev)
+    out = {"what": "the frozen 6DRepNet (RepVGG-B1g2, deploy form) of Emtn: 27 of its 28 blocks as one matrix-core launch each",
+           "commit": commit(), "device": torch.cuda.get_device_name(0), "torch": torch.__version__, "H": a.hw, "W": a.hw, "warmup": a.warmup,
+           "runs": a.runs, "timer": "HIP events around each call after `warmup` calls; median (and minimum) of `runs` calls, ms per call",
+           "predict_order": ["off", "on", "on", "off"], "forward_order": ["off", "resnets+stem", "all", "all", "resnets+stem", "off"],
+           "batches": {}}
+    mean = lambda legs, key, val: round(statistics.mean(l["median_ms"] for l in legs if l[key] == val), 4)
+    with torch.no_grad():
+        for b in a.b:
+            x = torch.rand(b, 3, a.hw, a.hw, device=dev) * 2 - 1
+            legs = []
+            for on in (False, True, True, False):
+                M.native_rotation_net(emtn, on)
+                med, best = median_ms(lambda: det.predict(x), a.warmup, a.runs)
+                legs.append({"native_rotation_net": on, "median_ms": round(med, 4), "min_ms": round(best, 4)})
+            with torch.autocast(device_type="cuda", dtype=torch.float16):
+                amp, amp_best = median_ms(lambda: det.predict(x), a.warmup, a.runs)
+            M.native_rotation_net(emtn, True)
+            deg_on, _ = det.predict(x)
+            M.native_rotation_net(emtn, False)
+            deg_off, _ = det.predict(x)
+            off, on = mean(legs, "native_rotation_net", False), mean(legs, "native_rotation_net", True)
+            predict = {"legs": legs, "off_ms": off, "on_ms": on, "off_over_on": round(off / on, 3), "torch_autocast_fp16_ms": round(amp, 4),
+                       "torch_autocast_fp16_min_ms": round(amp_best, 4), "degrees_on_vs_off_max_abs": (deg_on - deg_off).abs().max().item()}
+            flegs = []
+            for mode in (0, 1, 2, 2, 1, 0):
+                emtn.native_resnets(mode > 0, fuse_stem=mode > 0)
+                emtn.native_rotation_net(mode == 2)
+                med, best = median_ms(lambda: emtn(x), a.warmup, a.runs)
+                flegs.append({"mode": ("off", "resnets+stem", "all")[mode], "median_ms": round(med, 4), "min_ms": round(best, 4)})
+            with torch.autocast(device_type="cuda", dtype=torch.float16):
+                famp, famp_best = median_ms(lambda: emtn(x), a.warmup, a.runs)
+            out["batches"][str(b)] = {"predict": predict,
+                                      "forward": {"legs": flegs, "off_ms": mean(flegs, "mode", "off"),
+                                                  "resnets_stem_ms": mean(flegs, "mode", "resnets+stem"), "all_ms": mean(flegs, "mode", "all"),
+                                                  "torch_autocast_fp16_ms": round(famp, 4), "torch_autocast_fp16_min_ms": round(famp_best, 4)}}
+            del x
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--b", type=int, nargs="+", default=[1, 8])
@@ -99,6 +153,7 @@ def main():
     ap.add_argument("--runs", type=int, default=20)
     ap.add_argument("--out")
     ap.add_argument("--stem", action="store_true", help="measure the fused stem (model.StemFused) instead; see the module docstring")
+    ap.add_argument("--rotation", action="store_true", help="measure the 6DRepNet switch (model.native_rotation_net) instead; see the module docstring")
     a = ap.parse_args()
     if a.runs < 20:
         ap.error("--runs: the median of at least 20 runs is reported")
@@ -106,8 +161,8 @@ def main():
     torch.manual_seed(20241018)
     torch.backends.cudnn.benchmark = True
     emtn = E.Emtn().to(dev).eval()
-    if a.stem:
-        out = stem_timing(a, dev, emtn)
+    if a.stem or a.rotation:
+        out = rotation_timing(a, dev, emtn) if a.rotation else stem_timing(a, dev, emtn)
         print(json.dumps(out))
         if a.out:
             with open(a.out, "w") as f:
