@@ -229,8 +229,9 @@ warp_frame_box_kernel(const float *__restrict__ coords, int *__restrict__ fbox, 
         }
         const int ex = min(hx + 1, W - 1) - lx + 1, ey = min(hy + 1, H - 1) - ly + 1, ez = min(hz + 1, D - 1) - lz + 1;
         const int e = max(max(ex, ey), max(ez, DENSE_E_MIN));
-        // (the GEMM walks the outputs in aligned groups of 4: 16-byte loads of dout)
-        const bool shape_ok = (H * W) % 4 == 0 && vol >= 32;
+        // (the GEMM walks the outputs in aligned groups of 4: 16-byte loads of dout; and in whole iterations of 32: its split over the
+        // waves and the clamped prefetch of warp_bwd_dense_dv_kernel have no partial last iteration to get wrong)
+        const bool shape_ok = (H * W) % 4 == 0 && vol >= 32 && vol % 32 == 0;
         int *o = fbox + b * FBOX_INTS;
         o[0] = lx; o[1] = ly; o[2] = lz; o[3] = ex; o[4] = ey; o[5] = ez;
         o[6] = (e <= DENSE_E_MAX && shape_ok && allow_dense) ? e : 0;
@@ -255,7 +256,8 @@ warp_bwd_dense_dv_kernel(const float *__restrict__ coords, const float *__restri
     const int cblk = blockIdx.y * (MT * 32);
     // this wave's outputs: [t0, t1), walked 32 at a time: lane half h takes outputs +16h .. +16h+15, one per k-step (the order of
     // the k index is free).  One iteration = 16 k-steps x MT x NT MFMAs (1.5-6 us of matrix time), with the next iteration's
-    // loads (4 x 16 B of dout per lane and row tile, one coordinate triple per lane) in flight underneath.
+    // loads (4 x 16 B of dout per lane and row tile, one coordinate triple per lane) in flight underneath.  vol % 32 == 0 (shape_ok of
+    // warp_frame_box_kernel): the 256 ranges cover the frame and every iteration is a whole one — neither holds for a ragged volume.
     const size_t per_wave = (vol / 32 + DENSE_SEGS * 4 - 1) / (DENSE_SEGS * 4) * 32;
     const size_t t0 = min(vol, ((size_t)blockIdx.x * 4 + wave) * per_wave), t1 = min(vol, t0 + per_wave);
     // LDS table of the current 32 outputs: per output the dense per-axis weight vectors fx[0..E), fy[0..E), fz[0..E) (a slot of
