@@ -707,6 +707,33 @@ int mphip_conv2d_grouped_fwd(const float *x, const float *x_range, const void *w
                              float *out_range, int N, int Ci, int Co, int H, int W, int groups, int relu, void *workspace,
                              size_t workspace_bytes, void *stream);
 
+/* Split-K (added within ABI 25: exports only, no signature or layout above changed; a caller that may meet an older ABI-25 library
+ * probes for these entries, e.g. dlsym of mphip_conv2d_split_supported; csrc/conv2d_splitk_f16x3.hip): mphip_conv2d_grouped_fwd with the
+ * reduction over the (Ci / groups) / 16 input-channel chunks split over `splits` workgroups per (16 x 16-pixel tile, 64-channel tile), for
+ * the 64^2 .. 16^2 maps of layer3 / layer4 of Emtn's ResNet-18s and of the RepVGG backbone at B = 1, where the unsplit kernels start only
+ * 4 .. 64 workgroups.  Two launches: K range z = chunks [z * nchunks / splits, (z + 1) * nchunks / splits) leaves its raw fp32
+ * accumulators (from +0; the unsplit kernels' staging, MFMA sequence and slab index) in part[z][N,Co,H,W] of the workspace; a finish
+ * launch computes  a = part[0]; a = a + part[z], z = 1 .. splits - 1, in that order;  y = act(a * unscale + bias[co] (+ residual)),  each
+ * term rounded on its own, and out_range (exact max|y|).  No arrival counters, no floating-point atomics: the bits are reproducible, and
+ * with one descriptor of x and one header scale they are those of  act(((y_0 + y_1) + ... + y_{splits-1}) + bias (+ residual))  in fp32,
+ * y_z = mphip_conv2d_fwd of K range z with a zero bias (power-of-two scales commute with rounding away from underflow).
+ * w_packed: the ordinary pack; groups > 1: the grouped pack of [Co, Ci / groups].  fp32 maps, stride 1, one source, three products.
+ * Shapes (mphip_conv2d_split_supported): mphip_conv2d_grouped_supported(N, Ci, Co, H, W, groups), 1 <= splits <= 16, and splits divides
+ * (Ci / groups) / 16.  splits == 1 launches the plain or the grouped kernel: the bits, the workspace and the verdicts of those entries.
+ * mphip_conv2d_splits: the library's recommendation for a shape, 1 = do not split (a shape no entry takes: 1); DESIGN.md section 3.14.
+ * Workspace (mphip_conv2d_split_workspace_bytes; 4-byte aligned, must not alias x, y or residual): the descriptor slot of x (used when
+ * x_range == NULL), then `splits` partial maps of N * Co * H * W floats (splits > 1; REQUIRED then, with or without x_range).  The finish
+ * launch takes 16-byte accesses when H * W % 4 == 0 and the partial maps, y and residual lie on 16-byte boundaries, else 4-byte ones:
+ * the same bits.  Refusals come before the first HIP call in the shared order (null pointer, shape, alignment, aliasing, workspace size
+ * and alignment) and, last, partial maps that alias x, y or residual (MPHIP_EINVAL); messages name conv2d_split_fwd.  Saturation is
+ * counted in the unit's own counter (mphip_f16x3_saturation_count sums it).                                                          */
+int mphip_conv2d_split_supported(int N, int Ci, int Co, int H, int W, int groups, int splits);
+int mphip_conv2d_splits(int N, int Ci, int Co, int H, int W, int groups);
+size_t mphip_conv2d_split_workspace_bytes(int N, int Ci, int Co, int H, int W, int groups, int splits);
+int mphip_conv2d_split_fwd(const float *x, const float *x_range, const void *w_packed, const float *bias, const float *residual, float *y,
+                           float *out_range, int N, int Ci, int Co, int H, int W, int groups, int splits, int relu, void *workspace,
+                           size_t workspace_bytes, void *stream);
+
 /* The reference's reduced-precision policy for the convs (train.py:145,188: the generator step runs under torch.cuda.amp.autocast(), its
  * conv3d calls take f16 operands with fp32 accumulation).  mphip_conv3d_set_half_products(1) makes the CALLING THREAD's subsequent precision-1
  * 3x3x3 launches that run in the F(2,3) domain (mphip_conv3d_kernel_variant == 5: G3d's levels 0-2, Eapp's 3-D tail, their bwd-data

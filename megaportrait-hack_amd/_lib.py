@@ -168,6 +168,11 @@ SIGNATURES = {
     "mphip_conv2d_grouped_supported": (_i, [_i] * 6),
     "mphip_conv2d_grouped_workspace_bytes": (_sz, [_i] * 6),
     "mphip_conv2d_grouped_fwd": (_i, [_p] * 7 + [_i] * 7 + [_p, _sz, _p]),
+    # its split-K form (added within ABI 25, csrc/conv2d_splitk_f16x3.hip): splits after groups
+    "mphip_conv2d_split_supported": (_i, [_i] * 7),
+    "mphip_conv2d_splits": (_i, [_i] * 6),
+    "mphip_conv2d_split_workspace_bytes": (_sz, [_i] * 7),
+    "mphip_conv2d_split_fwd": (_i, [_p] * 7 + [_i] * 8 + [_p, _sz, _p]),
     "mphip_build_flags": (_i, []),
     "mphip_graph_memsets_to_kernels": (_i, [_p, ctypes.POINTER(ctypes.c_int)]),
     "mphip_graph_memset_nodes_left": (_i, [_p, ctypes.POINTER(ctypes.c_int)]),

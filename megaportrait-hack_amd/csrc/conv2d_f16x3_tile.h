@@ -34,6 +34,11 @@
 //   GRP       a grouped conv: x is [N,Ci,H,W], the weight [Co,Ci/groups,3,3] in the ordinary pack, and output channel tile `cot` belongs
 //             to group cot / grp_cots (grp_cots = 64-channel tiles per group).  The K loop runs over the grp_cig / 16 chunks that start
 //             at channel group * grp_cig of an image whose stride is Ci channels.  Nothing else differs.
+//
+// And one instantiated by conv2d_splitk_f16x3.hip, alone and with GRP (every other unit is SPLIT = false; the unit's header has the contract):
+//   SPLIT     one K range of a conv whose reduction is split over gridDim.z workgroups: workgroup z runs chunks [z * nchunks / Z,
+//             (z + 1) * nchunks / Z) of the K loop (GRP: of its group's chunks) and stores its raw fp32 accumulators, neither unscaled nor
+//             biased, to y + z * part_stride, masked like any store; bias, residual, relu and out_range are not read.
 #pragma once
 #include <algorithm>
 
@@ -129,17 +134,20 @@ __device__ __forceinline__ float up2_blend(float x00, float x01, float x10, floa
 }
 
 // SAT: the instantiating unit's saturation counter
-template <bool CAT, unsigned long long *SAT, int XDT = MPHIP_DTYPE_F32, int YDT = MPHIP_DTYPE_F32, int NP = 3, int UP = 0, bool GRP = false>
+template <bool CAT, unsigned long long *SAT, int XDT = MPHIP_DTYPE_F32, int YDT = MPHIP_DTYPE_F32, int NP = 3, int UP = 0, bool GRP = false,
+          bool SPLIT = false>
 __device__ __forceinline__ void conv2d_k3_tile(const dtype_t<XDT> *__restrict__ x, const float *__restrict__ x_range, const C2CatArgs cat,
                                                const _Float16 *__restrict__ wslabs, const float *__restrict__ whdr,
                                                const float *__restrict__ bias, const float *__restrict__ residual,
                                                dtype_t<YDT> *__restrict__ y, float *__restrict__ out_range, int Ci, int Co, int H, int W,
                                                int relu, int tiles_w, int tiles_h, unsigned nslots,
-                                               const dtype_t<YDT> *__restrict__ residual_t = nullptr, int grp_cig = 0, int grp_cots = 1) {
+                                               const dtype_t<YDT> *__restrict__ residual_t = nullptr, int grp_cig = 0, int grp_cots = 1,
+                                               size_t part_stride = 0) {
     static_assert(NP == 3 || NP == 1, "three products (f16x3) or one (the autocast policy)");
     static_assert(!CAT || XDT == MPHIP_DTYPE_F32, "the two-source form stages fp32 sources");
     static_assert(UP == 0 || (!CAT && XDT == MPHIP_DTYPE_F32 && YDT == MPHIP_DTYPE_F32 && NP == 3), "the up2 forms: one fp32 source, three products");
     static_assert(!GRP || (!CAT && XDT == MPHIP_DTYPE_F32 && YDT == MPHIP_DTYPE_F32 && NP == 3 && UP == 0), "the grouped form: one fp32 source, three products");
+    static_assert(!SPLIT || (!CAT && XDT == MPHIP_DTYPE_F32 && YDT == MPHIP_DTYPE_F32 && NP == 3 && UP == 0), "the split-K form: one fp32 source, three products");
     constexpr int NPART = NP == 3 ? 2 : 1;                   // operand halves in LDS: hi and lo, or hi alone
     constexpr int W_HALFS = C2_SLAB_HALFS / 2 * NPART;       // of a slab, the planes this kernel fetches
     __shared__ __attribute__((aligned(16))) _Float16 smem[W_HALFS + NPART * C2_X_PART];
@@ -348,15 +356,20 @@ __device__ __forceinline__ void conv2d_k3_tile(const dtype_t<XDT> *__restrict__ 
             *reinterpret_cast<u32x4 *>(ups + C2_UP_PATCH + tid * 4) = ent;
         }
     }
-    C2_LOAD_CHUNK(0)
+    int c_lo = 0, c_hi = nchunks;   // the K range of this workgroup: all of it unless SPLIT
+    if constexpr (SPLIT) {
+        const int z = blockIdx.z, nz = gridDim.z;
+        c_lo = z * nchunks / nz, c_hi = (z + 1) * nchunks / nz;
+    }
+    C2_LOAD_CHUNK(c_lo)
     if constexpr (CAT || UP == 1) {
         C2_PARK_AFFINE()
         __syncthreads();
     }
-    C2_WRITE_CHUNK(0)
+    C2_WRITE_CHUNK(c_lo)
     __syncthreads();
-    for (int c = 0; c < nchunks; ++c) {
-        const bool more = c + 1 < nchunks;
+    for (int c = c_lo; c < c_hi; ++c) {
+        const bool more = c + 1 < c_hi;
         if (more) C2_LOAD_CHUNK(c + 1)   // in flight during this chunk's MFMAs
 #pragma unroll
         for (int tap = 0; tap < 9; ++tap) {
@@ -402,7 +415,7 @@ __device__ __forceinline__ void conv2d_k3_tile(const dtype_t<XDT> *__restrict__ 
 #undef C2_WRITE_CHUNK
 
     // epilogue: unscale (a power of two), bias, residual, ReLU in fp32; stores masked at the ragged edge and past Co
-    const float unscale = whdr[0] * x_unscale;
+    const float unscale = SPLIT ? 0.0f : whdr[0] * x_unscale;   // (SPLIT: no header is read)
     unsigned ymax = 0;
     unsigned ro[2][4];          // UP = 2: this lane's four offsets into a channel of r, per column tile, ...
     float rlam[2], rmu = 0.0f;  // ... and its weights
@@ -430,6 +443,10 @@ __device__ __forceinline__ void conv2d_k3_tile(const dtype_t<XDT> *__restrict__ 
                     for (int reg = 0; reg < 16; ++reg) {
                         const int row = (reg & 3) + 8 * (reg >> 2);
                         const size_t oi = o + (size_t)row * HW;
+                        if constexpr (SPLIT) {   // the raw accumulator of this K range: the finish kernel owns the epilogue
+                            y[(size_t)blockIdx.z * part_stride + oi] = acc[m][t][reg];
+                            continue;
+                        }
                         float v = acc[m][t][reg] * unscale + bias[co0 + 4 * kg + row];
                         if constexpr (UP == 2) {   // + up2(r): the blend, then one add
                             const float *const rc = residual + ((size_t)n * Co + co0 + 4 * kg + row) * ((size_t)xh * xw);
@@ -449,7 +466,7 @@ __device__ __forceinline__ void conv2d_k3_tile(const dtype_t<XDT> *__restrict__ 
             }
         }
     }
-    if (out_range) {   // workgroup-uniform
+    if (!SPLIT && out_range) {   // workgroup-uniform
         ymax = wave_umax(ymax);
         if (lane == 0) red[wave] = ymax;
         __syncthreads();

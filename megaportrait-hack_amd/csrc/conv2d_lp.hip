@@ -117,9 +117,12 @@ void conv2d_lp_launch(const C2Call &c, const C2Grid &g) {
 
 // The host side of every 2-D 3x3 conv entry (the stride-2 entry of conv2d_s2_f16x3.hip included: c.stride == 2, extents of y and
 // residual from the halved map; and the two of conv2d_up2_f16x3.hip: c.up2 == 1, y and residual on the doubled map, c.up2 == 2, the
-// residual on the halved one; and the grouped one of conv2d_grp_f16x3.hip: c.groups != 0, the group rule ahead of the plain shape rule).
+// residual on the halved one; and the grouped one of conv2d_grp_f16x3.hip: c.groups != 0, the group rule ahead of the plain shape rule;
+// and the split-K one of conv2d_splitk_f16x3.hip: c.splits != 0, the split rule ahead of the group rule, the partial maps in the
+// workspace behind the descriptor slot).
 // The rules in the order they are checked, all before the first HIP call: dtypes and products (lp_rule), pointers, the second source, the shape, alignment, tables, aliasing (MPHIP_EINVAL each), then the workspace
-// (MPHIP_EWORKSPACE).  Messages carry the called entry's name; a three-product call (all of its maps are fp32) is the fp32 entry's call
+// (MPHIP_EWORKSPACE for its size, then MPHIP_EINVAL for its alignment and, for the split-K entry, for partial maps that alias x, y or the
+// residual: that check needs the workspace, so it is the last one).  Messages carry the called entry's name; a three-product call (all of its maps are fp32) is the fp32 entry's call
 // under whichever name it came in, and reports under that entry's name.
 int conv2d_run(C2Call c) {
     int np = 0;
@@ -133,9 +136,14 @@ int conv2d_run(C2Call c) {
     MPHIP_REQUIRE(up == 0 || ((up == 1 || up == 2) && !s2 && !c.cat && np == 3), "%s: the up2 convs are plain fp32 three-product forms", c.who);
     const int grp = c.groups;
     MPHIP_REQUIRE(grp == 0 || (!s2 && !up && !c.cat && np == 3), "%s: the grouped conv is the plain fp32 three-product form at stride 1", c.who);
+    const int spl = c.splits;
+    MPHIP_REQUIRE(spl == 0 || grp != 0, "%s: the split-K conv takes a group count", c.who);
     const char *who = s2 || up || grp ? c.who : c.products == 3 ? (c.cat ? "conv2d_cat_fwd" : "conv2d_fwd") : c.who;
     MPHIP_REQUIRE(c.x1 && c.w_packed && c.bias && c.y && (up != 2 || c.residual), "%s: null pointer", who);
     MPHIP_REQUIRE(c.C2 >= 0 && (c.x2 != nullptr) == (c.C2 > 0), "%s: x2 and C2 = %d: a second source needs both, one source neither", who, c.C2);
+    MPHIP_REQUIRE(spl == 0 || c2_split_supported(c.N, c.C1, c.Co, c.H, c.W, grp, spl),
+                  "%s: unsupported shape N=%d Ci=%d Co=%d H=%d W=%d groups=%d splits=%d (the shape rule of conv2d_grouped_fwd; 1 <= splits <= %d, "
+                  "a divisor of the (Ci / groups) / 16 chunks)", who, c.N, c.C1, c.Co, c.H, c.W, grp, spl, C2_MAX_SPLITS);
     MPHIP_REQUIRE(grp == 0 || c2_grouped_supported(c.N, c.C1, c.Co, c.H, c.W, grp),
                   "%s: unsupported shape N=%d Ci=%d Co=%d H=%d W=%d groups=%d (groups >= 1; above 1: Ci and Co multiples of groups, (Ci / groups) "
                   "%% 16 == 0, (Co / groups) %% 64 == 0; and the shape rule of conv2d_fwd)", who, c.N, c.C1, c.Co, c.H, c.W, grp);
@@ -161,14 +169,22 @@ int conv2d_run(C2Call c) {
                       !c2_overlap(c.y, ny * yb, c.residual, nr * rb),
                   "%s: y must not alias a source or residual (a workgroup reads the halo of tiles other workgroups write)", who);
     const bool scan1 = !c.x1_range, scan2 = c.x2 && !c.x2_range;
-    if (scan1 || scan2) {
-        const size_t need = c2_workspace_bytes((scan1 ? 1 : 0) + (scan2 ? 1 : 0));
+    const size_t part_bytes = spl > 1 ? (size_t)spl * ny * sizeof(float) : 0;   // the split-K partial maps, behind the descriptor slots
+    float *part = nullptr;
+    if (scan1 || scan2 || part_bytes) {
+        const size_t need = c2_workspace_bytes((scan1 ? 1 : 0) + (scan2 ? 1 : 0)) + part_bytes;
         if (!c.workspace || c.workspace_bytes < need) {
             set_error("%s: workspace %zu bytes < required %zu", who, c.workspace_bytes, need);
             return MPHIP_EWORKSPACE;
         }
         MPHIP_REQUIRE(((uintptr_t)c.workspace & 3) == 0, "%s: the workspace must be 4-byte aligned", who);
         float *slot = (float *)c.workspace;
+        if (part_bytes) {   // the last refusal, still ahead of the scans below: the first HIP call
+            part = slot + ((scan1 ? 1 : 0) + (scan2 ? 1 : 0)) * MPHIP_RANGE_FLOATS;
+            MPHIP_REQUIRE(!c2_overlap(part, part_bytes, c.y, ny * yb) && !c2_overlap(part, part_bytes, c.x1, n1 * xb) &&
+                              !c2_overlap(part, part_bytes, c.residual, nr * rb),
+                          "%s: the workspace's partial maps must not alias x, y or residual", who);
+        }
         if (scan1) {
             if (c.x_dtype == MPHIP_DTYPE_F32) {
                 conv2d_range_launch((const float *)c.x1, n1, slot, c.stream);
@@ -187,10 +203,11 @@ int conv2d_run(C2Call c) {
     g.tiles_w = cdiv(Wo, s2 ? C2S2_TW : C2_TW), g.tiles_h = cdiv(Ho, s2 ? C2S2_TH : C2_TH);
     const long long tiles = (long long)c.N * g.tiles_h * g.tiles_w;   // (N * H * W < 2^31 by the shape rule: they fit grid.x)
     g.grid = dim3((unsigned)tiles, (unsigned)c2_cots(c.Co));
-    g.nslots = (unsigned)std::min<long long>(tiles * c2_cots(c.Co), (long long)RANGE_MAX_PARTS);
+    g.nslots = (unsigned)std::min<long long>(part ? (long long)c2_split_finish_blocks(ny) : tiles * c2_cots(c.Co), (long long)RANGE_MAX_PARTS);
     if (c.out_range) conv2d_out_range_init_launch(c.out_range, g.nslots, c.stream);
     if (s2) conv2d_s2_launch(c, g);
     else if (up) conv2d_up2_launch(c, g);
+    else if (part) conv2d_split_launch(c, g, part);
     else if (grp > 1) conv2d_grouped_launch(c, g);
     else if (c.products == 1) conv2d_lp_launch(c, g);
     else if (c.cat) conv2d_cat_launch(c, g);

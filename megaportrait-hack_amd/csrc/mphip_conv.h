@@ -175,6 +175,8 @@ int conv2d_s2_saturation(unsigned long long *count, int reset);
 int conv2d_up2_saturation(unsigned long long *count, int reset);
 // conv2d_grp_f16x3.hip: the grouped form (mphip_conv2d_grouped_fwd), likewise
 int conv2d_grp_saturation(unsigned long long *count, int reset);
+// conv2d_splitk_f16x3.hip: the split-K form (mphip_conv2d_split_fwd, splits > 1), likewise
+int conv2d_split_saturation(unsigned long long *count, int reset);
 
 // One call of the 2-D 3x3 conv, as its eight C entries describe it to conv2d_run (conv2d_lp.hip).  Zero-initialised it is the plain fp32
 // form: the plain form is one source (C2 = 0, no tables), the fp32 entries are fp32 dtypes with three products.
@@ -187,6 +189,9 @@ struct C2Call {
     int groups;             // conv2d_grp_f16x3.hip (plain form, fp32 maps, three products, stride 1, no up2).  0: not that entry's call.
                             // Otherwise the call reports under its own name; > 1: x1 [N,C1,H,W] in `groups` groups, the pack that of a
                             // [Co,C1/groups,3,3] weight; 1: the plain kernel; < 0: a group count the shape rule refuses
+    int splits;             // conv2d_splitk_f16x3.hip (the grouped entry's forms: c.groups != 0).  0: not that entry's call.  > 1: the
+                            // reduction runs in `splits` K ranges that leave partial maps in the workspace, behind the descriptor slot,
+                            // and a finish launch; 1: the plain or grouped kernel; < 0: a count the shape rule refuses
     bool cat;               // the two-source kernels (also with C2 == 0: they are kernels of their own); false: the plain ones
     const void *x1, *x2;    // sources [N,C1,H,W] and [N,C2,H,W] or NULL; x1 in x_dtype (fp32 when cat), x2 fp32
     const float *aff1, *aff2, *x1_range, *x2_range;
@@ -227,6 +232,14 @@ bool c2_up2_supported(int N, int Ci, int Co, int h, int w);
 // conv2d_grp_f16x3.hip: its shape rule: groups >= 1 and c2_supported; groups > 1: Ci and Co multiples of groups, (Ci / groups) % 16 == 0,
 // (Co / groups) % 64 == 0
 bool c2_grouped_supported(int N, int Ci, int Co, int H, int W, int groups);
+// conv2d_splitk_f16x3.hip: its shape rule: c2_grouped_supported, 1 <= splits <= C2_MAX_SPLITS, ((Ci / groups) / 16) % splits == 0; the
+// constants of mphip_conv2d_splits; the workgroups of its finish launch over ny = N * Co * H * W elements (one
+// out_range slot each, up to RANGE_MAX_PARTS); and its two launches (c.splits > 1; part: c.splits maps of ny floats)
+constexpr int C2_MAX_SPLITS = 16;
+constexpr int C2_SPLIT_MAX_S = 8, C2_SPLIT_MIN_CHUNKS = 2, C2_SPLIT_MAX_WG = 512, C2_SPLIT_MIN_K = 8, C2_SPLIT_MAX_UNSPLIT_WG = 128;
+bool c2_split_supported(int N, int Ci, int Co, int H, int W, int groups, int splits);
+unsigned c2_split_finish_blocks(size_t ny);
+void conv2d_split_launch(const C2Call &c, const C2Grid &g, float *part);
 
 // api.hip: the calling thread's conv arithmetic policy (mphip_conv3d_set_half_products): true inside torch.autocast(float16) regions
 bool conv_half_products();

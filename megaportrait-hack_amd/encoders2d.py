@@ -295,7 +295,7 @@ class Emtn(nn.Module):
         self.expression_net.adaptive_pool = nn.AdaptiveAvgPool2d(FEATURE_SIZE)  # model.py:881: appended, runs last
         self.fc = nn.Linear(2048, COMPRESS_DIM)
 
-    def native_resnets(self, enable: bool = True, fuse_stem: bool = False) -> "Emtn":
+    def native_resnets(self, enable: bool = True, fuse_stem: bool = False, split_small_maps: bool = False) -> "Emtn":
         """Opt-in, inference only: run the eight BasicBlocks of `head_pose_net` and of `expression_net` as model.BasicBlockFused —
         BatchNorm folded, the 3x3 convs on the matrix cores with fp32-class accuracy (csrc/conv2d_f16x3.hip, and
         csrc/conv2d_s2_f16x3.hip for the three stride-2 convs of a net) — over the blocks' own children: same Parameter objects, same
@@ -303,18 +303,22 @@ class Emtn(nn.Module):
         blocks evaluate the original PyTorch expression; there is no half_precision form.
         fuse_stem (off by default): each net's 3->64 stem (conv, BatchNorm, ReLU, max-pool) also becomes one launch of
         csrc/conv2d_stem.hip (model.StemFused, model.native_emtn_stems); without the keyword, or with enable off, the original four
-        modules are put back.  The pools and the `fc`s stay on PyTorch; the 6DRepNet has a switch of its own, native_rotation_net."""
-        M.native_emtn_resnets(self, enable)
+        modules are put back.  The pools and the `fc`s stay on PyTorch; the 6DRepNet has a switch of its own, native_rotation_net.
+        split_small_maps (off by default): the blocks' stride-1 convs take the split-K launch where the library recommends one
+        (ops.conv2d_splits; csrc/conv2d_splitk_f16x3.hip); without the keyword they are back on the unsplit kernels."""
+        M.native_emtn_resnets(self, enable, split_small_maps)
         M.native_emtn_stems(self, bool(enable and fuse_stem))
         return self
 
-    def native_rotation_net(self, enable: bool = True) -> "Emtn":
+    def native_rotation_net(self, enable: bool = True, split_small_maps: bool = False) -> "Emtn":
         """Opt-in, inference only: run the 27 deploy-form RepVGG blocks of `rotation_net`'s `layer1..layer4` (3x3 conv + bias + ReLU
         each) as model.RepVGGBlockFused — one matrix-core launch per block with fp32-class accuracy: csrc/conv2d_f16x3.hip,
         csrc/conv2d_s2_f16x3.hip for the four stride-2 blocks and csrc/conv2d_grp_f16x3.hip for the thirteen groups = 2 blocks — over
         the blocks' own children: same Parameter objects, same state-dict keys.  `enable=False` puts the original blocks back.
-        `layer0` (3 -> 64 at stride 2), the pool, `linear_reg` and the Gram-Schmidt step stay on PyTorch.  Independent of native_resnets."""
-        M.native_rotation_net(self, enable)
+        `layer0` (3 -> 64 at stride 2), the pool, `linear_reg` and the Gram-Schmidt step stay on PyTorch.  Independent of native_resnets.
+        split_small_maps (off by default): the stride-1 plain and grouped launches take the split-K form where the library recommends
+        one (ops.conv2d_splits); without the keyword they are back on the unsplit kernels."""
+        M.native_rotation_net(self, enable, split_small_maps)
         return self
 
     def forward(self, x):

@@ -75,7 +75,8 @@ class Gbase(M._HotSliceRunner, nn.Module):
         M.native_eapp_trunk(self.appearanceEncoder, enable, half_precision)
         return self
 
-    def native_motion_encoder(self, enable: bool = True, fuse_stem: bool = False, rotation_net: bool = False) -> "Gbase":
+    def native_motion_encoder(self, enable: bool = True, fuse_stem: bool = False, rotation_net: bool = False,
+                              split_small_maps: bool = False) -> "Gbase":
         """Opt-in (off by default), inference only: the BasicBlocks of the motion encoder's two ResNet-18s (`head_pose_net`,
         `expression_net`) as model.BasicBlockFused — BatchNorm folded, 3x3 convs on the matrix cores, the stride-2 ones included
         (model.native_emtn_resnets); `enable=False` restores the original blocks.  Same parameters and state-dict keys.
@@ -84,10 +85,12 @@ class Gbase(M._HotSliceRunner, nn.Module):
         rotation_net (off by default): the 27 deploy-form RepVGG blocks of the frozen 6DRepNet's `layer1..layer4` as one matrix-core
         launch each, the groups = 2 ones on the grouped kernel (model.RepVGGBlockFused; model.native_rotation_net); without it, or
         with enable off, the original blocks are back.  The pools, the `fc`s, and of the 6DRepNet `layer0`, the pool and `linear_reg`
-        stay on PyTorch.  With channels_last_2d() the image and a block's input map are copied to NCHW once."""
-        M.native_emtn_resnets(self.motionEncoder, enable)
+        stay on PyTorch.  With channels_last_2d() the image and a block's input map are copied to NCHW once.
+        split_small_maps (off by default): the stride-1 convs of every block fused here take the split-K launch where the library
+        recommends one (ops.conv2d_splits; csrc/conv2d_splitk_f16x3.hip); without it they are back on the unsplit kernels."""
+        M.native_emtn_resnets(self.motionEncoder, enable, split_small_maps)
         M.native_emtn_stems(self.motionEncoder, bool(enable and fuse_stem))
-        M.native_rotation_net(self.motionEncoder, bool(enable and rotation_net))
+        M.native_rotation_net(self.motionEncoder, bool(enable and rotation_net), split_small_maps)
         return self
 
     def _nhwc(self, x):

@@ -77,7 +77,8 @@ def patch_functions(model_module) -> List[str]:
 
 def install(gbase: nn.Module, model_module: Optional[object] = None, eapp_tail: bool = True, g2d_final: bool = False,
             g2d_body: bool = False, eapp_trunk: bool = False, half_precision: bool = False, fuse_upsample: bool = False,
-            motion_encoder: bool = False, fuse_stem: bool = False, rotation_net: bool = False) -> List[str]:
+            motion_encoder: bool = False, fuse_stem: bool = False, rotation_net: bool = False,
+            split_small_maps: bool = False) -> List[str]:
     """swap_hot_path + patch_functions.  `model_module` is the imported reference `model` module (the one that defines
     Gbase); pass it so the two `apply_warping_field` call sites inside Gbase.forward use the HIP kernel too.
     g2d_final (off by default): also swap `gbase.G2d.final_conv` (model.py:747-752) for model.G2dFinalConv, which shares the
@@ -96,7 +97,11 @@ def install(gbase: nn.Module, model_module: Optional[object] = None, eapp_tail: 
     Emtn.native_resnets has it (fuse_upsample without g2d_body is ignored silently; a new keyword does not repeat that).
     rotation_net (off by default): with motion_encoder, the 27 deploy-form RepVGG blocks of the frozen 6DRepNet
     (`gbase.motionEncoder.rotation_net`) become model.RepVGGBlockFused, one matrix-core launch each (inference only;
-    model.native_rotation_net).  Without motion_encoder it is a ValueError, like fuse_stem."""
+    model.native_rotation_net).  Without motion_encoder it is a ValueError, like fuse_stem.
+    split_small_maps (off by default): with motion_encoder, the stride-1 convs of the blocks fused there take the split-K launch where the
+    library recommends one (ops.conv2d_splits).  Without motion_encoder it is a ValueError, like fuse_stem."""
+    if split_small_maps and not motion_encoder:
+        raise ValueError("install: split_small_maps=True needs motion_encoder=True")
     if fuse_stem and not motion_encoder:
         raise ValueError("install: fuse_stem=True needs motion_encoder=True")
     if rotation_net and not motion_encoder:
@@ -109,11 +114,11 @@ def install(gbase: nn.Module, model_module: Optional[object] = None, eapp_tail: 
     if eapp_trunk and M.native_eapp_trunk(getattr(gbase, "appearanceEncoder", None), True, half_precision):
         done.append("Eapp.trunk2d")
     emtn = getattr(gbase, "motionEncoder", None)
-    if motion_encoder and M.native_emtn_resnets(emtn, True):
+    if motion_encoder and M.native_emtn_resnets(emtn, True, split_small_maps):
         done.append("Emtn.resnets")
     if motion_encoder and fuse_stem and M.native_emtn_stems(emtn, True):
         done.append("Emtn.stems")
-    if motion_encoder and rotation_net and M.native_rotation_net(emtn, True):
+    if motion_encoder and rotation_net and M.native_rotation_net(emtn, True, split_small_maps):
         done.append("Emtn.rotation_net")
     if model_module is not None:
         done += [f"{getattr(model_module, '__name__', 'model')}.{n}" for n in patch_functions(model_module)]

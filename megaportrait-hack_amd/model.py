@@ -1076,6 +1076,7 @@ class BasicBlockFused(_FusedBlock2D):
     _EXPECTED = ("a ResNet BasicBlock (3x3 convs with or without bias, the first at stride 1 or 2, BatchNorm2d with running statistics, "
                  "downsample None or Conv2d 1x1 at that stride + BatchNorm2d, no `shortcut`)")
     _EVAL_ONLY = True
+    split_small_maps = False   # set: the stride-1 launches pass splits="auto" (the split-K form where ops.conv2d_splits recommends it)
 
     def __init__(self, inplanes: int, planes: int, stride: int = 1):
         super().__init__()
@@ -1150,14 +1151,15 @@ class BasicBlockFused(_FusedBlock2D):
         p1, p2, ps = packs
         xc = _f32(x).contiguous()   # (the kernels read NCHW: a channels_last map is copied once)
         s2 = self._stride() == 2
-        y1 = (ops.conv2d_s2 if s2 else ops.conv2d)(xc, p1, relu=True, want_range=True)
+        split = {"splits": "auto"} if self.split_small_maps else {}   # (stride 1 only: there is no split form of the stride-2 kernel)
+        y1 = ops.conv2d_s2(xc, p1, relu=True, want_range=True) if s2 else ops.conv2d(xc, p1, relu=True, want_range=True, **split)
         idt = xc
         if ps is not None:
             xr = ops.current_range(xc)   # (of the whole map: a valid bound of its sub-sample)
             xs = xc[:, :, ::2, ::2].contiguous() if s2 else xc
             n, c, h, w = xs.shape
             idt = ops.conv3d(xs.reshape(n, c, 1, h, w), ps, x_range=xr).reshape(n, ps.co, h, w)
-        return ops.conv2d(y1, p2, residual=idt, relu=True, want_range=True)
+        return ops.conv2d(y1, p2, residual=idt, relu=True, want_range=True, **split)
 
 
 def _swap_slot(cls, cur, enable: bool, half_precision: bool):
@@ -1214,13 +1216,26 @@ def native_g2d_body(g2d: nn.Module, enable: bool = True, half_precision: bool = 
     return changed
 
 
-def native_emtn_resnets(emtn: nn.Module, enable: bool = True) -> bool:
+def _set_split(block, on: bool) -> bool:
+    """`split_small_maps` of a BasicBlockFused / RepVGGBlockFused -> whether it changed (off: the class's default, no instance attribute)."""
+    if bool(block.split_small_maps) == on:
+        return False
+    if on:
+        block.split_small_maps = True
+    else:
+        block.__dict__.pop("split_small_maps", None)
+    return True
+
+
+def native_emtn_resnets(emtn: nn.Module, enable: bool = True, split_small_maps: bool = False) -> bool:
     """Swaps every matching BasicBlock in every nn.Sequential stage of `emtn.head_pose_net` and `emtn.expression_net` (this package's Emtn
     or the reference's, model.py:869-907; the stages are found by type: `layer1..4` in the first, positional children in the second)
     for a BasicBlockFused over the same children, or puts the very objects it replaced back.  Returns whether anything changed.  Off by
     default everywhere; opt-in, inference only.  What stays on PyTorch: each net's 3->64 stem conv + BatchNorm + ReLU + max-pool (Ci = 3
     does not fit the kernel; native_emtn_stems fuses it on its own), the pools and the `fc`s.  The third net, the 6DRepNet
-    `rotation_net` (not an nn.Module of Gbase), has a switch of its own: native_rotation_net."""
+    `rotation_net` (not an nn.Module of Gbase), has a switch of its own: native_rotation_net.
+    split_small_maps (off by default): the fused blocks' stride-1 convs ask ops.conv2d_splits for a split-K launch
+    (csrc/conv2d_splitk_f16x3.hip); without the keyword every fused block is back on the unsplit kernels."""
     changed = False
     for net in (getattr(emtn, "head_pose_net", None), getattr(emtn, "expression_net", None)):
         if not isinstance(net, nn.Module):
@@ -1232,6 +1247,8 @@ def native_emtn_resnets(emtn: nn.Module, enable: bool = True) -> bool:
                 new, did = _swap_slot(BasicBlockFused, stage[i], enable, False)
                 if new is not stage[i]:
                     stage[i] = new
+                if isinstance(new, BasicBlockFused):
+                    did |= _set_split(new, bool(enable and split_small_maps))
                 changed |= did
     return changed
 
@@ -1423,6 +1440,7 @@ class RepVGGBlockFused(_FusedBlock2D):
                  "Identity and `nonlinearity` a ReLU where present; no `rbr_dense`; in_channels % 16 == 0)")
     _EVAL_ONLY = True
     _CUDA_FLOAT_INPUT = True
+    split_small_maps = False   # set: the stride-1 launches pass splits="auto" (the split-K form where ops.conv2d_splits recommends it)
 
     def __init__(self, in_channels: int, out_channels: int, stride: int = 1, groups: int = 1):
         super().__init__()
@@ -1485,18 +1503,22 @@ class RepVGGBlockFused(_FusedBlock2D):
         xc = _f32(x).contiguous()   # (the kernels read NCHW: a channels_last map is copied once)
         if self.rbr_reparam.stride == (2, 2):
             return ops.conv2d_s2(xc, pack, relu=True, want_range=True)
+        split = {"splits": "auto"} if self.split_small_maps else {}
         if pack.groups == 1:
-            return ops.conv2d(xc, pack, relu=True, want_range=True)
-        return ops.conv2d_grouped(xc, pack, relu=True, want_range=True)
+            return ops.conv2d(xc, pack, relu=True, want_range=True, **split)
+        return ops.conv2d_grouped(xc, pack, relu=True, want_range=True, **split)
 
 
-def native_rotation_net(target, enable: bool = True) -> bool:
+def native_rotation_net(target, enable: bool = True, split_small_maps: bool = False) -> bool:
     """Swaps every matching deploy-form RepVGG block of the 6DRepNet backbone — `layer0` and the nn.Sequential stages `layer1..layer4` —
     for a RepVGGBlockFused over the same children, or puts the very objects it replaced back.  `target` is an Emtn (its `rotation_net`
     is looked up), a detector object with a `.model` (encoders2d.SixDRepNet_Detector, the reference's) or the backbone module itself.
     Returns whether anything changed.  Off by default everywhere; opt-in, inference only.  With RepVGG-B1g2 the 27 blocks of
     `layer1..layer4` are swapped; what stays on PyTorch: `layer0` (3 -> 64 at stride 2: Ci = 3 fits neither f16x3 kernel, so the block does not
-    match and is left as it is), the global average pool, `linear_reg` and the Gram-Schmidt step."""
+    match and is left as it is), the global average pool, `linear_reg` and the Gram-Schmidt step.
+    split_small_maps (off by default): the fused blocks' stride-1 plain and grouped convs ask ops.conv2d_splits for a split-K launch
+    (csrc/conv2d_splitk_f16x3.hip); without the keyword every fused block is back on the unsplit kernels."""
+    split = bool(enable and split_small_maps)
     net = getattr(target, "rotation_net", target)   # Emtn -> detector
     if not hasattr(net, "layer1"):
         net = getattr(net, "model", net)            # detector -> backbone
@@ -1507,6 +1529,8 @@ def native_rotation_net(target, enable: bool = True) -> bool:
         new, changed = _swap_slot(RepVGGBlockFused, net.layer0, enable, False)
         if new is not net.layer0:
             net.layer0 = new
+        if isinstance(new, RepVGGBlockFused):
+            changed |= _set_split(new, split)
     for name in ("layer1", "layer2", "layer3", "layer4"):
         stage = getattr(net, name, None)
         if not isinstance(stage, nn.Sequential):
@@ -1515,6 +1539,8 @@ def native_rotation_net(target, enable: bool = True) -> bool:
             new, did = _swap_slot(RepVGGBlockFused, stage[i], enable, False)
             if new is not stage[i]:
                 stage[i] = new
+            if isinstance(new, RepVGGBlockFused):
+                did |= _set_split(new, split)
             changed |= did
     return changed
 

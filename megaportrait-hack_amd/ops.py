@@ -9,7 +9,7 @@ also take fp16 / bf16.
 from __future__ import annotations
 
 import ctypes
-from typing import Optional, Tuple
+from typing import Optional, Tuple, Union
 
 import os as _os
 
@@ -1256,16 +1256,53 @@ def conv2d_typed_supported(two_source: bool, x_dtype: torch.dtype, residual_dtyp
                                                          dtype_code(y_dtype), int(products)))
 
 
+def conv2d_split_supported(n: int, ci: int, co: int, h: int, w: int, groups: int, splits: int) -> bool:
+    """Does the split-K form take this shape with the reduction in `splits` K ranges (mphip_conv2d_split_supported: the rule of
+    ops.conv2d_grouped, 1 <= splits <= 16, and splits divides the (ci / groups) / 16 chunks)?"""
+    return bool(_lib.load().mphip_conv2d_split_supported(int(n), int(ci), int(co), int(h), int(w), int(groups), int(splits)))
+
+
+def conv2d_splits(n: int, ci: int, co: int, h: int, w: int, groups: int = 1) -> int:
+    """The library's recommendation for splits= of ops.conv2d / ops.conv2d_grouped on this shape (mphip_conv2d_splits); 1: do not split."""
+    return int(_lib.load().mphip_conv2d_splits(int(n), int(ci), int(co), int(h), int(w), int(groups)))
+
+
+def _conv2d_splits(who: str, splits, typed: bool, shape, groups: int) -> int:
+    """The `splits` keyword of ops.conv2d / ops.conv2d_grouped -> the count to launch with; 1: today's entry."""
+    if splits is None:
+        return 1
+    if isinstance(splits, str):
+        if splits != "auto":
+            raise RuntimeError(f"{who}: splits = {splits!r} (None, an int or \"auto\")")
+        if typed:
+            raise RuntimeError(f"{who}: splits = \"auto\" with a typed map, out_dtype or products: the split-K form is fp32 with three products")
+        return conv2d_splits(*shape, groups)
+    if isinstance(splits, bool) or not isinstance(splits, int):
+        raise RuntimeError(f"{who}: splits = {splits!r} (None, an int or \"auto\")")
+    if splits == 1:
+        return 1
+    if typed:
+        raise RuntimeError(f"{who}: splits = {splits} with a typed map, out_dtype or products: the split-K form is fp32 with three products")
+    if not conv2d_split_supported(*shape, groups, splits):
+        raise RuntimeError(f"{who}: splits = {splits} does not fit N={shape[0]} Ci={shape[1]} Co={shape[2]} H={shape[3]} W={shape[4]} "
+                           f"groups={groups} (2 .. 16, a divisor of the (Ci / groups) / 16 chunks; there is no fallback)")
+    return splits
+
+
 def conv2d(x: torch.Tensor, pack: PackedConv2d, residual: Optional[torch.Tensor] = None, relu: bool = False,
            x_range: Optional[torch.Tensor] = None, want_range: bool = False, out_dtype: Optional[torch.dtype] = None,
-           products: Optional[int] = None) -> torch.Tensor:
+           products: Optional[int] = None, splits: Union[None, int, str] = None) -> torch.Tensor:
     """y = act(conv3x3(x) + bias (+ residual)) on NCHW fp32, padding 1 (mphip_conv2d_fwd): the f16x3 arithmetic, fp32-class accuracy.
     x_range: the input's range descriptor; without one the descriptor its producer tagged on x is used, else the library scans x.
     want_range: y comes back tagged with the descriptor of its exact max|y| (ops.tensor_range(y)), which the next conv2d picks up.
     out_dtype / products (mphip_conv2d_fwd_typed): x may be fp16 / bf16 (widened on load), y is written in out_dtype (default fp32; the
     fp32 value rounded once, the descriptor then is that of the rounded values), the residual is fp32 or in out_dtype.  products: 3 (the
     default), 1 = one f16 product per multiply (the autocast arithmetic), 0 = follow ops.half_products.  With neither keyword and an fp32
-    x this is the fp32 entry, whatever the policy flag says.  Not every combination is built (conv2d_typed_supported)."""
+    x this is the fp32 entry, whatever the policy flag says.  Not every combination is built (conv2d_typed_supported).
+    splits: None or 1 is that path, bit for bit.  An int above 1 runs the reduction in that many K ranges (mphip_conv2d_split_fwd,
+    csrc/conv2d_splitk_f16x3.hip: partial maps and a finish launch, reproducible bits that differ from the unsplit launch's in the last
+    place); "auto" takes ops.conv2d_splits' recommendation.  fp32 maps and three products only: with a typed map, out_dtype or products
+    it is a RuntimeError."""
     typed = _conv2d_typed(out_dtype, products, x)
     x = _req_typed(x, "x") if typed else _req(x, "x")
     if x.dim() != 4 or x.shape[1] != pack.ci:
@@ -1274,17 +1311,24 @@ def conv2d(x: torch.Tensor, pack: PackedConv2d, residual: Optional[torch.Tensor]
     if not _lib.load().mphip_conv2d_supported(n, ci, pack.co, h, w):
         raise RuntimeError(f"conv2d: unsupported shape N={n} Ci={ci} Co={pack.co} H={h} W={w} (there is no fallback)")
     xr = x_range if x_range is not None else current_range(x)   # None: the library scans x
-    return _conv2d_launch("conv2d", typed, pack, x, None, xr, False, None, None, None, False, residual, relu, want_range, out_dtype, products)
+    ns = _conv2d_splits("conv2d", splits, typed, (n, ci, pack.co, h, w), 1)
+    return _conv2d_launch("conv2d", typed, pack, x, None, xr, False, None, None, None, False, residual, relu, want_range, out_dtype, products,
+                          ns)
 
 
-def _conv2d_launch(who, typed, pack, x1, aff1, r1, relu1, x2, aff2, r2, relu2, residual, relu, want_range, out_dtype, products):
+def _conv2d_launch(who, typed, pack, x1, aff1, r1, relu1, x2, aff2, r2, relu2, residual, relu, want_range, out_dtype, products, splits=1):
     """What ops.conv2d (who = "conv2d": the plain kernels), ops.conv2d_cat, ops.conv2d_s2 (the stride-2 kernel: y and residual on the
     halved map), ops.conv2d_up2 (y and residual on the doubled map), ops.conv2d_resup2 (the residual on the halved map) and
     ops.conv2d_grouped (the entry takes the pack's group count after W) share once
     their sources are checked and the descriptors r1 / r2 chosen: the residual check, the workspace, y and out_range, and the call of
-    the fp32 or (`typed`) the typed entry."""
+    the fp32 or (`typed`) the typed entry.  splits > 1 (ops.conv2d, ops.conv2d_grouped): the split-K entry, which takes the group count
+    and the split count after W and always a workspace."""
     cat = who == "conv2d_cat"
     grp = (pack.groups,) if who == "conv2d_grouped" else ()
+    if splits > 1:   # (the pack's group check below reads `grp`: the entry is chosen after it)
+        entry_who, grp_args = "conv2d_split", (pack.groups, splits)
+    else:
+        entry_who, grp_args = who, grp
     if pack.groups != 1 and not grp:   # (its slabs hold Ci / groups channels: any other kernel would read past them)
         raise RuntimeError(f"{who}: the pack is that of a grouped conv (groups = {pack.groups}): only ops.conv2d_grouped takes it")
     lib = _lib.load()
@@ -1297,10 +1341,10 @@ def _conv2d_launch(who, typed, pack, x1, aff1, r1, relu1, x2, aff2, r2, relu2, r
         if tuple(residual.shape) != rshape:
             raise RuntimeError(f"{who}: residual {tuple(residual.shape)} does not match {rshape}, the output{' at half its size' if who == 'conv2d_resup2' else ''}")
     ws_bytes = 0
-    if r1 is None or (x2 is not None and r2 is None):   # a source to scan
-        ws_name = "conv2d" if who == "conv2d_resup2" else who
+    if splits > 1 or r1 is None or (x2 is not None and r2 is None):   # a source to scan, or partial maps
+        ws_name = "conv2d" if who == "conv2d_resup2" else entry_who
         ws_bytes = (lib.mphip_conv2d_cat_workspace_bytes(n, c1, c2, pack.co, h, w) if cat
-                    else getattr(lib, f"mphip_{ws_name}_workspace_bytes")(n, c1, pack.co, h, w, *grp))
+                    else getattr(lib, f"mphip_{ws_name}_workspace_bytes")(n, c1, pack.co, h, w, *grp_args))
     ws = torch.empty((ws_bytes + 3) // 4, dtype=torch.float32, device=x1.device) if ws_bytes else None
     ydt = torch.float32 if out_dtype is None else out_dtype
     y = torch.empty((n, pack.co, ho, wo), dtype=ydt, device=x1.device)
@@ -1313,10 +1357,10 @@ def _conv2d_launch(who, typed, pack, x1, aff1, r1, relu1, x2, aff2, r2, relu2, r
         shape = (n, pack.co, h, w)
     else:
         sources = (_ptr(x1), *xdt, _ptr(r1))
-        shape = (n, c1, pack.co, h, w, *grp)
+        shape = (n, c1, pack.co, h, w, *grp_args)
     args = (*sources, _ptr(pack.packed()), _ptr(pack.bias), _ptr(residual), *rdt, _ptr(y), *ydt, _ptr(out_range), *shape, int(bool(relu)), *np_,
             _ptr(ws), ws_bytes, _stream())
-    entry = f"mphip_{who}_fwd" + ("_typed" if typed else "")
+    entry = f"mphip_{entry_who}_fwd" + ("_typed" if typed else "")
     _lib.check(getattr(lib, entry)(*args), entry)
     return tag_range(y, out_range)
 
@@ -1348,11 +1392,12 @@ def conv2d_grouped_supported(n: int, ci: int, co: int, h: int, w: int, groups: i
 
 
 def conv2d_grouped(x: torch.Tensor, pack: PackedConv2d, residual: Optional[torch.Tensor] = None, relu: bool = False,
-                   x_range: Optional[torch.Tensor] = None, want_range: bool = False) -> torch.Tensor:
+                   x_range: Optional[torch.Tensor] = None, want_range: bool = False, splits: Union[None, int, str] = None) -> torch.Tensor:
     """y = act(conv3x3(x, groups = pack.groups) + bias (+ residual)) on NCHW fp32, stride 1, padding 1 (mphip_conv2d_grouped_fwd): the
     pack is PackedConv2d(weight [Co, Ci / groups, 3, 3], bias, groups).  The f16x3 arithmetic and the descriptors are ops.conv2d's: with
     the same x_range the result is, bit for bit, conv2d on the dense weight with the group blocks on its diagonal and zeros elsewhere;
-    with groups == 1 it is conv2d.  fp32 only."""
+    with groups == 1 it is conv2d.  fp32 only.  splits: as in ops.conv2d (None or 1: this entry, bit for bit; an int above 1 or "auto":
+    the split-K entry with this pack, the K ranges taken from each group's chunks)."""
     x = _req(x, "x")
     if x.dim() != 4 or x.shape[1] != pack.ci:
         raise RuntimeError(f"conv2d_grouped: input {tuple(x.shape)} does not match Ci={pack.ci}")
@@ -1360,7 +1405,9 @@ def conv2d_grouped(x: torch.Tensor, pack: PackedConv2d, residual: Optional[torch
     if not _lib.load().mphip_conv2d_grouped_supported(n, ci, pack.co, h, w, pack.groups):
         raise RuntimeError(f"conv2d_grouped: unsupported shape N={n} Ci={ci} Co={pack.co} H={h} W={w} groups={pack.groups} (there is no fallback)")
     xr = x_range if x_range is not None else current_range(x)   # None: the library scans x
-    return _conv2d_launch("conv2d_grouped", False, pack, x, None, xr, False, None, None, None, False, residual, relu, want_range, None, None)
+    ns = _conv2d_splits("conv2d_grouped", splits, False, (n, ci, pack.co, h, w), pack.groups)
+    return _conv2d_launch("conv2d_grouped", False, pack, x, None, xr, False, None, None, None, False, residual, relu, want_range, None, None,
+                          ns)
 
 
 def conv2d_up2_supported(n: int, ci: int, co: int, h: int, w: int) -> bool:

@@ -64,6 +64,9 @@ def parse(argv=None):
     ap.add_argument("--native-rotation-net", action="store_true",
                     help="with --native-motion-encoder: the 27 RepVGG blocks of the frozen 6DRepNet pose regressor as one matrix-core "
                          "launch each, the grouped ones included (model.native_rotation_net; inference only; off by default)")
+    ap.add_argument("--native-split-small-maps", action="store_true",
+                    help="with --native-motion-encoder: the stride-1 convs of the fused blocks take the split-K launch where the library "
+                         "recommends one for a small map (ops.conv2d_splits; inference only; off by default)")
     ap.add_argument("--fp16", action="store_true",
                     help="run the PyTorch-ROCm 2D modules under torch.autocast(float16) (the reference's policy, train.py:188); "
                          "the HIP hot path stays fp32-class")
@@ -78,6 +81,8 @@ def parse(argv=None):
         ap.error("--native-fuse-stem needs --native-motion-encoder")
     if args.native_rotation_net and not args.native_motion_encoder:
         ap.error("--native-rotation-net needs --native-motion-encoder")
+    if args.native_split_small_maps and not args.native_motion_encoder:
+        ap.error("--native-split-small-maps needs --native-motion-encoder")
     return args
 
 
@@ -196,7 +201,8 @@ def run(job: dict, args, rank: int, world: int) -> List[str]:
         g.native_trunk(**half)
     if args.native_motion_encoder:
         g.native_motion_encoder(**({"fuse_stem": True} if args.native_fuse_stem else {}),
-                                **({"rotation_net": True} if args.native_rotation_net else {}))
+                                **({"rotation_net": True} if args.native_rotation_net else {}),
+                                **({"split_small_maps": True} if args.native_split_small_maps else {}))
     xs = _load_tensor(job["source_tensor"]) if job["source_tensor"] else _load_image(job["source"])
     n = _load_tensor(job["drivers_tensor"]).shape[0] if job["drivers_tensor"] else len(job["drivers"])
     b, e, outputs = shard_plan(job, n, rank, world)

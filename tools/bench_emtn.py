@@ -14,9 +14,16 @@ resnets, off.
 thirteen groups = 2 blocks), same timer and rules: (a) `rotation_net.predict` alone, legs off, on, on, off, and for context the unswapped
 net under torch.autocast(float16); (b) Emtn.forward with everything off, with the ResNets and stems fused, and with the ResNets, the
 stems and the rotation net fused, legs off, resnets+stem, all, all, resnets+stem, off, and the all-off call under autocast(float16).
+--split measures the split-K form of the stride-1 convs instead (csrc/conv2d_splitk_f16x3.hip; the `split_small_maps` switches), same timer
+and rules: (a) per conv: every stride-1 3x3 conv shape of the three nets at this frame size, one launch as the fused blocks issue it (ReLU,
+a descriptor of x given, the output's descriptor wanted), legs S = 1, then every S of 2, 4, 8, 16 that divides the (Ci / groups) / 16
+chunks, then S = 1 again: the spread between the two S = 1 legs is the noise a gain has to beat; (b) Emtn.forward and rotation_net.predict
+with everything off (torch fp32), with today's switches (ResNets, stems, rotation net), with those plus split_small_maps, and for context
+the all-off call under torch.autocast(float16): legs off, on, split, autocast, autocast, split, on, off.
 usage: python tools/bench_emtn.py [--b 1 8] [--warmup 5] [--runs 20] [--out profiles/emtn_timing.json]
        python tools/bench_emtn.py --stem [--b 1 8] [--out profiles/emtn_stem_timing.json]
-       python tools/bench_emtn.py --rotation [--b 1 8] [--out profiles/rotation_net_timing.json]"""
+       python tools/bench_emtn.py --rotation [--b 1 8] [--out profiles/rotation_net_timing.json]
+       python tools/bench_emtn.py --split [--b 1 8] [--out profiles/conv2d_splitk_timing.json]"""
 import argparse, json, os, statistics, subprocess, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -145,6 +152,80 @@ def rotation_timing(a, dev, emtn):
     return out
 
 
+def split_timing(a, dev, emtn):
+    """--split: (a) the per-conv sweep over S, (b) Emtn.forward and rotation_net.predict off / on / on + split_small_maps / autocast."""
+    det = emtn.rotation_net
+    gen = torch.Generator().manual_seed(7)
+    with torch.no_grad():   # (rotation_timing's He initialisation)
+        for m in det.model.modules():
+            if isinstance(m, torch.nn.Conv2d):
+                torch.nn.init.kaiming_normal_(m.weight, mode="fan_in", nonlinearity="relu", generator=gen)
+                m.bias.normal_(0.0, 0.1, generator=gen)
+    det.model.to(dev)
+    hw = a.hw
+    # (Ci, Co, H = W, groups, where): layer1 .. layer4 of the ResNet-18s (after the stem's max-pool), stages 1 .. 3 of RepVGG-B1g2
+    shapes = [(64, 64, hw // 2, 1, "resnet18.layer1"), (128, 128, hw // 4, 1, "resnet18.layer2, repvgg.layer1"),
+              (128, 128, hw // 4, 2, "repvgg.layer1 (groups 2)"), (256, 256, hw // 8, 1, "resnet18.layer3, repvgg.layer2"),
+              (256, 256, hw // 8, 2, "repvgg.layer2 (groups 2)"), (512, 512, hw // 16, 1, "resnet18.layer4, repvgg.layer3"),
+              (512, 512, hw // 16, 2, "repvgg.layer3 (groups 2)")]
+    out = {"what": "split-K form of the stride-1 2-D 3x3 f16x3 convs (csrc/conv2d_splitk_f16x3.hip) and the split_small_maps switches",
+           "commit": commit(), "device": torch.cuda.get_device_name(0), "torch": torch.__version__, "H": hw, "W": hw, "warmup": a.warmup,
+           "runs": a.runs, "timer": "HIP events around each call after `warmup` calls; median (and minimum) of `runs` calls, ms per call",
+           "cudnn_benchmark": True, "sweep_order": "S = 1, the S > 1 legs in ascending order, S = 1 again",
+           "net_order": ["off", "on", "split", "autocast", "autocast", "split", "on", "off"],
+           "net_modes": {"off": "torch fp32, every switch off", "on": "native_resnets(fuse_stem) + native_rotation_net (predict: the latter)",
+                         "split": "the same with split_small_maps=True", "autocast": "every switch off under torch.autocast(float16)"},
+           "sweep": [], "batches": {}}
+    with torch.no_grad():
+        for b in a.b:
+            for ci, co, h, g, where in shapes:
+                x = torch.randn(b, ci, h, h, device=dev)
+                pack = ops.PackedConv2d(torch.randn(co, ci // g, 3, 3, device=dev) * 0.05, torch.zeros(co, device=dev), g)
+                rng = ops.absmax_range(x)
+                conv = ops.conv2d if g == 1 else ops.conv2d_grouped
+                cands = [s for s in (2, 4, 8, 16) if ops.conv2d_split_supported(b, ci, co, h, h, g, s)]
+                legs = []
+                for s in [1] + cands + [1]:
+                    med, best = median_ms(lambda: conv(x, pack, relu=True, x_range=rng, want_range=True, splits=s), a.warmup, a.runs)
+                    legs.append({"S": s, "median_ms": round(med, 4), "min_ms": round(best, 4)})
+                ones = [l["median_ms"] for l in legs if l["S"] == 1]
+                s1, spread = statistics.mean(ones), abs(ones[0] - ones[1])
+                best_leg = min((l for l in legs if l["S"] > 1), key=lambda l: l["median_ms"], default=None)
+                row = {"N": b, "Ci": ci, "Co": co, "H": h, "W": h, "groups": g, "where": where, "legs": legs, "s1_ms": round(s1, 4),
+                       "s1_spread_ms": round(spread, 4), "recommended_S": ops.conv2d_splits(b, ci, co, h, h, g)}
+                if best_leg is not None:
+                    gain = s1 - best_leg["median_ms"]
+                    row.update({"best_S": best_leg["S"], "best_ms": best_leg["median_ms"], "gain_ms": round(gain, 4),
+                                "gain_beats_spread": bool(gain > spread and best_leg["median_ms"] < min(ones))})
+                out["sweep"].append(row)
+                del x, pack
+        mean = lambda legs, mode: round(statistics.mean(l["median_ms"] for l in legs if l["mode"] == mode), 4)
+        for b in a.b:
+            x = torch.rand(b, 3, hw, hw, device=dev) * 2 - 1
+            res = {}
+            for name in ("emtn_forward", "rotation_net_predict"):
+                fn = (lambda: emtn(x)) if name == "emtn_forward" else (lambda: det.predict(x))
+                legs = []
+                for mode in ("off", "on", "split", "autocast", "autocast", "split", "on", "off"):
+                    on, split = mode in ("on", "split"), mode == "split"
+                    if name == "emtn_forward":
+                        emtn.native_resnets(on, fuse_stem=on, split_small_maps=split)
+                    emtn.native_rotation_net(on, split_small_maps=split)
+                    if mode == "autocast":
+                        with torch.autocast(device_type="cuda", dtype=torch.float16):
+                            med, best = median_ms(fn, a.warmup, a.runs)
+                    else:
+                        med, best = median_ms(fn, a.warmup, a.runs)
+                    legs.append({"mode": mode, "median_ms": round(med, 4), "min_ms": round(best, 4)})
+                emtn.native_resnets(False)
+                emtn.native_rotation_net(False)
+                res[name] = {"legs": legs, "off_ms": mean(legs, "off"), "on_ms": mean(legs, "on"), "split_ms": mean(legs, "split"),
+                             "torch_autocast_fp16_ms": mean(legs, "autocast")}
+            out["batches"][str(b)] = res
+            del x
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--b", type=int, nargs="+", default=[1, 8])
@@ -154,6 +235,7 @@ def main():
     ap.add_argument("--out")
     ap.add_argument("--stem", action="store_true", help="measure the fused stem (model.StemFused) instead; see the module docstring")
     ap.add_argument("--rotation", action="store_true", help="measure the 6DRepNet switch (model.native_rotation_net) instead; see the module docstring")
+    ap.add_argument("--split", action="store_true", help="measure the split-K convs and the split_small_maps switches instead; see the module docstring")
     a = ap.parse_args()
     if a.runs < 20:
         ap.error("--runs: the median of at least 20 runs is reported")
@@ -161,8 +243,8 @@ def main():
     torch.manual_seed(20241018)
     torch.backends.cudnn.benchmark = True
     emtn = E.Emtn().to(dev).eval()
-    if a.stem or a.rotation:
-        out = rotation_timing(a, dev, emtn) if a.rotation else stem_timing(a, dev, emtn)
+    if a.stem or a.rotation or a.split:
+        out = split_timing(a, dev, emtn) if a.split else rotation_timing(a, dev, emtn) if a.rotation else stem_timing(a, dev, emtn)
         print(json.dumps(out))
         if a.out:
             with open(a.out, "w") as f:
