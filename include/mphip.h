@@ -180,6 +180,18 @@ int mphip_conv3d_gn_table_fwd(const float *x, const float *x_range, const void *
                               const float *gamma, const float *beta, const float *w2, const float *b2, float *table, float *table_range,
                               int N, int Ci, int Co, int D, int H, int W, int k, int precision, int gn_groups, float gn_eps,
                               void *workspace, size_t workspace_bytes, void *stream);
+/* The 1x1x1 shortcut conv of a ResBlock3D, launched LAST, finishes its block (reference model.py:510, 519-523 and the nn.AvgPool3d(2) of
+ * 576-580):   out = [avgpool2]( relu?( GroupNorm(y2) * gamma + beta  +  conv1x1x1(x) + bias ) )
+ * y2 [N,Co,D,H,W] = conv2's finished output, stats [N*groups][2] its (mean, rstd); out [N,Co,D,H,W], or [N,Co,D/2,H/2,W/2] with pool2;
+ * out_range (optional) = out's range descriptor.  The shortcut's result is never written: every element is the expression
+ * mphip_conv3d_fwd(k = 1) stores, handed as the residual to the expression mphip_groupnorm_apply evaluates, so out and the scale derived from
+ * out_range are bit-identical to those two calls.  precision 1 only (w_packed: the k = 1 pack; x_range required).  _supported: the shape
+ * takes the k = 1 f16x3 kernel, its grid fits the descriptor's partial maxima, pool2 has even D, H and W % 16 == 0 on a launch with two column
+ * tiles per wave; 0 also under MPHIP_SHORTCUT_FINISH=0.  (Added at ABI 25: no existing signature or layout changed.)                     */
+int mphip_conv3d_k1_gn_res_supported(int N, int Ci, int Co, int D, int H, int W, int groups, int pool2);
+int mphip_conv3d_k1_gn_res_fwd(const float *x, const float *x_range, const void *w_packed, const float *bias, const float *y2,
+                               const float *stats, const float *gamma, const float *beta, float *out, float *out_range, int N, int Ci,
+                               int Co, int D, int H, int W, int groups, int relu, int pool2, void *stream);
 /* FlowField's first three residual blocks (reference model.py:369-408 at the fixed levels of model.py:439-471) in two launches per block:
  *   y = upsample_nearest(relu?(AGN(conv3x3x3(x) + b) [+ conv1x1x1(res_x) + res_b]))      AGN: GroupNorm(groups) * gamma + beta, then * w2 + b2
  * One workgroup owns a whole (frame, GroupNorm group): full input-channel loop, statistics, both affines, residual conv, ReLU and the

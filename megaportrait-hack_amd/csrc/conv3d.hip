@@ -17,6 +17,7 @@
 
 #include "mphip_common.h"
 #include "mphip_conv.h"
+#include "mphip_gn.h"
 
 namespace mphip {
 
@@ -948,6 +949,27 @@ extern "C" int mphip_conv3d_gn_table_fwd(const float *x, const float *x_range, c
     t.gamma = gamma; t.beta = beta; t.w2 = w2; t.b2 = b2; t.table = table; t.range = table_range;
     return conv3d_run(x, nullptr, 0, x_range, w_packed, bias, y, gn_stats, gn_groups, gn_eps, false, N, Ci, Co, D, H, W, k, precision, workspace,
                       workspace_bytes, stream, nullptr, 0, 0, &t);
+}
+
+// The k = 1 shortcut conv that finishes its ResBlock3D (conv3d_k1_f16x3_kernel's FIN modes): out = [pool2](relu?(GN(y2) + conv(x)))
+extern "C" int mphip_conv3d_k1_gn_res_supported(int N, int Ci, int Co, int D, int H, int W, int groups, int pool2) {
+    if (N <= 0 || Ci <= 0 || Co <= 0 || D <= 0 || H <= 0 || W <= 0) return 0;
+    return f16x3_k1_finish_supported(f16x3_switches(), N, Ci, Co, D, H, W, groups, pool2) ? 1 : 0;
+}
+
+extern "C" int mphip_conv3d_k1_gn_res_fwd(const float *x, const float *x_range, const void *w_packed, const float *bias, const float *y2,
+                                          const float *stats, const float *gamma, const float *beta, float *out, float *out_range, int N,
+                                          int Ci, int Co, int D, int H, int W, int groups, int relu, int pool2, void *stream) {
+    MPHIP_REQUIRE(x && x_range && w_packed && y2 && stats && gamma && beta && out, "conv3d_k1_gn_res_fwd: null pointer");
+    MPHIP_REQUIRE(N > 0 && Ci > 0 && Co > 0 && D > 0 && H > 0 && W > 0, "conv3d_k1_gn_res_fwd: bad dims");
+    MPHIP_REQUIRE(groups > 0 && Co % groups == 0, "conv3d_k1_gn_res_fwd: Co=%d not divisible into %d groups", Co, groups);
+    const F16x3Switches sw = f16x3_switches();
+    MPHIP_REQUIRE(f16x3_k1_finish_supported(sw, N, Ci, Co, D, H, W, groups, pool2),
+                  "conv3d_k1_gn_res_fwd: shape not fused (query mphip_conv3d_k1_gn_res_supported; run mphip_conv3d_fwd + mphip_groupnorm_apply)");
+    GnParams fin{};
+    fin.x = y2; fin.stats = stats; fin.gamma = gamma; fin.beta = beta; fin.y = out; fin.range = out_range;
+    fin.C = Co; fin.cpg = Co / groups; fin.relu = relu;
+    return f16x3_launch_k1_finish(sw, x, w_packed, bias, N, Ci, Co, D, H, W, x_range, fin, pool2, (hipStream_t)stream);
 }
 
 extern "C" int mphip_conv3d_gnin_fwd(const float *x, const float *in_affine, const float *x_range, int in_relu, const void *w_packed,

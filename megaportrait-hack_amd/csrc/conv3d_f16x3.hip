@@ -27,6 +27,7 @@
 #include "mphip_common.h"
 #include "mphip_conv.h"
 #include "mphip_f16x3.h"
+#include "mphip_gn.h"
 
 namespace mphip {
 
@@ -781,26 +782,113 @@ __global__ void __launch_bounds__(256) f16x3_pack_k1_kernel(const float *__restr
 // (contiguous ranges), then fold their accumulators through LDS in wave order — the small launches (<= one wave per SIMD on the
 // chip) were a serial chain of nchunks dependent global-load round trips (12-48 x ~1.2 us: 28-41 us for 1-2 GFLOP).
 // Either way the loads of chunk c+1 are issued before the MFMAs of chunk c (two register sets).
-template <int KS, int NTT = 2>
+//
+// FIN (the shortcut of a ResBlock3D, launched LAST): the epilogue finishes the block instead of storing the conv.  With res the value the
+// plain epilogue stores, it loads y2 = conv2's output at the same index and the (mean, rstd) of the element's (sample, group), forms
+// gn_value(y2, ..., residual = res) — gn_apply_kernel's expression, mphip_gn.h — stores that, and leaves out's range descriptor (one partial
+// maximum per workgroup).  The tensor `identity` is never written.  FIN = 2 also does the AvgPool3d(2) that follows the block: the wave
+// tile is a 2(d) x 2(h) x 16(w) brick instead of 64 consecutive voxels (column tile t = the plane, lane bit 4 the row, lane bits 0-3 the
+// column: only the per-lane voxel offset of the x and y2 loads changes), so the eight values of a 2x2x2 cell sit in one lane's two column
+// tiles and in its partners lane ^ 1, ^ 16, ^ 17; the lane of the cell's first voxel adds them in gn_apply_pool_kernel's order and stores.
+// The epilogue runs at this kernel's two waves per SIMD, and out may alias y2 as far as the compiler knows (no load moves above a store):
+// the y2 values of a row tile are loaded as one batch, the next row tile's before the current one's stores, and the per-channel parameters
+// (mean, rstd of the wave's sample; gamma, beta, bias) wait in LDS from before the channel loop.
+struct K1Channel {
+    float mean, rstd, g, b;
+};
+template <int FIN, int NT>
+__device__ __forceinline__ unsigned k1_finish(const GnParams &fin, const float (&yv)[NT], const float (&res)[NT], const K1Channel &ch, bool live,
+                                              size_t plane, int DHW, int rl, int tfloats, bool owner, int pool_off) {
+    float v[NT];
+#pragma unroll
+    for (int t = 0; t < NT; ++t) v[t] = gn_value(fin, yv[t], ch.mean, ch.rstd, ch.g, ch.b, 1.0f, 0.0f, false, res[t], true);
+    unsigned mbits = 0;
+    if (FIN == 2) {
+        float s = 0.0f;   // (d outer, then h, then w; / 8 at the end: gn_apply_pool_kernel's sum)
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+            const float w1 = __shfl_xor(v[t], 1, 64), h1 = __shfl_xor(v[t], 16, 64), h1w1 = __shfl_xor(v[t], 17, 64);
+            s += v[t];
+            s += w1;
+            s += h1;
+            s += h1w1;
+        }
+        if (owner) {   // (the other lanes' sums are not a cell's)
+            if (live) fin.y[plane * (DHW / 8) + pool_off] = s / 8.0f;
+            mbits = range_bits(s / 8.0f);
+        }
+    } else {
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+            if (live) fin.y[plane * DHW + rl + t * tfloats] = v[t];
+            mbits = max(mbits, range_bits(v[t]));
+        }
+    }
+    return mbits;
+}
+
+template <int KS, int NTT = 2, int FIN = 0>
 __global__ void __launch_bounds__(KS == 1 ? 256 : 64 * KS) __attribute__((amdgpu_waves_per_eu(2)))
 conv3d_k1_f16x3_kernel(const float *__restrict__ x, const _Float16 *__restrict__ wslabs, const float *__restrict__ whdr,
                        const float *__restrict__ bias, float *__restrict__ y, int N, int Ci, int Co, int DHW, unsigned x_bytes,
-                       const float *__restrict__ x_range) {
+                       const float *__restrict__ x_range, GnParams fin, int H, int W) {
     constexpr int MT = 3, NT = NTT;   // NT: 32-voxel column tiles per wave
+    fin.tanh_ = 0;   // (known here: gn_value's tanh branch is not compiled into the epilogue)
+    static_assert(FIN != 2 || NTT == 2, "the pooled epilogue pairs the two column tiles of a wave");
     float x_scale = X_SCALE, x_unscale = 1.0f / X_SCALE;
     if (x_range) range_scale_block(x_range, x_scale, x_unscale);
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int j = lane & 31, kg = lane >> 5;
-    const long v0 = (KS == 1 ? (long)blockIdx.x * 4 + wave : (long)blockIdx.x) * (NT * 32);   // this wave's 64 voxels (DHW % 64 == 0: one sample)
-    if (v0 >= (long)N * DHW) return;                                 // wave-uniform (KS > 1: workgroup-uniform)
+    long v0 = (KS == 1 ? (long)blockIdx.x * 4 + wave : (long)blockIdx.x) * (NT * 32);   // this wave's 64 voxels (DHW % 64 == 0: one sample)
+    bool live = true;
+    if (v0 >= (long)N * DHW) {                                       // wave-uniform (KS > 1: workgroup-uniform)
+        if (FIN == 0) return;
+        // FIN: a spare wave of the last workgroup still has range_note_block's barrier to reach — it runs tile 0 again with its stores off
+        live = false;
+        v0 = 0;
+    }
     const int n = (int)(v0 / DHW), r0 = (int)(v0 - (long)n * DHW);
+    // rl: this lane's voxel of column tile 0 inside the sample; the voxel of column tile t is tfloats * t further on
+    int rl = r0 + j, tfloats = 32, pool_off = 0;
+    if (FIN == 2) {
+        const int bw = W / 16, bh = H / 2, brick = r0 / 64;
+        const int wq = brick % bw, hq = (brick / bw) % bh, dq = brick / (bw * bh);
+        rl = ((2 * dq) * H + 2 * hq + (j >> 4)) * W + wq * 16 + (j & 15);
+        tfloats = H * W;
+        pool_off = (dq * bh + hq) * (W / 2) + wq * 8 + ((j & 15) >> 1);
+    }
+    const bool owner = (j & 17) == 0;   // FIN == 2: the lane of a 2x2x2 cell's first voxel
     const int cot = blockIdx.y, nchunks = Ci / F16X3_KC;
     const int cps = (nchunks + KS - 1) / KS;
     const int c_begin = KS == 1 ? 0 : wave * cps, c_end = KS == 1 ? nchunks : min(nchunks, c_begin + cps);
     __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc((void *)x, 0, (int)x_bytes, 0x00020000);
-    const unsigned vbase = (unsigned)((((long)n * Ci + kg * 8) * DHW + r0 + j) * 4);   // (n, ci = kg*8, voxel j of tile 0)
-    const unsigned cstride = (unsigned)DHW * 4u;
+    const unsigned vbase = (unsigned)((((long)n * Ci + kg * 8) * DHW + rl) * 4);   // (n, ci = kg*8, voxel j of tile 0)
+    const unsigned cstride = (unsigned)DHW * 4u, tstride = (unsigned)tfloats * 4u;
     const _Float16 *wl = wslabs + (size_t)cot * nchunks * K1_SLAB_HALFS + (kg * F16X3_COT + j) * 8;
+    const int co0 = cot * F16X3_COT;
+    // FIN: [wave (KS > 1: one)][channel](mean, rstd) of the tile's sample, then [channel] gamma, beta, bias
+    constexpr int FIN_TILES = KS == 1 ? 4 : 1;
+    __shared__ float fin_prm[FIN ? (FIN_TILES * 2 + 3) * F16X3_COT : 1];
+    if (FIN) {
+        if (KS == 1 || wave == 0) {
+            float *mr = fin_prm + (KS == 1 ? wave : 0) * 2 * F16X3_COT;
+            for (int c = lane; c < F16X3_COT; c += 64) {
+                const int grp = n * (fin.C / fin.cpg) + (co0 + c) / fin.cpg;
+                mr[2 * c] = fin.stats[grp * 2];
+                mr[2 * c + 1] = fin.stats[grp * 2 + 1];
+            }
+        }
+        float *gb = fin_prm + FIN_TILES * 2 * F16X3_COT;
+        for (int c = threadIdx.x; c < F16X3_COT; c += blockDim.x) {
+            gb[c] = fin.gamma[co0 + c];
+            gb[F16X3_COT + c] = fin.beta[co0 + c];
+            gb[2 * F16X3_COT + c] = bias ? bias[co0 + c] : 0.0f;
+        }
+        __syncthreads();   // (every wave is here: no FIN wave has returned)
+    }
+    const float *fin_mr = fin_prm + (KS == 1 ? wave : 0) * 2 * F16X3_COT, *fin_gb = fin_prm + FIN_TILES * 2 * F16X3_COT;
+    const size_t plane0 = (size_t)n * Co + co0;   // FIN: channel c of the tile is plane0 + c of y2 and out
+#define K1_CHANNEL(c_) K1Channel{fin_mr[2 * (c_)], fin_mr[2 * (c_) + 1], fin_gb[c_], fin_gb[F16X3_COT + (c_)]}
 
     f32x16 acc[MT][NT];
 #pragma unroll
@@ -818,7 +906,7 @@ conv3d_k1_f16x3_kernel(const float *__restrict__ x, const _Float16 *__restrict__
         const unsigned soff_ = (unsigned)((long)(c_) * F16X3_KC * DHW * 4);                                           \
         _Pragma("unroll") for (int t = 0; t < NT; ++t)                                                                \
             _Pragma("unroll") for (int e = 0; e < 8; ++e)                                                             \
-                xv[set][t][e] = buf_load_f(rsrc, vbase + (unsigned)t * 128u + (unsigned)e * cstride, soff_);          \
+                xv[set][t][e] = buf_load_f(rsrc, vbase + (unsigned)t * tstride + (unsigned)e * cstride, soff_);              \
         const _Float16 *ws_ = wl + (size_t)(c_) * K1_SLAB_HALFS;                                                      \
         _Pragma("unroll") for (int m = 0; m < MT; ++m) {                                                              \
             ah[set][m] = *reinterpret_cast<const half8 *>(ws_ + m * 32 * 8);                                          \
@@ -859,8 +947,29 @@ conv3d_k1_f16x3_kernel(const float *__restrict__ x, const _Float16 *__restrict__
 #undef K1_LOAD
 #undef K1_MFMA
     const float unscale = whdr[0] * x_unscale;
-    const int co0 = cot * F16X3_COT;
-    if (KS == 1) {
+    unsigned mbits = 0;   // FIN: this thread's max|out|
+    if (KS == 1 && FIN) {
+        float yv[2][16][NT];   // y2 of row tile m in yv[m & 1]
+#define K1_Y2(m_)                                                                                                      \
+    _Pragma("unroll") for (int reg = 0; reg < 16; ++reg)                                                               \
+        _Pragma("unroll") for (int t = 0; t < NT; ++t)                                                                 \
+            yv[(m_) & 1][reg][t] = fin.x[(plane0 + (m_) * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * kg) * DHW + rl + t * tfloats];
+        K1_Y2(0)
+#pragma unroll
+        for (int m = 0; m < MT; ++m) {
+            if (m + 1 < MT) K1_Y2(m + 1)
+#pragma unroll
+            for (int reg = 0; reg < 16; ++reg) {
+                const int c = m * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * kg;
+                const float bv = fin_gb[2 * F16X3_COT + c];
+                float res[NT];
+#pragma unroll
+                for (int t = 0; t < NT; ++t) res[t] = acc[m][t][reg] * unscale + bv;
+                mbits = max(mbits, k1_finish<FIN, NT>(fin, yv[m & 1][reg], res, K1_CHANNEL(c), live, plane0 + c, DHW, rl, tfloats, owner, pool_off));
+            }
+        }
+#undef K1_Y2
+    } else if (KS == 1) {
 #pragma unroll
         for (int m = 0; m < MT; ++m) {
 #pragma unroll
@@ -878,29 +987,62 @@ conv3d_k1_f16x3_kernel(const float *__restrict__ x, const _Float16 *__restrict__
         __shared__ float red[KS > 1 ? KS : 1][NT * 16 * 64];
 #pragma unroll
         for (int m = 0; m < MT; ++m) {
+            // FIN: wave w finishes registers w, w + KS, ... of BOTH column tiles (a cell's two planes; the fold below hands it the same ones); their
+            // y2 values are requested before the fold's barrier
+            constexpr int NQ = 16 / KS;
+            float yq[NQ][NT];
+            if (FIN) {
+#pragma unroll
+                for (int i = 0; i < NQ; ++i) {
+                    const int reg = wave + i * KS;
+#pragma unroll
+                    for (int t = 0; t < NT; ++t) yq[i][t] = fin.x[(plane0 + m * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * kg) * DHW + rl + t * tfloats];
+                }
+            }
 #pragma unroll
             for (int t = 0; t < NT; ++t)
 #pragma unroll
                 for (int reg = 0; reg < 16; ++reg) red[wave][(t * 16 + reg) * 64 + lane] = acc[m][t][reg];
             __syncthreads();
-            for (int q = wave; q < NT * 16; q += KS) {
-                const int t = q >> 4, reg = q & 15;
-                float sum = red[0][q * 64 + lane];
+            if (FIN) {
 #pragma unroll
-                for (int k = 1; k < KS; ++k) sum += red[k][q * 64 + lane];
-                const int co = co0 + m * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * kg;
-                const float bv = bias ? bias[co] : 0.0f;
-                y[((size_t)n * Co + co) * DHW + r0 + j + t * 32] = sum * unscale + bv;
+                for (int i = 0; i < NQ; ++i) {
+                    const int reg = wave + i * KS;
+                    const int c = m * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * kg;
+                    const float bv = fin_gb[2 * F16X3_COT + c];
+                    float res[NT];
+#pragma unroll
+                    for (int t = 0; t < NT; ++t) {
+                        float sum = red[0][(t * 16 + reg) * 64 + lane];
+#pragma unroll
+                        for (int k = 1; k < KS; ++k) sum += red[k][(t * 16 + reg) * 64 + lane];
+                        res[t] = sum * unscale + bv;
+                    }
+                    mbits = max(mbits, k1_finish<FIN, NT>(fin, yq[i], res, K1_CHANNEL(c), live, plane0 + c, DHW, rl, tfloats, owner, pool_off));
+                }
+            } else {
+                for (int q = wave; q < NT * 16; q += KS) {
+                    const int t = q >> 4, reg = q & 15;
+                    float sum = red[0][q * 64 + lane];
+#pragma unroll
+                    for (int k = 1; k < KS; ++k) sum += red[k][q * 64 + lane];
+                    const int co = co0 + m * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * kg;
+                    const float bv = bias ? bias[co] : 0.0f;
+                    y[((size_t)n * Co + co) * DHW + r0 + j + t * 32] = sum * unscale + bv;
+                }
             }
             __syncthreads();
         }
     }
+    if (FIN && !live) sat_ = 0;   // (tile 0 is counted by its own wave)
     if (__builtin_amdgcn_ballot_w64(sat_ != 0) != 0) {  // never taken in normal operation (non-finite operands)
         unsigned tot = sat_;
 #pragma unroll
         for (int sft = 32; sft >= 1; sft >>= 1) tot += __shfl_xor(tot, sft, 64);
         if (lane == 0) atomicAdd(&g_f16x3_saturated, (unsigned long long)tot);
     }
+#undef K1_CHANNEL
+    if (FIN && fin.range) range_note_block(mbits, fin.range, blockIdx.y * gridDim.x + blockIdx.x, gridDim.x * gridDim.y);   // every thread arrives
 }
 
 // waves sharing a tile (1 = none): small launches split the channel loop 4 or 8 ways
@@ -993,29 +1135,70 @@ int f16x3_pack_many(const PackJob *jobs, PackSel absmax, PackSel k3, PackSel k1,
     return check_launch("pack_conv_weights(f16x3)");
 }
 
-int f16x3_launch_k1(const F16x3Switches &sw, const float *x, const void *wpacked, const float *bias, float *dst, int N, int Ci, int Co,
-                    int DHW, const float *x_range, hipStream_t s) {
+// the launch geometry of a k = 1 conv: waves sharing a tile, column tiles per wave, grid, workgroup size
+struct K1Geometry {
+    int ks;
+    bool nt1;
+    dim3 grid;
+    unsigned block;
+};
+static K1Geometry f16x3_k1_geometry(const F16x3Switches &sw, int N, int Ci, int Co, int DHW) {
+    K1Geometry g;
+    const long waves = (long)N * DHW / 64;
+    g.ks = f16x3_k1_ksplit(sw, N, Ci, Co, DHW);
+    // a launch with ONE wave per SIMD (64-voxel wave tiles) runs 32-voxel tiles on twice the waves (192->96 @8x32x32, B=8: 29 -> 25 us; with two
+    // waves per SIMD already — 96->192 — it is slower, 26 -> 31 us: the weight fragments are re-read per wave)
+    g.nt1 = g.ks == 1 && (sw.k1_nt >= 0 ? sw.k1_nt == 1 : waves * (Co / F16X3_COT) <= 1024);   // (switch: same-box A/B, 1 / 2 forces)
+    // (nt1: 32 voxels per wave, twice the waves of a launch that has one or two per SIMD)
+    g.grid = dim3((unsigned)(g.ks > 1 ? waves : g.nt1 ? (2 * waves + 3) / 4 : (waves + 3) / 4), Co / F16X3_COT);
+    g.block = g.ks > 1 ? 64u * g.ks : 256u;
+    return g;
+}
+
+template <int FIN>
+static void f16x3_launch_k1_mode(const K1Geometry &g, const float *x, const void *wpacked, const float *bias, float *dst, int N, int Ci, int Co,
+                                 int DHW, const float *x_range, const GnParams &fin, int H, int W, hipStream_t s) {
     const float *hdr = (const float *)wpacked;
     const _Float16 *slabs = (const _Float16 *)((const char *)wpacked + 16);
     const unsigned xb = (unsigned)((size_t)N * Ci * DHW * 4);
-    const long waves = (long)N * DHW / 64;
-    const int ks = f16x3_k1_ksplit(sw, N, Ci, Co, DHW);
-    // a launch with ONE wave per SIMD (64-voxel wave tiles) runs 32-voxel tiles on twice the waves (192->96 @8x32x32, B=8: 29 -> 25 us; with two
-    // waves per SIMD already — 96->192 — it is slower, 26 -> 31 us: the weight fragments are re-read per wave)
-    const bool nt1 = ks == 1 && (sw.k1_nt >= 0 ? sw.k1_nt == 1 : waves * (Co / F16X3_COT) <= 1024);   // (switch: same-box A/B, 1 / 2 forces)
-    if (ks == 8)
-        hipLaunchKernelGGL(conv3d_k1_f16x3_kernel<8>, dim3((unsigned)waves, Co / F16X3_COT), dim3(512), 0, s, x, slabs, hdr, bias, dst, N, Ci,
-                           Co, DHW, xb, x_range);
-    else if (ks == 4)
-        hipLaunchKernelGGL(conv3d_k1_f16x3_kernel<4>, dim3((unsigned)waves, Co / F16X3_COT), dim3(256), 0, s, x, slabs, hdr, bias, dst, N, Ci,
-                           Co, DHW, xb, x_range);
-    else if (nt1)   // 32 voxels per wave: twice the waves of a launch that has one or two per SIMD
-        hipLaunchKernelGGL((conv3d_k1_f16x3_kernel<1, 1>), dim3((unsigned)((2 * waves + 3) / 4), Co / F16X3_COT), dim3(256), 0, s, x, slabs, hdr,
-                           bias, dst, N, Ci, Co, DHW, xb, x_range);
-    else
-        hipLaunchKernelGGL(conv3d_k1_f16x3_kernel<1>, dim3((unsigned)((waves + 3) / 4), Co / F16X3_COT), dim3(256), 0, s, x, slabs, hdr, bias,
-                           dst, N, Ci, Co, DHW, xb, x_range);
+    if (g.ks == 8)
+        hipLaunchKernelGGL((conv3d_k1_f16x3_kernel<8, 2, FIN>), g.grid, dim3(g.block), 0, s, x, slabs, hdr, bias, dst, N, Ci, Co, DHW, xb, x_range,
+                           fin, H, W);
+    else if (g.ks == 4)
+        hipLaunchKernelGGL((conv3d_k1_f16x3_kernel<4, 2, FIN>), g.grid, dim3(g.block), 0, s, x, slabs, hdr, bias, dst, N, Ci, Co, DHW, xb, x_range,
+                           fin, H, W);
+    else if (g.nt1) {
+        if constexpr (FIN != 2)   // (the pooled form pairs two column tiles: f16x3_k1_finish_supported refuses it here)
+            hipLaunchKernelGGL((conv3d_k1_f16x3_kernel<1, 1, FIN>), g.grid, dim3(g.block), 0, s, x, slabs, hdr, bias, dst, N, Ci, Co, DHW, xb,
+                               x_range, fin, H, W);
+    } else
+        hipLaunchKernelGGL((conv3d_k1_f16x3_kernel<1, 2, FIN>), g.grid, dim3(g.block), 0, s, x, slabs, hdr, bias, dst, N, Ci, Co, DHW, xb, x_range,
+                           fin, H, W);
+}
+
+int f16x3_launch_k1(const F16x3Switches &sw, const float *x, const void *wpacked, const float *bias, float *dst, int N, int Ci, int Co,
+                    int DHW, const float *x_range, hipStream_t s) {
+    f16x3_launch_k1_mode<0>(f16x3_k1_geometry(sw, N, Ci, Co, DHW), x, wpacked, bias, dst, N, Ci, Co, DHW, x_range, GnParams{}, 0, 0, s);
     return check_launch("conv3d_fwd(f16x3, k=1)");
+}
+
+// Can the k = 1 launch of this shape finish its ResBlock3D (conv3d_k1_f16x3_kernel's FIN modes)?  Its grid is the plain launch's; the
+// output's range descriptor takes one partial maximum per workgroup; the pooled form needs two column tiles per wave and whole bricks.
+bool f16x3_k1_finish_supported(const F16x3Switches &sw, int N, int Ci, int Co, int D, int H, int W, int groups, int pool2) {
+    if (sw.finish_off || !f16x3_supported(sw, N, Ci, Co, D, H, W, 1) || groups <= 0 || Co % groups != 0) return false;
+    const K1Geometry g = f16x3_k1_geometry(sw, N, Ci, Co, D * H * W);
+    if ((size_t)g.grid.x * g.grid.y > RANGE_MAX_PARTS) return false;
+    if (pool2 && (g.nt1 || D % 2 != 0 || H % 2 != 0 || W % 16 != 0)) return false;
+    return true;
+}
+
+// fin: x = conv2's output, y = the block's output (pooled: [N,Co,D/2,H/2,W/2]), range = y's descriptor; residual unused (the accumulators)
+int f16x3_launch_k1_finish(const F16x3Switches &sw, const float *x, const void *wpacked, const float *bias, int N, int Ci, int Co, int D, int H,
+                           int W, const float *x_range, const GnParams &fin, int pool2, hipStream_t s) {
+    const K1Geometry g = f16x3_k1_geometry(sw, N, Ci, Co, D * H * W);
+    if (pool2) f16x3_launch_k1_mode<2>(g, x, wpacked, bias, nullptr, N, Ci, Co, D * H * W, x_range, fin, H, W, s);
+    else f16x3_launch_k1_mode<1>(g, x, wpacked, bias, nullptr, N, Ci, Co, D * H * W, x_range, fin, H, W, s);
+    return check_launch("conv3d_k1_gn_res_fwd(f16x3)");
 }
 
 int f16x3_launch(const F16x3Switches &sw, const F16x3Plan &p, const float *x, const void *wpacked, const float *bias, float *dst, int N, int Ci,

@@ -32,6 +32,7 @@ F16x3Switches f16x3_switches() {
     sw.wino_pp = !pp ? 1 : pp[0] == '0' ? 0 : pp[0] == '2' ? 2 : 1;
     sw.k1_ks = (int)num("MPHIP_F16X3_K1_KS", 0);
     sw.k1_min_voxels = num("MPHIP_F16X3_K1_MIN", 1024);
+    sw.finish_off = zero("MPHIP_SHORTCUT_FINISH");
     return sw;
 }
 

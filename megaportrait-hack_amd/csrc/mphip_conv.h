@@ -51,6 +51,7 @@ struct F16x3Switches {
     int wino_pp;           // per call  MPHIP_WINO_PP: 0 lockstep, 2 big tile (without half products), anything else / unset 1 = role-split
     int k1_ks;             // per call  MPHIP_F16X3_K1_KS=1|4|8: waves sharing a tile of the k = 1 kernel (0 = the rule)
     long k1_min_voxels;    // per call  MPHIP_F16X3_K1_MIN: voxels from which the k = 1 kernel takes a launch (default 1024)
+    bool finish_off;       // per call  MPHIP_SHORTCUT_FINISH=0: the k = 1 shortcut conv does not finish its ResBlock3D (the separate apply pass)
     bool old_splits;       // fixed     MPHIP_F16X3_OLD_SPLITS (set): r02's split-K rule on direct launches
     bool xcd_on;           // fixed     MPHIP_F16X3_XCD=0 clears it: the hardware's round-robin tile placement
     bool wino_nopack;      // fixed     MPHIP_WINOGRAD_PACK=0: packs carry no F(2,3) slabs (so no launch takes those kernels)
@@ -91,6 +92,11 @@ size_t f16x3_packed_bytes(int Co, int Ci);
 size_t f16x3_packed_bytes_k1(int Co, int Ci);
 int f16x3_launch_k1(const F16x3Switches &sw, const float *x, const void *wpacked, const float *bias, float *dst, int N, int Ci, int Co,
                     int DHW, const float *x_range, hipStream_t s);
+// the k = 1 launch that finishes its ResBlock3D: relu(GN(y2) + conv(x)) (+ AvgPool3d(2)) and the range descriptor of the result (mphip_gn.h)
+struct GnParams;
+bool f16x3_k1_finish_supported(const F16x3Switches &sw, int N, int Ci, int Co, int D, int H, int W, int groups, int pool2);
+int f16x3_launch_k1_finish(const F16x3Switches &sw, const float *x, const void *wpacked, const float *bias, int N, int Ci, int Co, int D, int H,
+                           int W, const float *x_range, const GnParams &fin, int pool2, hipStream_t s);
 int f16x3_pack(const float *w_oidhw, void *out, int Co, int Ci, int k, int transposed, const void *header_from, hipStream_t s);
 // Batched re-packing (mphip_pack_table_*): one launch per kernel kind for every weight of a module.  PackJob is the device-side job
 // (the public mphip_pack_job + what the host resolved); PackSel a launch's selection: indices into the job array and the first block

@@ -6,6 +6,7 @@
 
 #include "mphip_common.h"
 #include "mphip_conv.h"
+#include "mphip_gn.h"
 #include "mphip_resample.h"
 
 namespace mphip {
@@ -217,24 +218,6 @@ __global__ void gn_finalize_kernel(const float *__restrict__ x, const double *__
         }
     }
     if (tbl.table && tbl.range) range_note_block(mbits, tbl.range, blockIdx.x, gridDim.x);   // (every thread of the block arrives)
-}
-
-struct GnParams {
-    const float *x, *stats, *gamma, *beta, *w2, *b2, *residual;
-    float *y;
-    int C, cpg;
-    int relu, tanh_;
-    float *range;  // optional: range descriptor of y (zeroed by the launcher; max|y| is folded in — the next conv's f16x3 scale)
-};
-
-__device__ __forceinline__ float gn_value(const GnParams &p, float xv, float mean, float rstd, float g, float b,
-                                          float w2, float b2, bool has2, float res, bool has_res) {
-    float v = (xv - mean) * rstd * g + b;
-    if (has2) v = v * w2 + b2;
-    if (has_res) v += res;
-    if (p.relu) v = fmaxf(v, 0.0f);
-    if (p.tanh_) v = tanhf(v);
-    return v;
 }
 
 // apply, no pooling: one thread per VW contiguous elements of one (n,c) plane.

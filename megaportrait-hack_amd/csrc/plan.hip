@@ -285,14 +285,22 @@ ConvOut conv3d(Ctx &c, T5 &x, ConvW &cw, int gn_groups, const Norm *nm = nullptr
     return o;
 }
 
+// ops.conv3d_split_slabs: the slabs conv3d_split leaves of this conv (1: a finished tensor)
+int conv3d_split_slabs(const Ctx &c, int n, const ConvW &cw, int d, int h, int w) {
+    const int splits = mphip_conv3d_splits(n, cw.ci, cw.co, d, h, w, cw.k, precision_for(c, n, cw.ci, cw.co, d, h, w, cw.k));
+    const size_t elems = (size_t)n * cw.co * d * h * w;
+    if (splits > 1 && (elems > SPLIT_CHAIN_MAX_ELEMS || (splits >= SPLIT_CHAIN_MAX_SPLITS && (size_t)splits * elems > SPLIT_CHAIN_MAX_SLAB_ELEMS)))
+        return 1;   // (reduced by the conv call itself)
+    return splits;
+}
+
 // ops.conv3d_split: split-K slabs are kept for the GroupNorm kernels when the tensor is small
 ConvOut conv3d_split(Ctx &c, T5 &x, ConvW &cw, int gn_groups, const Norm *nm = nullptr, const ConvW *next = nullptr) {
     const int n = x.n, d = x.d, h = x.h, w = x.w;
     const int prec = precision_for(c, n, cw.ci, cw.co, d, h, w, cw.k);
     const int splits = mphip_conv3d_splits(n, cw.ci, cw.co, d, h, w, cw.k, prec);
     const size_t elems = (size_t)n * cw.co * d * h * w;
-    if (splits > 1 && (elems > SPLIT_CHAIN_MAX_ELEMS || (splits >= SPLIT_CHAIN_MAX_SPLITS && (size_t)splits * elems > SPLIT_CHAIN_MAX_SLAB_ELEMS)))
-        return conv3d(c, x, cw, gn_groups, nm, next);
+    if (splits > 1 && conv3d_split_slabs(c, n, cw, d, h, w) == 1) return conv3d(c, x, cw, gn_groups, nm, next);
     if (gn_groups && splits == 1 && prec == 1) return conv3d(c, x, cw, gn_groups, nm, next);
     const void *wp = packed(c, cw, prec);
     const float *xr = prec == 1 ? range_for(c, x) : nullptr;
@@ -573,10 +581,30 @@ void generator_coords(GenLane (&ln)[L], int B, Buf (&coords)[L]) {
     }
 }
 
+// ops.shortcut_finish_ok: will the block's conv shortcut, launched last, finish it (relu(GN2(conv2) + shortcut) and the pool in the k = 1
+// kernel's epilogue)?  It takes conv2's output as a finished tensor.
+bool shortcut_finish_ok(const Ctx &c, const ResBlock &b, const T5 &x, bool pool_after) {
+    if (b.identity || c.p->precision != 1 || !mphip_conv3d_k1_gn_res_supported(x.n, b.shortcut.ci, b.shortcut.co, x.d, x.h, x.w, 32, pool_after)) return false;
+    const bool gn_in = conv3d_split_slabs(c, x.n, b.conv1, x.d, x.h, x.w) == 1 && gn_in_conv_ok(c, x.n, x.d, x.h, x.w, b.conv2);
+    return gn_in || conv3d_split_slabs(c, x.n, b.conv2, x.d, x.h, x.w) == 1;
+}
+
+// ops.conv3d_k1_gn_res: the shortcut conv and the rest of its block in one launch; consumes nothing
+T5 conv3d_k1_gn_res(Ctx &c, T5 &x, ConvW &cw, ConvOut &y2, const Norm &nm, int groups, bool relu, bool pool2) {
+    const int n = x.n, d = x.d, h = x.h, w = x.w;
+    const void *wp = packed(c, cw, 1);
+    const float *xr = range_for(c, x);
+    T5 out = pool2 ? new_t5(c, n, cw.co, d / 2, h / 2, w / 2, true) : new_t5(c, n, cw.co, d, h, w, true);
+    RUN(c, mphip_conv3d_k1_gn_res_fwd(x.data.p, xr, wp, cw.b, y2.t.data.p, y2.stats.p, nm.gw, nm.gb, out.data.p, out.range.p, n, cw.ci, cw.co, d, h, w,
+                                      groups, relu, pool2, c.s));
+    return out;
+}
+
 // ResBlock3D._forward, inference branch (model.py:500-528); consumes x.  `hook`: called right after conv1 was launched.
 template <typename Hook>
 T5 resblock(Ctx &c, ResBlock &b, T5 &x, bool pool_after, Hook hook) {
-    ConvOut identity = b.identity ? as_convout(x) : conv3d_split(c, x, b.shortcut, 0);
+    const bool finish = shortcut_finish_ok(c, b, x, pool_after);   // the shortcut conv goes last and finishes the block
+    ConvOut identity = b.identity ? as_convout(x) : finish ? ConvOut() : conv3d_split(c, x, b.shortcut, 0);
     ConvOut y = conv3d_split(c, x, b.conv1, 32, &b.gn1, &b.conv2);   // (+ gn1's affine table when it will be folded into conv2)
     hook();
     ensure_stats(c, y, 32);
@@ -591,9 +619,10 @@ T5 resblock(Ctx &c, ResBlock &b, T5 &x, bool pool_after, Hook hook) {
         give(c, a);
     }
     ensure_stats(c, y2, 32);
-    T5 out = groupnorm_apply(c, y2, b.gn2, 32, &identity, true, false, pool_after, 1, 1, 1);
+    T5 out = finish ? conv3d_k1_gn_res(c, x, b.shortcut, y2, b.gn2, 32, true, pool_after)
+                    : groupnorm_apply(c, y2, b.gn2, 32, &identity, true, false, pool_after, 1, 1, 1);
     give(c, y2);
-    if (!b.identity) give(c, identity);
+    if (!b.identity && !finish) give(c, identity);
     give(c, x);
     return out;
 }

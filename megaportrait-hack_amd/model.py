@@ -484,12 +484,15 @@ class ResBlock3D(nn.Module):
             if _after_conv1 is not None:
                 _after_conv1()
             return ag.AvgPool2Fn.apply(y) if _pool_after else y
-        identity = x if isinstance(self.shortcut, nn.Identity) else ops.conv3d_split(x, _packs.get(self.shortcut))
+        pc2 = _packs.get(self.conv2)
+        psc = None if isinstance(self.shortcut, nn.Identity) else _packs.get(self.shortcut)
+        # a conv shortcut that can finish the block (GN2, residual add, ReLU, pool in the k = 1 kernel's epilogue) is launched LAST
+        finish = psc is not None and ops.shortcut_finish_ok(x.shape, psc, _packs.get(self.conv1), pc2, _pool_after)
+        identity = x if psc is None else None if finish else ops.conv3d_split(x, psc)
         y = ops.conv3d_split(x, _packs.get(self.conv1), gn_groups=32, gn_eps=self.gn1.eps)  # + GN1's statistics
         if _after_conv1 is not None:
             _after_conv1()
         st = ops.groupnorm_stats(y, 32, self.gn1.eps)
-        pc2 = _packs.get(self.conv2)
         if y.splits == 1 and ops.gn_in_conv_ok(y.shape, pc2):
             # GN1 + ReLU folded into conv2's input staging: the normalised tensor never touches HBM
             y2, st2 = ops.conv3d_gn_in(y.data, st, self.gn1.weight, self.gn1.bias, 32, pc2, out_gn_groups=32,
@@ -499,6 +502,8 @@ class ResBlock3D(nn.Module):
             a = ops.groupnorm_apply(y, st, self.gn1.weight, self.gn1.bias, 32, relu=True)
             y = ops.conv3d_split(a, pc2, gn_groups=32, gn_eps=self.gn2.eps)
         st = ops.groupnorm_stats(y, 32, self.gn2.eps)
+        if finish:
+            return ops.conv3d_k1_gn_res(x, psc, y.data, st, self.gn2.weight, self.gn2.bias, 32, relu=True, pool2=_pool_after)
         return ops.groupnorm_apply(y, st, self.gn2.weight, self.gn2.bias, 32, residual=identity, relu=True,
                                    pool2=_pool_after)
 

@@ -734,8 +734,7 @@ def conv3d_split(x: torch.Tensor, pc: PackedConv, precision: Optional[int] = Non
         prec = 0
     splits = lib.mphip_conv3d_splits(n, ci, pc.co, d, h, w, pc.k, prec)
     shape = (n, pc.co, d, h, w)
-    elems = n * pc.co * d * h * w
-    if splits > 1 and (elems > _SPLIT_CHAIN_MAX_ELEMS or (splits >= _SPLIT_CHAIN_MAX_SPLITS and splits * elems > _SPLIT_CHAIN_MAX_SLAB_ELEMS)):
+    if splits > 1 and conv3d_split_slabs(x.shape, pc, prec) == 1:
         # mid-sized tensors (G3d's inner levels): the dedicated reduce + vectorised GN kernels are faster than the
         # one-thread-per-element split-aware kernels (measured: -13 % end to end when those were used everywhere)
         if gn_groups:
@@ -759,6 +758,20 @@ def conv3d_split(x: torch.Tensor, pc: PackedConv, precision: Optional[int] = Non
     else:
         launch()
     return ConvOut(out, splits, pc.bias if splits > 1 else None, shape)
+
+
+def conv3d_split_slabs(x_shape, pc: PackedConv, precision: Optional[int] = None) -> int:
+    """The slabs conv3d_split leaves of this conv on an input of this shape (1: a finished tensor)."""
+    n, ci, d, h, w = x_shape
+    lib = _lib.load()
+    prec = _default_precision if precision is None else precision
+    if prec != 0 and not lib.mphip_conv3d_supported(n, ci, pc.co, d, h, w, pc.k, prec):
+        prec = 0
+    splits = lib.mphip_conv3d_splits(n, ci, pc.co, d, h, w, pc.k, prec)
+    elems = n * pc.co * d * h * w
+    if splits > 1 and (elems > _SPLIT_CHAIN_MAX_ELEMS or (splits >= _SPLIT_CHAIN_MAX_SPLITS and splits * elems > _SPLIT_CHAIN_MAX_SLAB_ELEMS)):
+        return 1   # (reduced by the conv call itself)
+    return splits
 
 
 _SPLIT_CHAIN_MAX_ELEMS = 1 << 18  # conv outputs up to 1 MB keep their split-K slabs for the GN kernels (FlowField)
@@ -847,6 +860,49 @@ def groupnorm_apply(x, stats, gamma, beta, groups: int, w2=None, b2=None, residu
                                              _ptr(y), _ptr(rng), n, c, d, h, w, groups, int(relu), int(tanh), int(pool2),
                                              _stream()), "mphip_groupnorm_apply")
     return tag_range(y, rng)
+
+
+def conv3d_k1_gn_res_ok(x_shape, pc: PackedConv, groups: int, pool2: bool = False) -> bool:
+    """True when the 1x1x1 conv `pc` on an input of this shape can finish its residual block (conv3d_k1_gn_res): the f16x3 k = 1 kernel
+    takes the launch, its grid fits the result's range descriptor, and a pooled block is made of whole 2x2x16 bricks.  False under
+    MPHIP_SHORTCUT_FINISH=0 (the library reads the switch at every query)."""
+    if _default_precision != 1 or pc.k != 1:
+        return False
+    n, ci, d, h, w = x_shape
+    return bool(_lib.load().mphip_conv3d_k1_gn_res_supported(n, ci, pc.co, d, h, w, groups, int(pool2)))
+
+
+def shortcut_finish_ok(x_shape, shortcut: PackedConv, conv1: PackedConv, conv2: PackedConv, pool2: bool) -> bool:
+    """Will a ResBlock3D's conv shortcut, launched last, finish the block?  It takes conv2's output as a finished tensor."""
+    if not conv3d_k1_gn_res_ok(x_shape, shortcut, 32, pool2):
+        return False
+    mid = (x_shape[0], conv1.co) + tuple(x_shape[2:])
+    return (conv3d_split_slabs(x_shape, conv1) == 1 and gn_in_conv_ok(mid, conv2)) or conv3d_split_slabs(mid, conv2) == 1
+
+
+def conv3d_k1_gn_res(x: torch.Tensor, pc: PackedConv, y2: torch.Tensor, stats: torch.Tensor, gamma, beta, groups: int, relu: bool = True,
+                     pool2: bool = False) -> torch.Tensor:
+    """[avgpool2](relu(GroupNorm(y2) + conv1x1x1(x))) in the k = 1 conv's own launch (mphip_conv3d_k1_gn_res_fwd): the same bits as
+    conv3d(x, pc) followed by groupnorm_apply(y2, ..., residual=that), without the residual tensor.  Ask conv3d_k1_gn_res_ok first."""
+    x, y2 = _req(x, "x"), _req(y2, "y2")
+    n, ci, d, h, w = x.shape
+    if ci != pc.ci or tuple(y2.shape) != (n, pc.co, d, h, w):
+        raise RuntimeError(f"conv3d_k1_gn_res: x {tuple(x.shape)} / y2 {tuple(y2.shape)} do not match the conv {pc.ci} -> {pc.co}")
+    lib = _lib.load()
+    gamma, beta = _req(gamma.detach(), "gamma"), _req(beta.detach(), "beta")
+    wp = pc.packed(1)
+    xr = _range_for(x)
+    out = torch.empty((n, pc.co, d // 2, h // 2, w // 2) if pool2 else (n, pc.co, d, h, w), dtype=torch.float32, device=x.device)
+    rng = new_range(x.device) if _RANGES_ENABLED else None
+
+    def launch():
+        _lib.check(lib.mphip_conv3d_k1_gn_res_fwd(_ptr(x), _ptr(xr), _ptr(wp), _ptr(pc.bias), _ptr(y2), _ptr(stats), _ptr(gamma), _ptr(beta),
+                                                  _ptr(out), _ptr(rng), n, ci, pc.co, d, h, w, groups, int(relu), int(pool2), _stream()),
+                   "mphip_conv3d_k1_gn_res_fwd")
+        return out
+
+    out = _conv_hook(x, pc, launch) if _conv_hook is not None else launch()
+    return tag_range(out, rng)
 
 
 _GN_FUSED_MAX_SPAN = 12288  # floats per (sample, group): LDS cache of the one-launch GroupNorm
