@@ -9,7 +9,7 @@
 // sequence per chunk, epilogue, out_range and saturation counting are conv2d_f16x3.hip's.  A group's sum is that of the dense conv whose
 // [Co, Ci, 3, 3] weight has the group blocks on its diagonal and exact zeros elsewhere, less the chunks that add those zeros: with the
 // same descriptor of x and the same max|w| the launch writes the bits of mphip_conv2d_fwd on that dense weight.
-// fp32 maps, stride 1, one source and three products only.  groups == 1 is the plain kernel's launch (conv2d_run).
+// fp32 maps, stride 1, one source and three products only.  groups == 1 is the plain kernel's launch (conv2d_grouped_launch).
 #include "conv2d_f16x3_tile.h"
 
 namespace mphip {
@@ -39,6 +39,7 @@ bool c2_grouped_supported(int N, int Ci, int Co, int H, int W, int groups) {
 }
 
 void conv2d_grouped_launch(const C2Call &c, const C2Grid &g) {
+    if (c.groups == 1) return conv2d_plain_launch(c, g);
     hipLaunchKernelGGL(conv2d_k3_grp_f16x3_kernel, g.grid, dim3(C2_NTHR), 0, c.stream, (const float *)c.x1, c.x1_range,
                        (const _Float16 *)((const char *)c.w_packed + 16), (const float *)c.w_packed, c.bias, (const float *)c.residual,
                        (float *)c.y, c.out_range, c.C1, c.Co, c.H, c.W, c.relu, g.tiles_w, g.tiles_h, g.nslots, c.C1 / c.groups,
@@ -60,13 +61,8 @@ extern "C" size_t mphip_conv2d_grouped_workspace_bytes(int N, int Ci, int Co, in
 extern "C" int mphip_conv2d_grouped_fwd(const float *x, const float *x_range, const void *w_packed, const float *bias, const float *residual,
                                         float *y, float *out_range, int N, int Ci, int Co, int H, int W, int groups, int relu,
                                         void *workspace, size_t workspace_bytes, void *stream) {
-    C2Call c{};
-    c.who = "conv2d_grouped_fwd";
-    c.groups = groups >= 1 ? groups : -1;   // (0 in a C2Call is the other entries' "not grouped"; here it is a group count nobody has)
-    c.x1 = x, c.x1_range = x_range, c.C1 = Ci;
-    c.x_dtype = c.residual_dtype = c.y_dtype = MPHIP_DTYPE_F32, c.products = 3;
-    c.w_packed = w_packed, c.bias = bias, c.residual = residual, c.y = y, c.out_range = out_range;
-    c.N = N, c.Co = Co, c.H = H, c.W = W, c.relu = relu;
-    c.workspace = workspace, c.workspace_bytes = workspace_bytes, c.stream = (hipStream_t)stream;
+    C2Call c = c2_call_f32("conv2d_grouped_fwd", C2_GROUPED, x, x_range, w_packed, bias, residual, y, out_range, N, Ci, Co, H, W, relu, workspace,
+                           workspace_bytes, stream);
+    c.groups = groups;
     return conv2d_run(c);
 }

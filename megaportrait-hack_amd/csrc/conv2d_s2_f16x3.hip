@@ -233,12 +233,6 @@ extern "C" size_t mphip_conv2d_s2_workspace_bytes(int N, int Ci, int Co, int H, 
 extern "C" int mphip_conv2d_s2_fwd(const float *x, const float *x_range, const void *w_packed, const float *bias, const float *residual,
                                    float *y, float *out_range, int N, int Ci, int Co, int H, int W, int relu, void *workspace,
                                    size_t workspace_bytes, void *stream) {
-    C2Call c{};
-    c.who = "conv2d_s2_fwd", c.stride = 2;
-    c.x1 = x, c.x1_range = x_range, c.C1 = Ci;
-    c.x_dtype = c.residual_dtype = c.y_dtype = MPHIP_DTYPE_F32, c.products = 3;
-    c.w_packed = w_packed, c.bias = bias, c.residual = residual, c.y = y, c.out_range = out_range;
-    c.N = N, c.Co = Co, c.H = H, c.W = W, c.relu = relu;
-    c.workspace = workspace, c.workspace_bytes = workspace_bytes, c.stream = (hipStream_t)stream;
-    return conv2d_run(c);
+    return conv2d_run(c2_call_f32("conv2d_s2_fwd", C2_S2, x, x_range, w_packed, bias, residual, y, out_range, N, Ci, Co, H, W, relu, workspace,
+                                  workspace_bytes, stream));
 }

@@ -15,7 +15,7 @@
 // Contract.  Power-of-two scales commute with fp32 rounding away from underflow and overflow, so with one descriptor of x and one header
 // scale the launch writes  act(((y_0 + y_1) + ... + y_{splits-1}) + bias (+ residual)),  y_z = mphip_conv2d_fwd of K range z with a zero
 // bias, evaluated in fp32 in that order (tests/test_gpu_conv2d_splitk.py).
-// fp32 maps, stride 1, one source, three products.  splits == 1 is the plain or the grouped kernel's launch (conv2d_run).
+// fp32 maps, stride 1, one source, three products.  splits == 1 is the plain or the grouped kernel's launch (conv2d_split_launch).
 #include "conv2d_f16x3_tile.h"
 
 namespace mphip {
@@ -114,8 +114,10 @@ bool c2_split_supported(int N, int Ci, int Co, int H, int W, int groups, int spl
 
 unsigned c2_split_finish_blocks(size_t ny) { return (unsigned)cdiv(ny, (size_t)(C2F_NTHR * C2F_PER)); }
 
-// grid.z = c.splits; part: c.splits maps of N * Co * H * W floats; every range in place, out_range initialised for g.nslots slots
-void conv2d_split_launch(const C2Call &c, const C2Grid &g, float *part) {
+// grid.z = c.splits; g.part: c.splits maps of N * Co * H * W floats; every range in place, out_range initialised for g.nslots slots
+void conv2d_split_launch(const C2Call &c, const C2Grid &g) {
+    if (!g.part) return conv2d_grouped_launch(c, g);   // (c.splits == 1)
+    float *part = g.part;
     const size_t ny = (size_t)c.N * c.Co * c.H * c.W;
     const _Float16 *slabs = (const _Float16 *)((const char *)c.w_packed + 16);
     const dim3 grid(g.grid.x, g.grid.y, (unsigned)c.splits);
@@ -169,14 +171,8 @@ extern "C" size_t mphip_conv2d_split_workspace_bytes(int N, int Ci, int Co, int 
 extern "C" int mphip_conv2d_split_fwd(const float *x, const float *x_range, const void *w_packed, const float *bias, const float *residual,
                                       float *y, float *out_range, int N, int Ci, int Co, int H, int W, int groups, int splits, int relu,
                                       void *workspace, size_t workspace_bytes, void *stream) {
-    C2Call c{};
-    c.who = "conv2d_split_fwd";
-    c.groups = groups >= 1 ? groups : -1;   // (as in mphip_conv2d_grouped_fwd)
-    c.splits = splits >= 1 ? splits : -1;   // (0 in a C2Call is the other entries' "not split")
-    c.x1 = x, c.x1_range = x_range, c.C1 = Ci;
-    c.x_dtype = c.residual_dtype = c.y_dtype = MPHIP_DTYPE_F32, c.products = 3;
-    c.w_packed = w_packed, c.bias = bias, c.residual = residual, c.y = y, c.out_range = out_range;
-    c.N = N, c.Co = Co, c.H = H, c.W = W, c.relu = relu;
-    c.workspace = workspace, c.workspace_bytes = workspace_bytes, c.stream = (hipStream_t)stream;
+    C2Call c = c2_call_f32("conv2d_split_fwd", C2_SPLIT, x, x_range, w_packed, bias, residual, y, out_range, N, Ci, Co, H, W, relu, workspace,
+                           workspace_bytes, stream);
+    c.groups = groups, c.splits = splits;
     return conv2d_run(c);
 }

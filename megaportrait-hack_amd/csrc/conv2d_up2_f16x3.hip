@@ -57,7 +57,7 @@ bool c2_up2_supported(int N, int Ci, int Co, int h, int w) {
 
 void conv2d_up2_launch(const C2Call &c, const C2Grid &g) {
     const _Float16 *slabs = (const _Float16 *)((const char *)c.w_packed + 16);
-    if (c.up2 == 1)   // c.H, c.W: the source map
+    if (c.form == C2_UP2)   // c.H, c.W: the source map
         hipLaunchKernelGGL(conv2d_k3_up2_f16x3_kernel, g.grid, dim3(C2_NTHR), 0, c.stream, (const float *)c.x1, c.x1_range, slabs,
                            (const float *)c.w_packed, c.bias, (const float *)c.residual, (float *)c.y, c.out_range, c.C1, c.Co, 2 * c.H,
                            2 * c.W, c.relu, g.tiles_w, g.tiles_h, g.nslots);
@@ -77,29 +77,16 @@ extern "C" size_t mphip_conv2d_up2_workspace_bytes(int N, int Ci, int Co, int h,
     return c2_up2_supported(N, Ci, Co, h, w) ? c2_workspace_bytes(1) : 0;   // the library-computed descriptor of x (x_range == NULL)
 }
 
-static C2Call up2_call(const char *who, int up2, const float *x, const float *x_range, const void *w_packed, const float *bias,
-                       const float *residual, float *y, float *out_range, int N, int Ci, int Co, int H, int W, int relu, void *workspace,
-                       size_t workspace_bytes, void *stream) {
-    C2Call c{};
-    c.who = who, c.up2 = up2;
-    c.x1 = x, c.x1_range = x_range, c.C1 = Ci;
-    c.x_dtype = c.residual_dtype = c.y_dtype = MPHIP_DTYPE_F32, c.products = 3;
-    c.w_packed = w_packed, c.bias = bias, c.residual = residual, c.y = y, c.out_range = out_range;
-    c.N = N, c.Co = Co, c.H = H, c.W = W, c.relu = relu;
-    c.workspace = workspace, c.workspace_bytes = workspace_bytes, c.stream = (hipStream_t)stream;
-    return c;
-}
-
 extern "C" int mphip_conv2d_up2_fwd(const float *x, const float *x_range, const void *w_packed, const float *bias, const float *residual,
                                     float *y, float *out_range, int N, int Ci, int Co, int h, int w, int relu, void *workspace,
                                     size_t workspace_bytes, void *stream) {
-    return conv2d_run(up2_call("conv2d_up2_fwd", 1, x, x_range, w_packed, bias, residual, y, out_range, N, Ci, Co, h, w, relu, workspace,
-                               workspace_bytes, stream));
+    return conv2d_run(c2_call_f32("conv2d_up2_fwd", C2_UP2, x, x_range, w_packed, bias, residual, y, out_range, N, Ci, Co, h, w, relu, workspace,
+                                  workspace_bytes, stream));
 }
 
 extern "C" int mphip_conv2d_resup2_fwd(const float *x, const float *x_range, const void *w_packed, const float *bias,
                                        const float *residual_lowres, float *y, float *out_range, int N, int Ci, int Co, int H, int W,
                                        int relu, void *workspace, size_t workspace_bytes, void *stream) {
-    return conv2d_run(up2_call("conv2d_resup2_fwd", 2, x, x_range, w_packed, bias, residual_lowres, y, out_range, N, Ci, Co, H, W, relu,
-                               workspace, workspace_bytes, stream));
+    return conv2d_run(c2_call_f32("conv2d_resup2_fwd", C2_RESUP2, x, x_range, w_packed, bias, residual_lowres, y, out_range, N, Ci, Co, H, W,
+                                  relu, workspace, workspace_bytes, stream));
 }

@@ -184,22 +184,26 @@ int conv2d_grp_saturation(unsigned long long *count, int reset);
 // conv2d_splitk_f16x3.hip: the split-K form (mphip_conv2d_split_fwd, splits > 1), likewise
 int conv2d_split_saturation(unsigned long long *count, int reset);
 
-// One call of the 2-D 3x3 conv, as its eight C entries describe it to conv2d_run (conv2d_lp.hip).  Zero-initialised it is the plain fp32
-// form: the plain form is one source (C2 = 0, no tables), the fp32 entries are fp32 dtypes with three products.
+// The forms of the 2-D 3x3 conv: what conv2d_run's table (conv2d_run.hip) is indexed by.  One C entry each, the first two a typed one too.
+enum C2Form {
+    C2_PLAIN,    // one source; x1, residual and y in their dtypes, one product or three
+    C2_CAT,      // the two-source kernels (also with C2 == 0: they are kernels of their own); fp32 sources, typed residual and y
+    C2_S2,       // conv2d_s2_f16x3.hip: stride 2; y and residual are [N,Co,(H+1)/2,(W+1)/2]
+    C2_UP2,      // conv2d_up2_f16x3.hip: the source is up2(x1), x1 and H, W the LOW-resolution map, y and residual [N,Co,2H,2W]
+    C2_RESUP2,   // conv2d_up2_f16x3.hip: the residual is up2(r), r [N,Co,H/2,W/2], H and W even
+    C2_GROUPED,  // conv2d_grp_f16x3.hip: x1 [N,C1,H,W] in `groups` groups, the pack that of a [Co,C1/groups,3,3] weight; 1: the plain kernel
+    C2_SPLIT,    // conv2d_splitk_f16x3.hip: the grouped form with the reduction in `splits` K ranges that leave partial maps in the
+                 // workspace, behind the descriptor slot, and a finish launch; 1: the grouped form's launch
+    C2_FORMS
+};
+// One call of the 2-D 3x3 conv, as its nine C entries describe it to conv2d_run.  Zero-initialised it is the plain fp32 three-product
+// call: one source (C2 = 0, no tables), fp32 dtypes (MPHIP_DTYPE_F32 == 0); only `products` = 0 asks for the thread's policy.  Every
+// form but the first two is one source, fp32 maps and three products (c2_call_f32).
 struct C2Call {
     const char *who;        // the entry's name, for messages
-    int stride;             // 2: the stride-2 kernel (conv2d_s2_f16x3.hip; plain form, fp32 maps, three products; y and residual are
-                            // [N,Co,(H+1)/2,(W+1)/2]); anything else: stride 1
-    int up2;                // conv2d_up2_f16x3.hip (plain form, fp32 maps, three products).  1: the source is up2(x1), x1 and H, W the
-                            // LOW-resolution map, y and residual [N,Co,2H,2W].  2: the residual is up2(r), r [N,Co,H/2,W/2], H and W even
-    int groups;             // conv2d_grp_f16x3.hip (plain form, fp32 maps, three products, stride 1, no up2).  0: not that entry's call.
-                            // Otherwise the call reports under its own name; > 1: x1 [N,C1,H,W] in `groups` groups, the pack that of a
-                            // [Co,C1/groups,3,3] weight; 1: the plain kernel; < 0: a group count the shape rule refuses
-    int splits;             // conv2d_splitk_f16x3.hip (the grouped entry's forms: c.groups != 0).  0: not that entry's call.  > 1: the
-                            // reduction runs in `splits` K ranges that leave partial maps in the workspace, behind the descriptor slot,
-                            // and a finish launch; 1: the plain or grouped kernel; < 0: a count the shape rule refuses
-    bool cat;               // the two-source kernels (also with C2 == 0: they are kernels of their own); false: the plain ones
-    const void *x1, *x2;    // sources [N,C1,H,W] and [N,C2,H,W] or NULL; x1 in x_dtype (fp32 when cat), x2 fp32
+    C2Form form;
+    int groups, splits;     // the caller's counts (C2_GROUPED, C2_SPLIT), as they came: the form's shape rule refuses what is below 1
+    const void *x1, *x2;    // sources [N,C1,H,W] and [N,C2,H,W] or NULL; x1 in x_dtype (fp32 when C2_CAT), x2 fp32
     const float *aff1, *aff2, *x1_range, *x2_range;
     int relu1, relu2, C1, C2;
     int x_dtype, residual_dtype, y_dtype;
@@ -214,22 +218,37 @@ struct C2Call {
     size_t workspace_bytes;
     hipStream_t stream;
 };
+// the call of an fp32, one-source, three-product entry; a typed or two-source entry sets its dtypes, product count and second source on top
+inline C2Call c2_call_f32(const char *who, C2Form form, const void *x, const float *x_range, const void *w_packed, const float *bias,
+                          const void *residual, void *y, float *out_range, int N, int Ci, int Co, int H, int W, int relu, void *workspace,
+                          size_t workspace_bytes, void *stream) {
+    C2Call c{};
+    c.who = who, c.form = form;
+    c.x1 = x, c.x1_range = x_range, c.C1 = Ci;
+    c.x_dtype = c.residual_dtype = c.y_dtype = MPHIP_DTYPE_F32, c.products = 3;
+    c.w_packed = w_packed, c.bias = bias, c.residual = residual, c.y = y, c.out_range = out_range;
+    c.N = N, c.Co = Co, c.H = H, c.W = W, c.relu = relu;
+    c.workspace = workspace, c.workspace_bytes = workspace_bytes, c.stream = (hipStream_t)stream;
+    return c;
+}
 struct C2Grid {
     dim3 grid;
     int tiles_w, tiles_h;
     unsigned nslots;        // partial maxima of out_range
+    float *part;            // C2_SPLIT with c.splits > 1: c.splits maps of y's size in the workspace; else NULL
 };
-// the workspace: one library-computed range descriptor per source that comes without one
+// the workspace: one library-computed range descriptor per source that comes without one (C2_SPLIT: its partial maps behind them)
 inline size_t c2_workspace_bytes(int descriptors) { return (size_t)descriptors * MPHIP_RANGE_FLOATS * sizeof(float); }
-// validate, carve the workspace, scan the ranges, size the grid, initialise out_range, launch: in this order, for every entry
+// conv2d_run.hip: validate, carve the workspace, scan the ranges, size the grid, initialise out_range, launch: in this order, for every entry
 int conv2d_run(C2Call c);
 // each unit's launcher of its instantiations (c.products resolved, every range in place)
 void conv2d_plain_launch(const C2Call &c, const C2Grid &g);   // conv2d_f16x3.hip: conv2d_k3_f16x3_kernel
 void conv2d_cat_launch(const C2Call &c, const C2Grid &g);     // conv2d_gn_f16x3.hip: conv2d_k3_cat_f16x3_kernel
-void conv2d_lp_launch(const C2Call &c, const C2Grid &g);      // conv2d_lp.hip: the one-product kernels of both forms
+void conv2d_lp_launch(const C2Call &c, const C2Grid &g);      // conv2d_lp.hip: the one-product kernels of C2_PLAIN and C2_CAT
 void conv2d_s2_launch(const C2Call &c, const C2Grid &g);      // conv2d_s2_f16x3.hip: conv2d_k3s2_f16x3_kernel
 void conv2d_up2_launch(const C2Call &c, const C2Grid &g);     // conv2d_up2_f16x3.hip: conv2d_k3_up2_f16x3_kernel / conv2d_k3_resup2_f16x3_kernel
-void conv2d_grouped_launch(const C2Call &c, const C2Grid &g); // conv2d_grp_f16x3.hip: conv2d_k3_grp_f16x3_kernel (c.groups > 1)
+void conv2d_grouped_launch(const C2Call &c, const C2Grid &g); // conv2d_grp_f16x3.hip: conv2d_k3_grp_f16x3_kernel; c.groups == 1: the plain launch
+void conv2d_split_launch(const C2Call &c, const C2Grid &g);   // conv2d_splitk_f16x3.hip: its two launches; g.part == NULL: the grouped launch
 // conv2d_s2_f16x3.hip: its output tile (64 channels x 8 rows x 16 columns per workgroup) and its shape rule (H, W: the input map)
 constexpr int C2S2_TH = 8, C2S2_TW = 16;
 bool c2_s2_supported(int N, int Ci, int Co, int H, int W);
@@ -240,12 +259,11 @@ bool c2_up2_supported(int N, int Ci, int Co, int h, int w);
 bool c2_grouped_supported(int N, int Ci, int Co, int H, int W, int groups);
 // conv2d_splitk_f16x3.hip: its shape rule: c2_grouped_supported, 1 <= splits <= C2_MAX_SPLITS, ((Ci / groups) / 16) % splits == 0; the
 // constants of mphip_conv2d_splits; the workgroups of its finish launch over ny = N * Co * H * W elements (one
-// out_range slot each, up to RANGE_MAX_PARTS); and its two launches (c.splits > 1; part: c.splits maps of ny floats)
+// out_range slot each, up to RANGE_MAX_PARTS)
 constexpr int C2_MAX_SPLITS = 16;
 constexpr int C2_SPLIT_MAX_S = 8, C2_SPLIT_MIN_CHUNKS = 2, C2_SPLIT_MAX_WG = 512, C2_SPLIT_MIN_K = 8, C2_SPLIT_MAX_UNSPLIT_WG = 128;
 bool c2_split_supported(int N, int Ci, int Co, int H, int W, int groups, int splits);
 unsigned c2_split_finish_blocks(size_t ny);
-void conv2d_split_launch(const C2Call &c, const C2Grid &g, float *part);
 
 // api.hip: the calling thread's conv arithmetic policy (mphip_conv3d_set_half_products): true inside torch.autocast(float16) regions
 bool conv_half_products();

@@ -9,7 +9,7 @@ also take fp16 / bf16.
 from __future__ import annotations
 
 import ctypes
-from typing import Optional, Tuple, Union
+from typing import Callable, NamedTuple, Optional, Tuple, Union
 
 import os as _os
 
@@ -1359,48 +1359,86 @@ def conv2d(x: torch.Tensor, pack: PackedConv2d, residual: Optional[torch.Tensor]
     csrc/conv2d_splitk_f16x3.hip: partial maps and a finish launch, reproducible bits that differ from the unsplit launch's in the last
     place); "auto" takes ops.conv2d_splits' recommendation.  fp32 maps and three products only: with a typed map, out_dtype or products
     it is a RuntimeError."""
-    typed = _conv2d_typed(out_dtype, products, x)
+    return _conv2d_one_source(_CONV2D_FORMS["plain"], x, pack, residual, relu, x_range, want_range, out_dtype, products, splits)
+
+
+class _Conv2dForm(NamedTuple):
+    """One form of the 2-D 3x3 conv: what its wrapper and _conv2d_launch look up, keyed as the library's own table of forms
+    (csrc/conv2d_run.hip).  The entry is mphip_<who>_fwd, with a _typed twin where `typed`."""
+    who: str                 # the wrapper's name, in messages
+    rule: str                # mphip_<rule>_supported and mphip_<rule>_workspace_bytes take (n, ci, co, h, w, *counts)
+    unsupported: str         # the end of the wrapper's "unsupported shape" error
+    y_hw: Callable           # (h, w) of x -> of y and the residual
+    lowres_residual: bool    # the residual is required and lives on the halved map, h and w even
+    grouped: bool            # takes a grouped pack; the entry takes pack.groups (the split-K entry: then the split count) after W
+    typed: bool              # half maps, out_dtype and products are allowed
+
+
+_SAME_MAP = lambda h, w: (h, w)
+_CONV2D_FORMS = {
+    "plain": _Conv2dForm("conv2d", "conv2d", "H={h} W={w} (there is no fallback)", _SAME_MAP, False, False, True),
+    "cat": _Conv2dForm("conv2d_cat", "conv2d_cat", "", _SAME_MAP, False, False, True),   # (the library states its shape rule)
+    "s2": _Conv2dForm("conv2d_s2", "conv2d_s2", "H={h} W={w} (there is no fallback)", lambda h, w: ((h + 1) // 2, (w + 1) // 2), False, False, False),
+    "up2": _Conv2dForm("conv2d_up2", "conv2d_up2", "h={h} w={w} (there is no fallback)", lambda h, w: (2 * h, 2 * w), False, False, False),
+    "resup2": _Conv2dForm("conv2d_resup2", "conv2d", "H={h} W={w} (H and W even; there is no fallback)", _SAME_MAP, True, False, False),
+    "grouped": _Conv2dForm("conv2d_grouped", "conv2d_grouped", "H={h} W={w} groups={groups} (there is no fallback)", _SAME_MAP, False, True, False),
+    # what ops.conv2d and ops.conv2d_grouped launch with splits > 1, under their own name: it always takes a workspace
+    "split": _Conv2dForm("conv2d_split", "conv2d_split", "", _SAME_MAP, False, True, False),
+}
+
+
+_CONV2D_ENTRIES = {}   # form.who -> (supported, workspace_bytes, {typed: (forward entry, its name)}): looked up once, not per call
+
+
+def _conv2d_entries(form):
+    got = _CONV2D_ENTRIES.get(form.who)
+    if got is None:
+        lib, fwd = _lib.load(), [f"mphip_{form.who}_fwd", f"mphip_{form.who}_fwd_typed"][:1 + form.typed]
+        got = _CONV2D_ENTRIES[form.who] = (getattr(lib, f"mphip_{form.rule}_supported"), getattr(lib, f"mphip_{form.rule}_workspace_bytes"),
+                                           {typed: (getattr(lib, name), name) for typed, name in enumerate(fwd)})
+    return got
+
+
+def _conv2d_one_source(form, x, pack, residual, relu, x_range, want_range, out_dtype=None, products=None, splits=None):
+    """The one-source wrappers: the checks of x against the pack and the form's shape rule, the choice of its descriptor, the launch."""
+    typed = form.typed and _conv2d_typed(out_dtype, products, x)
     x = _req_typed(x, "x") if typed else _req(x, "x")
     if x.dim() != 4 or x.shape[1] != pack.ci:
-        raise RuntimeError(f"conv2d: input {tuple(x.shape)} does not match Ci={pack.ci}")
+        raise RuntimeError(f"{form.who}: input {tuple(x.shape)} does not match Ci={pack.ci}")
     n, ci, h, w = x.shape
-    if not _lib.load().mphip_conv2d_supported(n, ci, pack.co, h, w):
-        raise RuntimeError(f"conv2d: unsupported shape N={n} Ci={ci} Co={pack.co} H={h} W={w} (there is no fallback)")
+    groups = pack.groups if form.grouped else 1
+    counts = (groups,) if form.grouped else ()
+    if (form.lowres_residual and (h % 2 or w % 2)) or not _conv2d_entries(form)[0](n, ci, pack.co, h, w, *counts):
+        raise RuntimeError(f"{form.who}: unsupported shape N={n} Ci={ci} Co={pack.co} " + form.unsupported.format(h=h, w=w, groups=groups))
+    if form.lowres_residual and residual is None:
+        raise RuntimeError(f"{form.who}: residual_lowres is required")
     xr = x_range if x_range is not None else current_range(x)   # None: the library scans x
-    ns = _conv2d_splits("conv2d", splits, typed, (n, ci, pack.co, h, w), 1)
-    return _conv2d_launch("conv2d", typed, pack, x, None, xr, False, None, None, None, False, residual, relu, want_range, out_dtype, products,
-                          ns)
+    ns = _conv2d_splits(form.who, splits, typed, (n, ci, pack.co, h, w), groups)
+    return _conv2d_launch(form, typed, pack, x, xr, residual, relu, want_range, out_dtype, products, ns)
 
 
-def _conv2d_launch(who, typed, pack, x1, aff1, r1, relu1, x2, aff2, r2, relu2, residual, relu, want_range, out_dtype, products, splits=1):
-    """What ops.conv2d (who = "conv2d": the plain kernels), ops.conv2d_cat, ops.conv2d_s2 (the stride-2 kernel: y and residual on the
-    halved map), ops.conv2d_up2 (y and residual on the doubled map), ops.conv2d_resup2 (the residual on the halved map) and
-    ops.conv2d_grouped (the entry takes the pack's group count after W) share once
-    their sources are checked and the descriptors r1 / r2 chosen: the residual check, the workspace, y and out_range, and the call of
-    the fp32 or (`typed`) the typed entry.  splits > 1 (ops.conv2d, ops.conv2d_grouped): the split-K entry, which takes the group count
-    and the split count after W and always a workspace."""
-    cat = who == "conv2d_cat"
-    grp = (pack.groups,) if who == "conv2d_grouped" else ()
-    if splits > 1:   # (the pack's group check below reads `grp`: the entry is chosen after it)
-        entry_who, grp_args = "conv2d_split", (pack.groups, splits)
-    else:
-        entry_who, grp_args = who, grp
-    if pack.groups != 1 and not grp:   # (its slabs hold Ci / groups channels: any other kernel would read past them)
+def _conv2d_launch(form, typed, pack, x1, r1, residual, relu, want_range, out_dtype=None, products=None, splits=1, second=None):
+    """What the wrappers of every form share once their sources are checked and the descriptors chosen: the residual check, the
+    workspace, y and out_range, and the call of the fp32 or (`typed`) the typed entry.  second = (affine1, relu1, x2, affine2, r2, relu2):
+    what ops.conv2d_cat brings.  splits > 1 (ops.conv2d, ops.conv2d_grouped): the split-K form's entry and workspace."""
+    who = form.who
+    if pack.groups != 1 and not form.grouped:   # (its slabs hold Ci / groups channels: any other kernel would read past them)
         raise RuntimeError(f"{who}: the pack is that of a grouped conv (groups = {pack.groups}): only ops.conv2d_grouped takes it")
-    lib = _lib.load()
+    entry_form = _CONV2D_FORMS["split"] if splits > 1 else form
+    counts = (pack.groups, splits) if splits > 1 else (pack.groups,) if form.grouped else ()
+    aff1, relu1, x2, aff2, r2, relu2 = second or (None, False, None, None, None, False)
+    _, workspace_bytes, forward = _conv2d_entries(entry_form)
     n, c1, h, w = x1.shape
     c2 = 0 if x2 is None else int(x2.shape[1])
-    ho, wo = ((h + 1) // 2, (w + 1) // 2) if who == "conv2d_s2" else (2 * h, 2 * w) if who == "conv2d_up2" else (h, w)
+    ho, wo = form.y_hw(h, w)
     if residual is not None:
         residual = _req_typed(residual, "residual") if typed else _req(residual, "residual")
-        rshape = (n, pack.co, h // 2, w // 2) if who == "conv2d_resup2" else (n, pack.co, ho, wo)
+        rshape = (n, pack.co, h // 2, w // 2) if form.lowres_residual else (n, pack.co, ho, wo)
         if tuple(residual.shape) != rshape:
-            raise RuntimeError(f"{who}: residual {tuple(residual.shape)} does not match {rshape}, the output{' at half its size' if who == 'conv2d_resup2' else ''}")
+            raise RuntimeError(f"{who}: residual {tuple(residual.shape)} does not match {rshape}, the output{' at half its size' if form.lowres_residual else ''}")
     ws_bytes = 0
     if splits > 1 or r1 is None or (x2 is not None and r2 is None):   # a source to scan, or partial maps
-        ws_name = "conv2d" if who == "conv2d_resup2" else entry_who
-        ws_bytes = (lib.mphip_conv2d_cat_workspace_bytes(n, c1, c2, pack.co, h, w) if cat
-                    else getattr(lib, f"mphip_{ws_name}_workspace_bytes")(n, c1, pack.co, h, w, *grp_args))
+        ws_bytes = workspace_bytes(n, c1, *((c2,) if second else ()), pack.co, h, w, *counts)
     ws = torch.empty((ws_bytes + 3) // 4, dtype=torch.float32, device=x1.device) if ws_bytes else None
     ydt = torch.float32 if out_dtype is None else out_dtype
     y = torch.empty((n, pack.co, ho, wo), dtype=ydt, device=x1.device)
@@ -1408,16 +1446,16 @@ def _conv2d_launch(who, typed, pack, x1, aff1, r1, relu1, x2, aff2, r2, relu2, r
     # the entry's arguments in its order: a typed entry takes a dtype code after x1, residual and y, and the product count after relu
     rdt = torch.float32 if residual is None else residual.dtype
     xdt, rdt, ydt, np_ = [(v,) if typed else () for v in (dtype_code(x1.dtype), dtype_code(rdt), dtype_code(ydt), _conv2d_products(products, who))]
-    if cat:
+    if second:
         sources = (_ptr(x1), *xdt, _ptr(aff1), int(bool(relu1)), _ptr(r1), c1, _ptr(x2), _ptr(aff2), int(bool(relu2)), _ptr(r2), c2)
         shape = (n, pack.co, h, w)
     else:
         sources = (_ptr(x1), *xdt, _ptr(r1))
-        shape = (n, c1, pack.co, h, w, *grp_args)
+        shape = (n, c1, pack.co, h, w, *counts)
     args = (*sources, _ptr(pack.packed()), _ptr(pack.bias), _ptr(residual), *rdt, _ptr(y), *ydt, _ptr(out_range), *shape, int(bool(relu)), *np_,
             _ptr(ws), ws_bytes, _stream())
-    entry = f"mphip_{entry_who}_fwd" + ("_typed" if typed else "")
-    _lib.check(getattr(lib, entry)(*args), entry)
+    entry, name = forward[typed]
+    _lib.check(entry(*args), name)
     return tag_range(y, out_range)
 
 
@@ -1431,14 +1469,7 @@ def conv2d_s2(x: torch.Tensor, pack: PackedConv2d, residual: Optional[torch.Tens
     """y = act(conv3x3(x, stride 2) + bias (+ residual)) on NCHW fp32, padding 1 (mphip_conv2d_s2_fwd): y and residual are
     [N, Co, (H+1)//2, (W+1)//2].  The pack, the f16x3 arithmetic and the descriptors are ops.conv2d's: with the same x, x_range and pack
     the result is, bit for bit, conv2d(...)[:, :, ::2, ::2] (a residual being the even sub-sample of that call's).  fp32 only."""
-    x = _req(x, "x")
-    if x.dim() != 4 or x.shape[1] != pack.ci:
-        raise RuntimeError(f"conv2d_s2: input {tuple(x.shape)} does not match Ci={pack.ci}")
-    n, ci, h, w = x.shape
-    if not _lib.load().mphip_conv2d_s2_supported(n, ci, pack.co, h, w):
-        raise RuntimeError(f"conv2d_s2: unsupported shape N={n} Ci={ci} Co={pack.co} H={h} W={w} (there is no fallback)")
-    xr = x_range if x_range is not None else current_range(x)   # None: the library scans x
-    return _conv2d_launch("conv2d_s2", False, pack, x, None, xr, False, None, None, None, False, residual, relu, want_range, None, None)
+    return _conv2d_one_source(_CONV2D_FORMS["s2"], x, pack, residual, relu, x_range, want_range)
 
 
 def conv2d_grouped_supported(n: int, ci: int, co: int, h: int, w: int, groups: int) -> bool:
@@ -1454,16 +1485,7 @@ def conv2d_grouped(x: torch.Tensor, pack: PackedConv2d, residual: Optional[torch
     the same x_range the result is, bit for bit, conv2d on the dense weight with the group blocks on its diagonal and zeros elsewhere;
     with groups == 1 it is conv2d.  fp32 only.  splits: as in ops.conv2d (None or 1: this entry, bit for bit; an int above 1 or "auto":
     the split-K entry with this pack, the K ranges taken from each group's chunks)."""
-    x = _req(x, "x")
-    if x.dim() != 4 or x.shape[1] != pack.ci:
-        raise RuntimeError(f"conv2d_grouped: input {tuple(x.shape)} does not match Ci={pack.ci}")
-    n, ci, h, w = x.shape
-    if not _lib.load().mphip_conv2d_grouped_supported(n, ci, pack.co, h, w, pack.groups):
-        raise RuntimeError(f"conv2d_grouped: unsupported shape N={n} Ci={ci} Co={pack.co} H={h} W={w} groups={pack.groups} (there is no fallback)")
-    xr = x_range if x_range is not None else current_range(x)   # None: the library scans x
-    ns = _conv2d_splits("conv2d_grouped", splits, False, (n, ci, pack.co, h, w), pack.groups)
-    return _conv2d_launch("conv2d_grouped", False, pack, x, None, xr, False, None, None, None, False, residual, relu, want_range, None, None,
-                          ns)
+    return _conv2d_one_source(_CONV2D_FORMS["grouped"], x, pack, residual, relu, x_range, want_range, splits=splits)
 
 
 def conv2d_up2_supported(n: int, ci: int, co: int, h: int, w: int) -> bool:
@@ -1479,14 +1501,7 @@ def conv2d_up2(x: torch.Tensor, pack: PackedConv2d, residual: Optional[torch.Ten
     blended while the conv stages its input: the up-sampled map is never written.  x_range: the descriptor of the LOW-resolution x (a
     bound of up2(x)); without one the descriptor tagged on x is used, else the library scans x.  With the same x_range and pack the
     result is, bit for bit, conv2d(model.up2_reference(x), ...).  fp32 only."""
-    x = _req(x, "x")
-    if x.dim() != 4 or x.shape[1] != pack.ci:
-        raise RuntimeError(f"conv2d_up2: input {tuple(x.shape)} does not match Ci={pack.ci}")
-    n, ci, h, w = x.shape
-    if not _lib.load().mphip_conv2d_up2_supported(n, ci, pack.co, h, w):
-        raise RuntimeError(f"conv2d_up2: unsupported shape N={n} Ci={ci} Co={pack.co} h={h} w={w} (there is no fallback)")
-    xr = x_range if x_range is not None else current_range(x)   # None: the library scans x
-    return _conv2d_launch("conv2d_up2", False, pack, x, None, xr, False, None, None, None, False, residual, relu, want_range, None, None)
+    return _conv2d_one_source(_CONV2D_FORMS["up2"], x, pack, residual, relu, x_range, want_range)
 
 
 def conv2d_resup2(x: torch.Tensor, pack: PackedConv2d, residual_lowres: torch.Tensor, relu: bool = False,
@@ -1494,16 +1509,7 @@ def conv2d_resup2(x: torch.Tensor, pack: PackedConv2d, residual_lowres: torch.Te
     """y = act(conv3x3(x) + bias + up2(residual_lowres)) on NCHW fp32, padding 1 (mphip_conv2d_resup2_fwd): x is [N, Ci, H, W] with H
     and W even, residual_lowres [N, Co, H/2, W/2]; its up-sampled map is blended in the epilogue and never written.  Bit for bit
     conv2d(x, pack, residual=model.up2_reference(residual_lowres), ...).  fp32 only."""
-    x = _req(x, "x")
-    if x.dim() != 4 or x.shape[1] != pack.ci:
-        raise RuntimeError(f"conv2d_resup2: input {tuple(x.shape)} does not match Ci={pack.ci}")
-    n, ci, h, w = x.shape
-    if h % 2 or w % 2 or not _lib.load().mphip_conv2d_supported(n, ci, pack.co, h, w):
-        raise RuntimeError(f"conv2d_resup2: unsupported shape N={n} Ci={ci} Co={pack.co} H={h} W={w} (H and W even; there is no fallback)")
-    if residual_lowres is None:
-        raise RuntimeError("conv2d_resup2: residual_lowres is required")
-    xr = x_range if x_range is not None else current_range(x)   # None: the library scans x
-    return _conv2d_launch("conv2d_resup2", False, pack, x, None, xr, False, None, None, None, False, residual_lowres, relu, want_range, None, None)
+    return _conv2d_one_source(_CONV2D_FORMS["resup2"], x, pack, residual_lowres, relu, x_range, want_range)
 
 
 def conv2d_stem_supported(n: int, ci: int, co: int, h: int, w: int, pool: bool = True) -> bool:
@@ -1600,7 +1606,8 @@ def conv2d_cat(x1: torch.Tensor, pack: PackedConv2d, x2: Optional[torch.Tensor] 
     # (a table's source keeps the caller's descriptor or none: the one tagged on x_i describes the raw values, and the entry refuses none)
     r1 = x1_range if (x1_range is not None or affine1 is not None) else current_range(x1)
     r2 = x2_range if (x2_range is not None or affine2 is not None or x2 is None) else current_range(x2)
-    return _conv2d_launch("conv2d_cat", typed, pack, x1, affine1, r1, relu1, x2, affine2, r2, relu2, residual, relu, want_range, out_dtype, products)
+    return _conv2d_launch(_CONV2D_FORMS["cat"], typed, pack, x1, r1, residual, relu, want_range, out_dtype, products,
+                          second=(affine1, relu1, x2, affine2, r2, relu2))
 
 
 def avgpool2_bwd(dout: torch.Tensor) -> torch.Tensor:
