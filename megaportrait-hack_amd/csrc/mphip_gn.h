@@ -23,4 +23,14 @@ __device__ __forceinline__ float gn_value(const GnParams &p, float xv, float mea
     return v;
 }
 
+
+// host side, defined in warp.hip: mphip_groupnorm_apply(no second affine, relu = 1, tanh = 0, pool2 = 1) whose residual is the output of the
+// K2 that ran on `coords` with the corner image `img` and left its per-tile marks in `todo`.  The residual is rebuilt from the image
+// wherever K2 took it from there (gn_apply_pool_warp_kernel) and loaded elsewhere: bitwise the plain launch.  _ok: whether the kernel
+// covers the shape.
+bool gn_apply_pool_warp_ok(int N, int C, int D, int H, int W, int G);
+int gn_apply_pool_warp_launch(const float *x, const float *stats, const float *gamma, const float *beta, const float *residual, float *y,
+                              float *out_range, const float *coords, const int *todo, const float *img, int N, int C, int D, int H, int W, int G,
+                              hipStream_t s);
+
 }  // namespace mphip

@@ -202,6 +202,63 @@ __device__ __forceinline__ TapOff rebase(const Taps &t, int x0, int y0, int z0, 
     return r;
 }
 
+// The tap arithmetic on the PACKED fp32 pipe, two channels per instruction: the (c, c+1) pair of a tap is exactly what one ds_read2_b32
+// returns, and the tap's weight is broadcast to both halves by op_sel — weights stay single registers (pairs {w_2j, w_2j+1}, even / odd
+// picked by the instruction's op_sel bits).  Written as inline assembly because hipcc's own packing of this loop duplicates every weight
+// into a register pair (+180 registers, 700 B of scratch at 128).  With the staging gone the loop is VALU-bound (95 -> 52 instructions per
+// channel pair).  Per channel and position still acc = 0; acc = acc + p_k * w_k in tap order, one rounding per op.
+typedef float k2_f2 __attribute__((ext_vector_type(2)));
+template <int ODD>
+__device__ __forceinline__ k2_f2 k2_pk_mul(k2_f2 p, k2_f2 wpair) {
+    k2_f2 m;
+    if (ODD) asm("v_pk_mul_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,1]" : "=v"(m) : "v"(p), "v"(wpair));
+    else     asm("v_pk_mul_f32 %0, %1, %2 op_sel_hi:[1,0]" : "=v"(m) : "v"(p), "v"(wpair));
+    return m;
+}
+__device__ __forceinline__ k2_f2 k2_pk_add(k2_f2 a, k2_f2 b) {
+    k2_f2 m;
+    asm("v_pk_add_f32 %0, %1, %2" : "=v"(m) : "v"(a), "v"(b));
+    return m;
+}
+// The channel pair (c, c+1) of N samples from the staged [cell][channel] image (src = image + c): tb = the eight tap addresses of a sample
+// (floats, premultiplied by the even channel pitch: every read is one 8-byte-aligned ds_read_b64), wp = its weights in pairs.  All reads
+// first (k2_tap_reads), then per sample the chain above (k2_tap_chain).  K2 (warp_gather_kernel) and the pooled apply that rebuilds K2's
+// output (gn_apply_pool_warp_kernel, which issues the reads of the next pair ahead of the chain of this one) both get a value from these
+// two and nothing else: one definition, the same bits.
+template <int N>
+__device__ __forceinline__ void k2_tap_reads(const float *src, const int (&tb)[N][8], k2_f2 (&pv)[N][8]) {
+#pragma unroll
+    for (int i = 0; i < N; ++i)
+#pragma unroll
+        for (int k = 0; k < 8; ++k) pv[i][k] = *reinterpret_cast<const k2_f2 *>(src + tb[i][k]);   // (even pitch, even channel: 8-byte aligned)
+}
+template <int N>
+__device__ __forceinline__ void k2_tap_chain(const k2_f2 (&pv)[N][8], const k2_f2 (&wp)[N][4], k2_f2 (&acc)[N]) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        acc[i] = k2_f2{0.0f, 0.0f};
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            acc[i] = k2_pk_add(acc[i], k2_pk_mul<0>(pv[i][2 * j], wp[i][j]));
+            acc[i] = k2_pk_add(acc[i], k2_pk_mul<1>(pv[i][2 * j + 1], wp[i][j]));
+        }
+    }
+}
+template <int N>
+__device__ __forceinline__ void k2_tap_pairs(const float *src, const int (&tb)[N][8], const k2_f2 (&wp)[N][4], k2_f2 (&acc)[N]) {
+    k2_f2 pv[N][8];
+    k2_tap_reads<N>(src, tb, pv);
+    k2_tap_chain<N>(pv, wp, acc);
+}
+// a sample's tap addresses and weight pairs in that form, from its taps rebased into the image
+__device__ __forceinline__ void k2_tap_setup(const TapOff &o, const Taps &t, int (&tb)[8], k2_f2 (&wp)[4]) {
+    tb[0] = o.base; tb[1] = o.base + o.dx; tb[2] = o.base + o.dy; tb[3] = o.base + o.dy + o.dx;
+    tb[4] = o.base + o.dz; tb[5] = o.base + o.dz + o.dx; tb[6] = o.base + o.dz + o.dy;
+    tb[7] = o.base + o.dz + o.dy + o.dx;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) wp[j] = k2_f2{t.w[2 * j], t.w[2 * j + 1]};
+}
+
 // host side, defined in warp.hip: argument checks of the warp entry points and the coordinate pass (warp_coords_kernel)
 int check_warp_args(const char *name, const void *v, const void *field, const void *ld, const void *lh, const void *lw, const void *out, int B, int C,
                     int D, int H, int W, int fD, int fH, int fW);

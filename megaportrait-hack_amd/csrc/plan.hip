@@ -20,6 +20,7 @@
 
 #include "linspace_tables.h"
 #include "mphip_common.h"
+#include "mphip_gn.h"
 
 using namespace mphip;
 
@@ -600,9 +601,22 @@ T5 conv3d_k1_gn_res(Ctx &c, T5 &x, ConvW &cw, ConvOut &y2, const Norm &nm, int g
     return out;
 }
 
+// What K2 left behind when x is its output (run_slice): the coordinates it sampled at, its per-tile marks and the corner image it read.
+// With them the block's last launch rebuilds the identity residual instead of fetching it (warp.hip: gn_apply_pool_warp_kernel).
+struct WarpSrc {
+    Buf coords, todo, img;
+    bool on = true;   // MPHIP_RESIDUAL_FROM_WARP=0: the plain launch (same bits)
+};
+
+// ... and whether that launch covers the block: identity shortcut, pooled, plain (finished, no second affine) apply, a shape the kernel takes
+bool residual_from_warp_ok(const ResBlock &b, const T5 &x, const ConvOut &y2, bool pool_after, const WarpSrc *wsrc) {
+    return wsrc && wsrc->on && b.identity && pool_after && y2.splits == 1 && !b.gn2.w2 && gn_apply_pool_warp_ok(x.n, x.c, x.d, x.h, x.w, 32);
+}
+
 // ResBlock3D._forward, inference branch (model.py:500-528); consumes x.  `hook`: called right after conv1 was launched.
+// `wsrc`: x is the output of the K2 that left these behind.
 template <typename Hook>
-T5 resblock(Ctx &c, ResBlock &b, T5 &x, bool pool_after, Hook hook) {
+T5 resblock(Ctx &c, ResBlock &b, T5 &x, bool pool_after, Hook hook, const WarpSrc *wsrc = nullptr) {
     const bool finish = shortcut_finish_ok(c, b, x, pool_after);   // the shortcut conv goes last and finishes the block
     ConvOut identity = b.identity ? as_convout(x) : finish ? ConvOut() : conv3d_split(c, x, b.shortcut, 0);
     ConvOut y = conv3d_split(c, x, b.conv1, 32, &b.gn1, &b.conv2);   // (+ gn1's affine table when it will be folded into conv2)
@@ -619,8 +633,16 @@ T5 resblock(Ctx &c, ResBlock &b, T5 &x, bool pool_after, Hook hook) {
         give(c, a);
     }
     ensure_stats(c, y2, 32);
-    T5 out = finish ? conv3d_k1_gn_res(c, x, b.shortcut, y2, b.gn2, 32, true, pool_after)
-                    : groupnorm_apply(c, y2, b.gn2, 32, &identity, true, false, pool_after, 1, 1, 1);
+    T5 out;
+    if (finish) {
+        out = conv3d_k1_gn_res(c, x, b.shortcut, y2, b.gn2, 32, true, pool_after);
+    } else if (residual_from_warp_ok(b, x, y2, pool_after, wsrc)) {
+        out = new_t5(c, x.n, x.c, x.d / 2, x.h / 2, x.w / 2, true);
+        RUN(c, gn_apply_pool_warp_launch(y2.t.data.p, y2.stats.p, b.gn2.gw, b.gn2.gb, x.data.p, out.data.p, out.range.p, wsrc->coords.p,
+                                         (const int *)wsrc->todo.p, wsrc->img.p, x.n, x.c, x.d, x.h, x.w, 32, c.s));
+    } else {
+        out = groupnorm_apply(c, y2, b.gn2, 32, &identity, true, false, pool_after, 1, 1, 1);
+    }
     give(c, y2);
     if (!b.identity && !finish) give(c, identity);
     give(c, x);
@@ -651,11 +673,13 @@ T5 upsample2(Ctx &c, T5 &x, const Roi *roi = nullptr) {   // nn.Upsample(scale_f
 
 // G3d.forward (model.py:571-597); consumes x.  out: caller buffer (may be nullptr: arena)
 // `tail(n)`: called before the last upsample; returns the sample boxes of the warp that will read the result (or an "off" Roi)
+// `wsrc`: x is K2's output and these are what K2 left behind; consumed (given back once the first block is through)
 template <typename Hook, typename Tail>
-T5 g3d(Ctx &c, T5 &x, bool external_out, float *out, Hook hook, Tail tail) {
+T5 g3d(Ctx &c, T5 &x, bool external_out, float *out, Hook hook, Tail tail, WarpSrc *wsrc = nullptr) {
     Plan *p = c.p;
     auto none = [] {};
-    T5 t = resblock(c, p->down[0], x, true, hook);
+    T5 t = resblock(c, p->down[0], x, true, hook, wsrc);
+    if (wsrc) { give(c, wsrc->coords); give(c, wsrc->todo); give(c, wsrc->img); }
     t = resblock(c, p->down[1], t, true, none);
     t = resblock(c, p->down[2], t, true, none);
     t = resblock(c, p->down[3], t, false, none);
@@ -783,6 +807,10 @@ int run_slice(Plan *p, const void *vs, const float *es, const float *Rs, const f
         c_s2c = out1[0];
     }
     T5 vc = new_t5(cm, B, p->C, p->D, p->H, p->W, true);
+    // K2.  Its coordinates, per-tile marks (the head of its workspace) and corner image stay in the arena until G3d's first block is through:
+    // that block's last launch rebuilds its residual — K2's output — from them (WarpSrc).  Kept whether or not the switch is on: the arena's
+    // layout, sized once per B, does not depend on the environment.
+    WarpSrc wsrc;
     {
         const size_t wsb = mphip_warp_workspace_bytes(B, p->D, p->H, p->W);   // (covers the per-tile marks of the gather passes)
         Buf ws = take(cm, wsb);
@@ -790,10 +818,11 @@ int run_slice(Plan *p, const void *vs, const float *es, const float *Rs, const f
             RUN(cm, mphip_warp_volume_coords_img((const float *)vs, c_s2c.p, vc.data.p, vc.range.p, B, p->C, p->D, p->H, p->W, ws.p, wsb, cimg.p, s));
         else
             RUN(cm, mphip_warp_volume_coords_img_typed(vs, vs_dt, c_s2c.p, vc.data.p, vc.range.p, B, p->C, p->D, p->H, p->W, ws.p, wsb, cimg.p, s));
-        give(cm, ws);
+        wsrc.coords = c_s2c; wsrc.todo = ws; wsrc.img = cimg;
+        c_s2c = Buf(); cimg = Buf();
+        const char *e = getenv("MPHIP_RESIDUAL_FROM_WARP");
+        wsrc.on = !(e && e[0] == '0');
     }
-    give(cm, c_s2c);
-    give(cm, cimg);
     int join_rc = MPHIP_OK;
     auto tail = [&]() -> Roi {   // the boxes are needed from here on: join the side stream before G3d's last upsample
         if (overlap && (hipEventRecord(p->ev_join, p->side) != hipSuccess || hipStreamWaitEvent(s, p->ev_join, 0) != hipSuccess)) {
@@ -805,7 +834,7 @@ int run_slice(Plan *p, const void *vs, const float *es, const float *Rs, const f
         r.box = (const int *)box.p;
         return r;
     };
-    T5 vc2d = g3d(cm, vc, false, nullptr, issue_c2d, tail);
+    T5 vc2d = g3d(cm, vc, false, nullptr, issue_c2d, tail, &wsrc);
     if (cs.rc != MPHIP_OK && cm.rc == MPHIP_OK) cm.rc = cs.rc;
     if (join_rc != MPHIP_OK) return join_rc;
     // apply_warping_field + torch.sum(dim=2) (model.py:1167-1171) in one kernel (K3), on the coordinates computed above

@@ -5,6 +5,7 @@
 // ATen's CPU kernels round; the FMAs ATen uses are explicit fmaf().
 #include "mphip_ablate.h"
 #include "mphip_common.h"
+#include "mphip_gn.h"
 #include "mphip_resample.h"
 #include "mphip_warp.h"
 
@@ -282,11 +283,12 @@ warp_corner_image_kernel(const dtype_t<DT> *__restrict__ v, float *__restrict__ 
 }
 // one block of the corner image -> LDS, as LDS-DMA (16 bytes per lane, 1 KiB per wave and instruction, no registers); issued by hand:
 // the compiler would wait for each transfer before the next LDS access.  The caller waits (vmcnt(0)) before its barrier.
+template <int THREADS>
 __device__ __forceinline__ void k2_dma_image(const float *__restrict__ blk, float *lds, int floats) {
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const unsigned lds0 = (unsigned)(uintptr_t)(__attribute__((address_space(3))) float *)lds;
     const int pieces = (floats + 255) / 256;
-    for (int q = wave; q < pieces; q += K2_THREADS / 64) {
+    for (int q = wave; q < pieces; q += THREADS / 64) {
         const int f = q * 256 + lane * 4;   // float index of this lane's 16 bytes
         if (f < floats) {
             const float *src = blk + f;
@@ -304,24 +306,7 @@ __device__ __forceinline__ void k2_stage_corner(const float *__restrict__ vb, fl
     }
 }
 
-// The tap arithmetic on the PACKED fp32 pipe, two channels per instruction: the (c, c+1) pair of a tap is exactly what one ds_read2_b32
-// returns, and the tap's weight is broadcast to both halves by op_sel — weights stay single registers (pairs {w_2j, w_2j+1}, even / odd
-// picked by the instruction's op_sel bits).  Written as inline assembly because hipcc's own packing of this loop duplicates every weight
-// into a register pair (+180 registers, 700 B of scratch at 128).  With the staging gone the loop is VALU-bound (95 -> 52 instructions per
-// channel pair).  Per channel and position still acc = 0; acc = acc + p_k * w_k in tap order, one rounding per op.
-typedef float k2_f2 __attribute__((ext_vector_type(2)));
-template <int ODD>
-__device__ __forceinline__ k2_f2 k2_pk_mul(k2_f2 p, k2_f2 wpair) {
-    k2_f2 m;
-    if (ODD) asm("v_pk_mul_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,1]" : "=v"(m) : "v"(p), "v"(wpair));
-    else     asm("v_pk_mul_f32 %0, %1, %2 op_sel_hi:[1,0]" : "=v"(m) : "v"(p), "v"(wpair));
-    return m;
-}
-__device__ __forceinline__ k2_f2 k2_pk_add(k2_f2 a, k2_f2 b) {
-    k2_f2 m;
-    asm("v_pk_add_f32 %0, %1, %2" : "=v"(m) : "v"(a), "v"(b));
-    return m;
-}
+// (the tap arithmetic itself — packed fp32, two channels per instruction — is k2_tap_pairs, mphip_warp.h)
 #ifdef MPHIP_K2_TRACE   /* dev: wall-clock (100 MHz) stamps per workgroup: start, box known, image staged, done */
 __device__ unsigned long long g_k2_trace[4096 * 4];
 #define K2_STAMP(i) if (threadIdx.x == 0 && blockIdx.y * gridDim.x + blockIdx.x < 4096) g_k2_trace[(blockIdx.y * gridDim.x + blockIdx.x) * 4 + (i)] = wall_clock64();
@@ -377,7 +362,7 @@ warp_gather_kernel(const dtype_t<DT> *__restrict__ v, const float *__restrict__ 
     const bool maybe = TYPED || (fx >= 0.0f && fx < (float)(K2_CORNER_E - 1) && fy >= 0.0f && fy < (float)(K2_CORNER_E - 1) && fz >= 0.0f && fz < (float)(K2_CORNER_E - 1));
     const bool dma = maybe && img != nullptr;
 #ifndef MPHIP_K2_ABL_NOSTAGE   /* dev ablations (timing only, wrong results): tools/k2_ablate.sh */
-    if (dma) k2_dma_image(img + ((size_t)b * gridDim.y + blockIdx.y) * k2_block_floats(cg), lds, (int)k2_block_floats(cg));
+    if (dma) k2_dma_image<K2_THREADS>(img + ((size_t)b * gridDim.y + blockIdx.y) * k2_block_floats(cg), lds, (int)k2_block_floats(cg));
 #endif
     if (active) {
 #pragma unroll
@@ -423,21 +408,8 @@ warp_gather_kernel(const dtype_t<DT> *__restrict__ v, const float *__restrict__ 
 #pragma unroll
                 for (int j = 0; j < 4; ++j) wp[i][j] = k2_f2{taps[i].w[2 * j], taps[i].w[2 * j + 1]};
             auto two_channels = [&](const float *src, int c) {
-                k2_f2 pv[2][8];
-#pragma unroll
-                for (int i = 0; i < 2; ++i)
-#pragma unroll
-                    for (int k = 0; k < 8; ++k) pv[i][k] = *reinterpret_cast<const k2_f2 *>(src + tb[i][k]);   // (even pitch, even channel: 8-byte aligned)
                 k2_f2 acc[2];
-#pragma unroll
-                for (int i = 0; i < 2; ++i) {
-                    acc[i] = k2_f2{0.0f, 0.0f};
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        acc[i] = k2_pk_add(acc[i], k2_pk_mul<0>(pv[i][2 * j], wp[i][j]));
-                        acc[i] = k2_pk_add(acc[i], k2_pk_mul<1>(pv[i][2 * j + 1], wp[i][j]));
-                    }
-                }
+                k2_tap_pairs<2>(src, tb, wp, acc);
 #ifdef MPHIP_K2_ABL_NOSTORE
                 if (acc[0][0] == 1.2345e30f)
 #endif
@@ -473,6 +445,200 @@ warp_gather_kernel(const dtype_t<DT> *__restrict__ v, const float *__restrict__ 
     // (slot = group * tiles + tile: the follow-up kernels fold into group 0's slots)
     if (out_range) range_note_block(mbits, out_range, blockIdx.y * gridDim.x + blockIdx.x, gridDim.x * gridDim.y);
     K2_STAMP(3)
+}
+
+// GroupNorm apply + residual + ReLU + AvgPool3d(2) of the block K2's output enters (G3d's first ResBlock3D, identity shortcut), with the
+// residual REBUILT instead of fetched: the residual is K2's output, and wherever K2 served a tile from the corner image (todo == 0: every
+// tile of the reference's own fields) each of its values is k2_tap_reads + k2_tap_chain on 85 KB that are still in the workspace.  gn_apply_pool_kernel<2>
+// streams conv2's output AND the residual (2 x 201 MB at B = 8) to write 25 MB; this kernel streams conv2's output only and does the tap
+// arithmetic K2 did (20 us of the chip's fp32 pipe) underneath.
+// Organised like K2: a thread owns positions and walks the channels, so a sample's taps are built once.  A workgroup of 512 threads takes a
+// 32 x 64 (h, w) tile of one frame and the slice PAIR (2 od, 2 od + 1), in two passes of 16 rows; per pass a thread holds four samples — two
+// along w (its own pooling pair), times the two slices.  The h-partner of a cell is the other half of the wave (lanes 0-31: an even row,
+// lanes 32-63: the row below): per channel pair (c, c+1) one v_permlane32_swap per value hands the lower half all eight values of channel c
+// and the upper half those of c+1, which each adds in gn_apply_pool_kernel's order (d outer, then h, then w, from 0.0f, then / 8.0f) and
+// stores: 128 contiguous bytes per half wave.  blockIdx.y = (K2's channel group, i.e. block of the image) x csub parts of it: few tiles ->
+// more parts, so that the chip has a workgroup per CU.
+// A pair with a slice K2 did NOT serve from the corner (travelling fields) loads the residual from p.residual, as the plain kernel does.
+// Values: gn_value on the bits K2 stored (same make_taps / rebase / k2_tap_reads / k2_tap_chain), summed in that order: bitwise gn_apply_pool_kernel.
+// Schedule: nothing in the channel walk waits for memory it has just asked for — the channels' parameters sit in LDS, a pair's
+// tap reads go out a pair ahead of their chain, conv2's output a trip ahead.
+constexpr int GPW_THREADS = 512;
+constexpr int GPW_ROWS = GPW_THREADS / (K2_TW / 2);   // rows of the tile per pass
+constexpr int GPW_TRIP = 8;                              // channels per trip of the walk (their offsets: immediates of the tap reads)
+static_assert(K2_TH % GPW_ROWS == 0 && GPW_ROWS % 2 == 0, "whole passes of row pairs");
+__global__ void __launch_bounds__(GPW_THREADS)
+gn_apply_pool_warp_kernel(GnParams p, const float *__restrict__ coords, const int *__restrict__ todo, const float *__restrict__ img, int D, int H,
+                          int W, int cg /* channels per block of the image (K2's) */, int csub /* workgroups per block */) {
+    __shared__ __attribute__((aligned(16))) float lds[K2_LDS_FLOATS];
+    __shared__ float4 chn[K2_CG_MAX];   // (mean, rstd, gamma, beta) of this workgroup's channels
+    const int C = p.C, HW = H * W, oD = D / 2, oH = H / 2, oW = W / 2;
+    const int tiles_w = (W + K2_TW - 1) / K2_TW, tiles = tiles_w * ((H + K2_TH - 1) / K2_TH);
+    const unsigned bid = xcd_remap(blockIdx.x, gridDim.x);   // (slice pair fastest, then tile, then frame: K2's order)
+    const int od = (int)(bid % (unsigned)oD);
+    const int tile = (int)((bid / (unsigned)oD) % (unsigned)tiles);
+    const int b = (int)(bid / ((unsigned)oD * (unsigned)tiles));
+    const int grp = (int)blockIdx.y / csub, sub = (int)blockIdx.y % csub, groups = (int)gridDim.y / csub;
+    const int cg0 = grp * cg, Cg = min(C - cg0, cg), cgp = k2_pitch(cg);
+    const int cs = ((Cg / GPW_TRIP + csub - 1) / csub) * GPW_TRIP;   // channels per part: whole trips (C % GPW_TRIP == 0)
+    const int c_lo = sub * cs, c_hi = min(Cg, c_lo + cs);           // this workgroup's channels of the block
+    const size_t vol = (size_t)D * HW;
+    const int *mk = todo + ((size_t)b * tiles + tile) * D + 2 * od;   // K2's marks of the two slices
+    const bool rebuild = mk[0] == 0 && mk[1] == 0;                     // block-uniform
+    const int row = (int)(threadIdx.x / (K2_TW / 2));
+    const int h0 = (tile / tiles_w) * K2_TH + row;
+    const int w = (tile % tiles_w) * K2_TW + (int)(threadIdx.x % (K2_TW / 2)) * 2;
+    // a pass's coordinates: 2 slices x (x, y, z) of 2 positions; the first pass's are asked for ahead of the image, the second's ahead of the
+    // first's channel walk: one round trip in front of the stream
+    auto load_coords = [&](int h, float (&cf)[2][6]) {
+        if (h < H && w < W) {   // W % 4 == 0 -> a thread's 2 positions share validity
+#pragma unroll
+            for (int s = 0; s < 2; ++s) {
+                const float *cp = coords + (((size_t)b * D + 2 * od + s) * HW + h * W + w) * 3;   // (w even: 8-byte aligned)
+#pragma unroll
+                for (int q = 0; q < 3; ++q) {
+                    const float2 t2 = *reinterpret_cast<const float2 *>(cp + q * 2);
+                    cf[s][q * 2] = t2.x; cf[s][q * 2 + 1] = t2.y;
+                }
+            }
+        }
+    };
+    float cf[2][6] = {}, cfn[2][6] = {};
+    if (rebuild) load_coords(h0, cf);
+    if ((int)threadIdx.x < c_hi - c_lo) {   // (the channel walk reads these from LDS: a load from memory in it would wait for the whole stream)
+        const int c = cg0 + c_lo + (int)threadIdx.x, gi = b * (C / p.cpg) + c / p.cpg;
+        chn[threadIdx.x] = make_float4(p.stats[gi * 2], p.stats[gi * 2 + 1], p.gamma[c], p.beta[c]);
+    }
+    if (rebuild) {
+        k2_dma_image<GPW_THREADS>(img + ((size_t)b * groups + grp) * k2_block_floats(cg), lds, (int)k2_block_floats(cg));
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // this wave's pieces of the image have landed
+    }
+    __syncthreads();
+    // what the block asks of gn_value, as constants: no second affine, residual, ReLU, no tanh (the launcher passes nothing else)
+    GnParams q = p;
+    q.relu = 1;
+    q.tanh_ = 0;
+    const int half = (int)(threadIdx.x & 63) >> 5;   // 0: even row, channel c of a pair; 1: odd row, channel c + 1
+    unsigned mbits = 0;
+    // one pass: GPW_ROWS rows of the tile.  RB: the residual is rebuilt (else loaded); a compile-time copy of `rebuild`, so that the walk
+    // has no branch in it (the compiler counts the loads in flight only within straight-line code)
+    auto pass = [&](auto RB, int h) {
+        constexpr bool REBUILD = decltype(RB)::value;
+        int tb[2][2][8];      // [slice][position]: tap addresses in the image
+        k2_f2 wp[2][2][4];    // ... and weights in pairs
+        if constexpr (REBUILD) {
+            const Box cbx{0, 0, 0, K2_CORNER_E, K2_CORNER_E, K2_CORNER_E};
+#pragma unroll
+            for (int s = 0; s < 2; ++s)
+#pragma unroll
+                for (int i = 0; i < 2; ++i) {
+                    const Coord3 c{cf[s][i * 3], cf[s][i * 3 + 1], cf[s][i * 3 + 2]};
+                    const Taps t = make_taps(c, D, H, W);
+                    k2_tap_setup(rebase(t, (int)floorf(c.x), (int)floorf(c.y), (int)floorf(c.z), cbx, cgp), t, tb[s][i], wp[s][i]);
+                }
+        }
+        // addresses: a workgroup-uniform base (frame, slice 2 od, channel 0) + the thread's byte offset in the plane, 32 bits (vol < 2^30) —
+        // one register per thread for all the loads, not a 64-bit pointer each
+        const size_t in0 = (size_t)b * C * vol + (size_t)(2 * od) * HW;
+        const float *xb = p.x + in0, *rb = p.residual + in0;
+        const unsigned toff = (unsigned)(h * W + w) * 4u;
+        float *ob = p.y + ((size_t)b * C * oD + od) * (oH * oW);
+        const unsigned ooff = (unsigned)(half * oD * (oH * oW) + (h / 2) * oW + w / 2) * 4u;   // (lanes 32-63 store the pair's second channel)
+        // conv2's output (and a residual that is loaded) of a channel pair: two slices x two positions each; asked for a trip ahead, into
+        // the registers the pair before it in the same place of the trip has just left
+        auto load_pair = [&](const float *src, int c, float2 (&yv)[GPW_TRIP][2], int u) {
+#pragma unroll
+            for (int k = 0; k < 2; ++k)
+#pragma unroll
+                for (int s = 0; s < 2; ++s)
+                    yv[u + k][s] = *reinterpret_cast<const float2 *>(reinterpret_cast<const char *>(src + (size_t)(cg0 + c + k) * vol + s * HW) + toff);
+        };
+        // the tap values of a channel pair, per slice: read a pair ahead of their chain (two waves per SIMD do not hide an LDS round trip
+        // per four taps).  The walk's last pair asks for the pair behind its channels: the next part's, or the pitch's two pad floats.
+        k2_f2 pv0[2][8], pv1[2][8];
+        if constexpr (REBUILD) {
+            k2_tap_reads<2>(lds + c_lo, tb[0], pv0);
+            k2_tap_reads<2>(lds + c_lo, tb[1], pv1);
+        }
+        auto do_trip = [&](int cl, int cn, float2 (&yv)[GPW_TRIP][2], float2 (&rv)[GPW_TRIP][2]) {
+            const float *src = lds + cl;   // (the pair's offset in the trip: an immediate of the tap reads)
+#pragma unroll
+            for (int u = 0; u < GPW_TRIP; u += 2) {
+                k2_f2 res[2][2];   // [slice][position] = residual of channels (u, u + 1) of the trip
+                // (asked for ahead of the next pair's tap reads: LDS answers in order, behind them it would wait for all of them)
+                const float4 n2[2] = {chn[cl - c_lo + u], chn[cl - c_lo + u + 1]};
+                if constexpr (REBUILD) {
+                    k2_tap_chain<2>(pv0, wp[0], res[0]);
+                    k2_tap_reads<2>(src + u + 2, tb[0], pv0);
+                    __builtin_amdgcn_sched_barrier(0);
+                    k2_tap_chain<2>(pv1, wp[1], res[1]);
+                    k2_tap_reads<2>(src + u + 2, tb[1], pv1);
+                    __builtin_amdgcn_sched_barrier(0);
+                } else {
+#pragma unroll
+                    for (int k = 0; k < 2; ++k)
+#pragma unroll
+                        for (int s = 0; s < 2; ++s) { res[s][0][k] = rv[u + k][s].x; res[s][1][k] = rv[u + k][s].y; }
+                }
+                float v[2][2][2];   // [channel of the pair][slice][position]
+#pragma unroll
+                for (int k = 0; k < 2; ++k) {
+                    const float4 n = n2[k];
+#pragma unroll
+                    for (int s = 0; s < 2; ++s) {
+                        v[k][s][0] = gn_value(q, yv[u + k][s].x, n.x, n.y, n.z, n.w, 1.0f, 0.0f, false, res[s][0][k], true);
+                        v[k][s][1] = gn_value(q, yv[u + k][s].y, n.x, n.y, n.z, n.w, 1.0f, 0.0f, false, res[s][1][k], true);
+                    }
+                }
+                // lanes 0-31 keep channel u and receive the odd row's values of it, lanes 32-63 the reverse with u + 1
+                float sum = 0.0f;
+#pragma unroll
+                for (int s = 0; s < 2; ++s) {
+                    const auto e0 = __builtin_amdgcn_permlane32_swap(__float_as_uint(v[0][s][0]), __float_as_uint(v[1][s][0]), false, false);
+                    const auto e1 = __builtin_amdgcn_permlane32_swap(__float_as_uint(v[0][s][1]), __float_as_uint(v[1][s][1]), false, false);
+                    sum += __uint_as_float(e0[0]);   // even row, w
+                    sum += __uint_as_float(e1[0]);   // even row, w + 1
+                    sum += __uint_as_float(e0[1]);   // odd row, w
+                    sum += __uint_as_float(e1[1]);   // odd row, w + 1
+                }
+                load_pair(xb, cn + u, yv, u);
+                if constexpr (!REBUILD) load_pair(rb, cn + u, rv, u);
+                const float o = sum / 8.0f;
+                *reinterpret_cast<float *>(reinterpret_cast<char *>(ob + (size_t)(cg0 + cl + u) * oD * (oH * oW)) + ooff) = o;
+                mbits = max(mbits, range_bits(o));
+                __builtin_amdgcn_sched_barrier(0);   // one channel pair at a time (hoisting more of the next pairs' tap reads spills)
+            }
+        };
+        float2 ya[GPW_TRIP][2], ra[GPW_TRIP][2] = {};
+#pragma unroll
+        for (int u = 0; u < GPW_TRIP; u += 2) {
+            load_pair(xb, c_lo + u, ya, u);
+            if constexpr (!REBUILD) load_pair(rb, c_lo + u, ra, u);
+            __builtin_amdgcn_sched_barrier(0);   // (in the walk's order: the compiler's count of loads in flight at the top of a trip is the
+                                                 //  smaller of this path's and the loop's; out of order it drains them all, once per trip)
+        }
+#pragma unroll 1
+        for (int cl = c_lo; cl < c_hi; cl += GPW_TRIP)
+            do_trip(cl, min(cl + GPW_TRIP, c_hi - GPW_TRIP), ya, ra);   // (the last trip asks for itself again: no branch in the walk)
+    };
+    if (c_lo < c_hi) {
+#pragma unroll 1
+        for (int r = 0; r < K2_TH / GPW_ROWS; ++r) {
+            const int h = h0 + r * GPW_ROWS;
+            if (!(h < H && w < W)) break;   // (H even: both rows of a pair, i.e. both halves of the wave, stay or leave; later passes lie lower still)
+            if (rebuild) {
+                if (r + 1 < K2_TH / GPW_ROWS) load_coords(h + GPW_ROWS, cfn);
+                pass(std::true_type{}, h);
+            } else {
+                pass(std::false_type{}, h);
+            }
+#pragma unroll
+            for (int s = 0; s < 2; ++s)
+#pragma unroll
+                for (int i = 0; i < 6; ++i) cf[s][i] = cfn[s][i];
+        }
+    }
+    if (p.range) range_note_block(mbits, p.range, blockIdx.y * gridDim.x + blockIdx.x, gridDim.x * gridDim.y);
 }
 
 // The tiles warp_gather_kernel marked: one position per lane, lanes running along w, so for a smooth field every tap load of
@@ -1006,6 +1172,35 @@ extern "C" int mphip_warp_volume_dsum_typed(const float *v, int shared, const fl
                                             void *workspace, size_t workspace_bytes, void *stream) {
     return warp_volume_dsum_impl("warp_volume_dsum_typed", v, shared ? (size_t)0 : (size_t)C * D * H * W, field, lin_d, lin_h, lin_w, out, out_dtype,
                                  B, C, D, H, W, fD, fH, fW, workspace, workspace_bytes, stream);
+}
+
+// ---- gn_apply_pool_warp_kernel: the pooled GroupNorm apply whose residual is K2's output (the hot-slice plan's first block) ----
+// grid of the launch for a K2 of these dims: workgroups along x, K2's channels per image block, parts per block
+static void gpw_grid(int N, int C, int D, int H, int W, unsigned &gx, int &cg, int &csub) {
+    gx = (unsigned)((size_t)N * (D / 2) * ((H + K2_TH - 1) / K2_TH) * ((W + K2_TW - 1) / K2_TW));
+    cg = k2_group_channels(k2_tiles(N, D, H, W), C);
+    csub = 1;
+    while ((size_t)gx * cdiv(C, cg) * csub < 256 && cg / (2 * csub) >= GPW_TRIP) csub *= 2;   // (a part: at least one trip of the walk)
+}
+bool mphip::gn_apply_pool_warp_ok(int N, int C, int D, int H, int W, int G) {
+    if (N <= 0 || C <= 0 || D <= 0 || H <= 0 || W <= 0 || G <= 0 || C % G != 0) return false;
+    if (C % GPW_TRIP != 0 || D % 2 != 0 || H % 2 != 0 || W % 4 != 0 || (size_t)D * H * W >= (1u << 30)) return false;
+    unsigned gx; int cg, csub;
+    gpw_grid(N, C, D, H, W, gx, cg, csub);
+    return cg % GPW_TRIP == 0 && (size_t)gx * cdiv(C, cg) * csub <= RANGE_MAX_PARTS;
+}
+int mphip::gn_apply_pool_warp_launch(const float *x, const float *stats, const float *gamma, const float *beta, const float *residual, float *y, float *out_range, const float *coords, const int *todo, const float *img,
+                                     int N, int C, int D, int H, int W, int G, hipStream_t s) {
+    MPHIP_REQUIRE(x && stats && gamma && beta && residual && y && coords && todo && img, "groupnorm_apply(warp residual): null pointer");
+    MPHIP_REQUIRE(gn_apply_pool_warp_ok(N, C, D, H, W, G), "groupnorm_apply(warp residual): unsupported dims");
+    MPHIP_REQUIRE((((uintptr_t)x | (uintptr_t)residual | (uintptr_t)coords) & 7) == 0 && ((uintptr_t)img & 15) == 0,
+                  "groupnorm_apply(warp residual): misaligned pointer");
+    unsigned gx; int cg, csub;
+    gpw_grid(N, C, D, H, W, gx, cg, csub);
+    GnParams p{x, stats, gamma, beta, nullptr, nullptr, residual, y, C, C / G, 1, 0, out_range};
+    hipLaunchKernelGGL(gn_apply_pool_warp_kernel, dim3(gx, (unsigned)(cdiv(C, cg) * csub)), dim3(GPW_THREADS), 0, s, p, coords, todo, img, D, H, W, cg,
+                       csub);
+    return check_launch("groupnorm_apply(warp residual)");
 }
 
 extern "C" int mphip_warp_coords(const float *field, const float *lin_d, const float *lin_h, const float *lin_w, float *coords,
