@@ -41,7 +41,7 @@ extern "C" {
 
 /* ABI version of this header.  Bumped whenever an exported signature or a packed layout changes; mphip_version() returns the
  * value the LIBRARY was built with — compare the two after dlopen (the ctypes binding does, and refuses a mismatch). */
-#define MPHIP_ABI_VERSION 25
+#define MPHIP_ABI_VERSION 26
 int mphip_version(void);
 /* hipGraph hygiene (ABI 13).  On ROCm 7.x a MEMSET node of a captured hipGraph is not reliably ordered with its neighbouring kernel nodes
  * (observed twice: stale f16x3 pack headers, r03; a training step's loss that kept its previous value, r04-r05 — ATen's multi-block
@@ -125,8 +125,8 @@ int mphip_warp_volume_dsum_shared(const float *v, const float *field, const floa
  * x [N,Ci,D,H,W] fp32 -> y [N,Co,D,H,W] fp32 in both precisions.
  * precision 0: exact fp32 (v_mfma_f32_32x32x2_f32, bitwise an fmaf chain), any shape.
  * precision 1: "f16x3" — operands split into two f16 halves, 3 f16 MFMAs per product, fp32
- *              accumulate (~2^-21 relative per term, fp32 class, for tensors of ANY magnitude: every
- *              operand tensor is scaled by its own power of two, see "Range descriptors").  Only for
+ *              accumulate (~2^-21 relative per term, fp32 class, for tensors with 2^-107 <= max|x| <= FLT_MAX: every
+ *              operand tensor is scaled by its own power of two, exponent clamped to +-120, see "Range descriptors").  Only for
  *              k=3, Ci%16==0, Co%96==0, H%8==0, W%8==0, D%2==0: ask mphip_conv3d_supported().
  *
  * Range descriptors (precision 1).  x_range = MPHIP_RANGE_FLOATS floats on the device describing the magnitude of x:
@@ -302,13 +302,19 @@ int mphip_add_matmul(const float *a, const float *a2, const float *m, const floa
  * Gradients of the G3d building blocks as torch.autograd computes them for the reference's modules.
  * grad_prep:         one pass over a conv's output gradient dy [N,C,S]: dbias[c] = sum dy (may be NULL) and
  *                    scale[0..2] = (s, 1/s, max|dy|), s = the power of two with max|dy|*s in [2^13, 2^14) — the f16x3 kernels'
- *                    operand scale for this tensor (scale: 4 floats of device memory).
+ *                    operand scale for this tensor (scale: 4 floats of device memory).  The rule is the activations' ("Range
+ *                    descriptors"): the exponent of s is clamped to +-120, so s and 1/s are finite and nonzero for every finite
+ *                    max|dy|.  Supported magnitudes: 2^-107 <= max|dy| <= FLT_MAX keeps max|dy|*s in [2^13, 2^14) (fp32-class
+ *                    results); below 2^-107 s stays 2^120 and the operands lose low bits gradually, never to Inf or NaN
+ *                    (down to 2^-126 they still carry >= 18 bits below the maximum).  An all-zero or non-finite dy gets s = 1,
+ *                    and Inf / NaN propagate.  dy not 16-byte aligned (or S % 4 != 0) is read with scalar loads.
  * conv3d_bwd_data:   dx = conv(dy, Wt), Wt[ci][co][a][b][c] = W[co][ci][k-1-a][k-1-b][k-1-c]; same kernels as
  *                    mphip_conv3d_fwd (Ci/Co = channels of dy/dx).  mphip_pack_conv_weight_bwd_data packs Wt straight
  *                    from the original OIDHW weight W (its Co/Ci = Wt's: the original conv's Ci/Co); `_like` reuses the scale header
  *                    of W's own f16x3 forward pack instead of scanning W again.
  * conv3d_bwd_weight: dW[co][ci][tap] = sum_{n,v} dY[n][co][v] * X[n][ci][v+tap]  (nn.Conv3d model.py:505-510, 591).
- *                    precision 0: exact fp32 MFMA, any shape, k in {1,3}; precision 1: f16x3 (k=3: W%8==0; k=1: D*H*W%128==0).
+ *                    precision 0: exact fp32 MFMA, any shape, k in {1,3}; precision 1: f16x3 (k=3: W%8==0; k=1: D*H*W%128==0),
+ *                    x and dy 16-byte aligned (else MPHIP_EINVAL: use precision 0, which takes any alignment).
  *                    Split over voxels, deterministic slab reduce.
  * groupnorm_bwd_reduce / _apply: nn.GroupNorm (+ residual + ReLU) backward (model.py:506-523).  reduce computes
  *                    s1[n][c] = sum du, s2[n][c] = sum du*xhat (du = dy*(y>0) when relu) and folds them into
@@ -786,6 +792,13 @@ int mphip_debug_conv3d_f32_plan(int N, int Ci, int Co, int D, int H, int W, int 
  * dW element, 1 = the small-map MFMA kernel, 2 = one wave per (co, ci) pair, 3 = the LDS-tiled MFMA kernel, whose `splits` slabs a second
  * launch reduces.  MPHIP_BWD_WEIGHT_WAVE in the environment turns 1 into 2.  Returns 1, or 0 with out zeroed for a bad shape.  Host only. */
 int mphip_debug_conv3d_bwd_weight_f32_kernel(int N, int Ci, int Co, int D, int H, int W, int k, int dy_aligned, int out[2]);
+
+/* (ABI 26) Tests only: what mphip_conv3d_bwd_weight does at precision 1 for this shape.  out = { kernel, splits, voxel tiles per split,
+ * voxel tiles }; kernel: 1 = the 3x3x3 f16x3 kernel ((2,8,8)-voxel tiles), 2 = the 1x1x1 f16x3 kernel (128-voxel tiles), 0 (rest zero) =
+ * precision 1 does not reach them: the shape is unsupported at precision 1, or it is a tiny volume, which the exact kernels serve at both
+ * precisions.  `splits` slabs are folded in order by a second launch; the last split may hold fewer tiles.  It is the launcher's own
+ * decision (one function).  Returns 1, or 0 with out zeroed for a shape the library refuses.  Host only: no GPU is touched.            */
+int mphip_debug_conv3d_bwd_weight_f16x3_plan(int N, int Ci, int Co, int D, int H, int W, int k, int out[4]);
 
 /* Measurement only (tools/mfma_sol.py, bench.py `roofline.sustained_peak`): the f16x3 convs' MFMA stream and nothing else — three
  * v_mfma_f32_32x32x16_f16 per product on random hi/lo fragments, 3 x 2 accumulator tiles per wave, 8 waves per workgroup; mode 1 reads

@@ -813,6 +813,22 @@ extern "C" int mphip_debug_conv3d_bwd_weight_f32_kernel(int N, int Ci, int Co, i
     return 1;
 }
 
+// (tests only) what a precision-1 launch of this shape does: out = {kernel, splits, tiles per split, tiles}, the launcher's own
+// bwd_weight_f16x3_plan; kernel 0 (and the rest zero) where precision 1 never reaches the f16x3 kernels: an unsupported shape, or a
+// tiny volume (bwd_weight_direct), which the exact kernels above serve at both precisions.  Returns 1, or 0 for a bad shape.  Host only.
+extern "C" int mphip_debug_conv3d_bwd_weight_f16x3_plan(int N, int Ci, int Co, int D, int H, int W, int k, int out[4]) {
+    if (!out) return 0;
+    out[0] = out[1] = out[2] = out[3] = 0;
+    if (!mphip_conv3d_bwd_weight_supported(N, Ci, Co, D, H, W, k, 0)) return 0;
+    if (!mphip_conv3d_bwd_weight_supported(N, Ci, Co, D, H, W, k, 1) || bwd_weight_direct(N, D, H, W)) return 1;
+    const BwdWeightF16x3Plan p = bwd_weight_f16x3_plan(N, Ci, Co, D, H, W, k);
+    out[0] = p.kernel;
+    out[1] = p.splits;
+    out[2] = p.tps;
+    out[3] = p.ntiles;
+    return 1;
+}
+
 static int bwd_weight_impl(const float *x, const float *x_range, const float *dy, const float *dy_scale, float *dw, int N, int Ci, int Co, int D,
                            int H, int W, int k, int precision, void *workspace, size_t workspace_bytes, void *stream, const int *dy_boxes);
 
@@ -838,6 +854,9 @@ static int bwd_weight_impl(const float *x, const float *x_range, const float *dy
     MPHIP_REQUIRE(mphip_conv3d_bwd_weight_supported(N, Ci, Co, D, H, W, k, precision),
                   "conv3d_bwd_weight: precision %d not available for this shape (query mphip_conv3d_bwd_weight_supported)", precision);
     MPHIP_REQUIRE(precision == 0 || dy_scale, "conv3d_bwd_weight: the f16x3 kernel needs the gradient scale of mphip_grad_prep");
+    // the f16x3 kernels stage x and dy with 16-byte loads (W % 8 == 0 / D*H*W % 128 == 0 keep every row on the base pointer's alignment)
+    MPHIP_REQUIRE(precision == 0 || bwd_weight_direct(N, D, H, W) || ((((uintptr_t)x | (uintptr_t)dy) & 15) == 0),
+                  "conv3d_bwd_weight: the f16x3 kernel needs x and dy 16-byte aligned (use precision 0)");
     const size_t x_bytes = (size_t)N * Ci * D * H * W * sizeof(float);
     MPHIP_REQUIRE(x_bytes < 0x80000000ull, "conv3d_bwd_weight: input exceeds the 2 GiB buffer-addressing limit");
     const size_t need = mphip_conv3d_bwd_weight_workspace_bytes(N, Ci, Co, D, H, W, k, precision);

@@ -399,12 +399,12 @@ slab_reduce_plain_kernel(const float *__restrict__ slabs, float *__restrict__ ou
 // ---- gradient preparation: per-(n,c) plane sums (-> bias gradient) and max|dy| (-> f16 scale) in one pass ----
 constexpr int GP_CHUNK = 8192;  // floats per workgroup
 __global__ void __launch_bounds__(256)
-grad_prep_partial_kernel(const float *__restrict__ dy, float2 *__restrict__ partial, int S, int chunks) {
+grad_prep_partial_kernel(const float *__restrict__ dy, float2 *__restrict__ partial, int S, int chunks, int vec) {
     const int plane = blockIdx.x / chunks, chunk = blockIdx.x % chunks;
     const float *p = dy + (size_t)plane * S;
     const int begin = chunk * GP_CHUNK, end = min(S, begin + GP_CHUNK);
     float s = 0.0f, m = 0.0f;
-    if ((S & 3) == 0) {
+    if (vec) {   // S % 4 == 0 and dy 16-byte aligned (the host's rule): every plane and chunk starts on a 16-byte boundary
         for (int i = begin + threadIdx.x * 4; i < end; i += 1024) {
             const float4 v = *reinterpret_cast<const float4 *>(p + i);
             s += (v.x + v.y) + (v.z + v.w);
@@ -451,14 +451,12 @@ grad_prep_finalize_kernel(const float2 *__restrict__ partial, float *__restrict_
         __syncthreads();
         m = fmaxf(fmaxf(redm[0], redm[1]), fmaxf(redm[2], redm[3]));
         if (threadIdx.x == 0) {
-        float sc = 1.0f;
-        if (m > 0.0f && m < 1e30f) {
-            int e;
-            frexpf(m, &e);             // m < 2^e
-            sc = ldexpf(1.0f, 14 - e);  // m * sc < 2^14
-        }
+        // the activations' rule (scale_from_bits: the exponent clamped to +-120, every finite maximum accepted), so gradients from
+        // 2^-126 up to the largest finite fp32 get a finite, nonzero power of two and its exact inverse; Inf inside: unit scale
+        float sc, inv;
+        scale_from_bits(range_bits(m), sc, inv);
         scale[0] = sc;
-        scale[1] = 1.0f / sc;
+        scale[1] = inv;
         scale[2] = m;
         }
     }
@@ -484,64 +482,55 @@ slab_reduce_f16x3_kernel(const float *__restrict__ slabs, float *__restrict__ ou
     for (size_t i = threadIdx.x; i < n_here; i += 256) out[cc0 * 27 + i] = tile[i];
 }
 
-static void bwf_plan(int N, int Ci, int Co, int D, int H, int W, int &splits, int &tps) {
-    const long ntiles = (long)N * ((D + 1) / 2) * ((H + 7) / 8) * (W / 8);
-    const int bxy = ((Ci + 31) / 32) * ((Co + 95) / 96);
-    long sp = bxy >= 256 ? 1 : 256 / bxy;           // one workgroup per CU (114 KB of LDS each): fill the chip once
-    if (sp > ntiles) sp = ntiles;
-    if (sp < 1) sp = 1;
-    tps = (int)((ntiles + sp - 1) / sp);
-    splits = (int)((ntiles + tps - 1) / tps);
-}
-
-static void bwf_k1_plan(int N, int Ci, int Co, int DHW, int &splits, int &tps) {
-    const long ntiles = (long)N * (DHW / 128);
-    const int bxy = ((Ci + 95) / 96) * ((Co + 95) / 96);
-    long sp = bxy >= 256 ? 1 : 256 / bxy;
-    if (sp > ntiles) sp = ntiles;
-    if (sp < 1) sp = 1;
-    tps = (int)((ntiles + sp - 1) / sp);
-    splits = (int)((ntiles + tps - 1) / tps);
-}
-
 bool bwd_weight_f16x3_supported(int N, int Ci, int Co, int D, int H, int W, int k) {
     if (N <= 0 || Ci <= 0 || Co <= 0 || D <= 0 || H <= 0 || W <= 0) return false;
     if (k == 1) return ((long)D * H * W) % 128 == 0;
     return k == 3 && W % 8 == 0;
 }
 
+// voxel tiles, (ci, co) blocks and the split over voxels of both kernels: one workgroup per CU (114 KB of LDS each), fill the chip once
+BwdWeightF16x3Plan bwd_weight_f16x3_plan(int N, int Ci, int Co, int D, int H, int W, int k) {
+    BwdWeightF16x3Plan p = {0, 0, 0, 0, 0};
+    if (!bwd_weight_f16x3_supported(N, Ci, Co, D, H, W, k)) return p;
+    const long ntiles = k == 1 ? (long)N * (((long)D * H * W) / 128) : (long)N * ((D + 1) / 2) * ((H + 7) / 8) * (W / 8);
+    p.bxy = ((Ci + (k == 1 ? 95 : 31)) / (k == 1 ? 96 : 32)) * ((Co + 95) / 96);
+    long sp = p.bxy >= 256 ? 1 : 256 / p.bxy;
+    if (sp > ntiles) sp = ntiles;
+    if (sp < 1) sp = 1;
+    p.kernel = k == 1 ? 2 : 1;
+    p.ntiles = (int)ntiles;
+    p.tps = (int)((ntiles + sp - 1) / sp);
+    p.splits = (int)((ntiles + p.tps - 1) / p.tps);
+    return p;
+}
+
 size_t bwd_weight_f16x3_ws_bytes(int N, int Ci, int Co, int D, int H, int W, int k) {
-    int splits, tps;
-    if (k == 1) {
-        bwf_k1_plan(N, Ci, Co, D * H * W, splits, tps);
-        return (size_t)splits * Co * Ci * sizeof(float);
-    }
-    bwf_plan(N, Ci, Co, D, H, W, splits, tps);
-    return (size_t)splits * Co * Ci * 27 * sizeof(float);
+    return (size_t)bwd_weight_f16x3_plan(N, Ci, Co, D, H, W, k).splits * Co * Ci * k * k * k * sizeof(float);
 }
 
 int bwd_weight_f16x3_launch(const float *x, const float *x_range, const float *dy, const float *dy_scale, float *dw, int N, int Ci,
                             int Co, int D, int H, int W, int k, void *workspace, hipStream_t s, const int *dy_boxes) {
-    int splits, tps;
-    if (k == 1) {
-        bwf_k1_plan(N, Ci, Co, D * H * W, splits, tps);
-        dim3 grid(((Ci + 95) / 96) * ((Co + 95) / 96), 1, splits);
+    const BwdWeightF16x3Plan p = bwd_weight_f16x3_plan(N, Ci, Co, D, H, W, k);
+    const dim3 grid(p.bxy, 1, p.splits);
+    if (p.kernel == 2) {
         hipLaunchKernelGGL(conv_bwd_weight_k1_f16x3_kernel, grid, dim3(512), 0, s, x, dy, dy_scale, x_range, (float *)workspace, N, Ci, Co,
-                           D * H * W, tps);
+                           D * H * W, p.tps);
         const size_t nw = (size_t)Co * Ci;
-        hipLaunchKernelGGL(slab_reduce_plain_kernel, dim3(cdiv(nw, 256)), dim3(256), 0, s, (const float *)workspace, dw, nw, splits);
+        hipLaunchKernelGGL(slab_reduce_plain_kernel, dim3(cdiv(nw, 256)), dim3(256), 0, s, (const float *)workspace, dw, nw, p.splits);
         return check_launch("conv3d_bwd_weight(f16x3, k=1)");
     }
-    bwf_plan(N, Ci, Co, D, H, W, splits, tps);
-    dim3 grid(((Ci + 31) / 32) * ((Co + 95) / 96), 1, splits);
+    if (p.kernel != 1) {
+        set_error("conv3d_bwd_weight(f16x3): unsupported shape");
+        return MPHIP_EINVAL;
+    }
     if (conv_half_products())   // the calling thread's autocast policy
         hipLaunchKernelGGL(conv_bwd_weight_f16x3_kernel<true>, grid, dim3(512), 0, s, x, dy, dy_scale, x_range, (float *)workspace, N, Ci, Co, D,
-                           H, W, tps, dy_boxes);
+                           H, W, p.tps, dy_boxes);
     else
         hipLaunchKernelGGL(conv_bwd_weight_f16x3_kernel<false>, grid, dim3(512), 0, s, x, dy, dy_scale, x_range, (float *)workspace, N, Ci, Co, D,
-                           H, W, tps, dy_boxes);
+                           H, W, p.tps, dy_boxes);
     const size_t ncc = (size_t)Co * Ci;
-    hipLaunchKernelGGL(slab_reduce_f16x3_kernel, dim3(cdiv(ncc, 64)), dim3(256), 0, s, (const float *)workspace, dw, ncc, splits);
+    hipLaunchKernelGGL(slab_reduce_f16x3_kernel, dim3(cdiv(ncc, 64)), dim3(256), 0, s, (const float *)workspace, dw, ncc, p.splits);
     return check_launch("conv3d_bwd_weight(f16x3)");
 }
 
@@ -563,7 +552,8 @@ extern "C" int mphip_grad_prep(const float *dy, float *dbias, float *scale, int 
         return MPHIP_EWORKSPACE;
     }
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(grad_prep_partial_kernel, dim3(N * C * chunks), dim3(256), 0, s, dy, (float2 *)workspace, S, chunks);
+    const int vec = (S & 3) == 0 && ((uintptr_t)dy & 15) == 0;   // 16-byte loads only from 16-byte aligned planes, else the scalar loop
+    hipLaunchKernelGGL(grad_prep_partial_kernel, dim3(N * C * chunks), dim3(256), 0, s, dy, (float2 *)workspace, S, chunks, vec);
     hipLaunchKernelGGL(grad_prep_finalize_kernel, dim3(cdiv(C, 256)), dim3(256), 0, s, (const float2 *)workspace, scale, dbias, N,
                        C, chunks);
     return check_launch("grad_prep");

@@ -72,8 +72,10 @@ inline void zero_fill(void *p, size_t n_bytes, hipStream_t s) {
 // store — no atomics (same-address atomics serialise in one L2 channel: measured +0.27 ms per step), no zero-fill, no
 // finalize launch; the consuming conv kernel folds the <= 4096 partials in its prologue (16 KB from L2, once per
 // workgroup).  The f16x3 kernels scale every operand by the result before the hi/lo split, so no finite value can leave
-// the f16 range (the reference's fp32 conv has no range cliff either) and tensors of any magnitude keep fp32-class
-// accuracy; non-finite values are passed through by the split and propagate as Inf/NaN.
+// the f16 range (the reference's fp32 conv has no range cliff either) and tensors with 2^-107 <= max <= FLT_MAX keep fp32-class
+// accuracy (scale_from_bits clamps the exponent to +-120: below 2^-107 low bits are lost gradually, the scale and its inverse stay
+// finite); non-finite values are passed through by the split and propagate as Inf/NaN.  Gradients follow the same rule
+// (grad_prep_finalize_kernel calls scale_from_bits).
 constexpr unsigned RANGE_MAX_PARTS = MPHIP_RANGE_FLOATS - 4;
 
 __device__ __forceinline__ unsigned range_bits(float v) { return __float_as_uint(fabsf(v)); }  // NaN sorts above Inf above finite

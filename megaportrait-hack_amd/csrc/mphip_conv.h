@@ -270,6 +270,15 @@ bool conv_half_products();
 
 // conv3d_bwd_f16x3.hip: 3x3x3 backward-weight on the f16 matrix cores (split precision)
 bool bwd_weight_f16x3_supported(int N, int Ci, int Co, int D, int H, int W, int k);
+// the one decision of a launch: the launcher, the workspace size and mphip_debug_conv3d_bwd_weight_f16x3_plan all read it
+struct BwdWeightF16x3Plan {
+    int kernel;   // 0 = the shape is not supported, 1 = the 3x3x3 kernel, 2 = the 1x1x1 kernel
+    int splits;   // slabs = grid z; the slab reduce folds them in order
+    int tps;      // voxel tiles per split (the last split may hold fewer)
+    int ntiles;   // voxel tiles of the launch: N x (2,8,8) tiles (k = 3), N x 128-voxel tiles (k = 1)
+    int bxy;      // (ci, co) blocks = grid x
+};
+BwdWeightF16x3Plan bwd_weight_f16x3_plan(int N, int Ci, int Co, int D, int H, int W, int k);
 size_t bwd_weight_f16x3_ws_bytes(int N, int Ci, int Co, int D, int H, int W, int k);
 int bwd_weight_f16x3_launch(const float *x, const float *x_range, const float *dy, const float *dy_scale, float *dw, int N, int Ci,
                             int Co, int D, int H, int W, int k, void *workspace, hipStream_t s, const int *dy_boxes = nullptr);

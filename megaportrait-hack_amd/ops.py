@@ -89,7 +89,8 @@ def cast_from_f32(x: torch.Tensor, dtype: torch.dtype) -> torch.Tensor:
 
 # ------------------------------------------------------------------ range descriptors (f16x3 operand scales)
 # include/mphip.h "Range descriptors": a small device buffer per tensor; the f16x3 conv kernels scale their input by the
-# power of two it implies, so activations of any magnitude keep fp32-class accuracy and nothing is ever clamped.  Kernels
+# power of two it implies, so activations (and gradients: grad_prep, the same rule) with 2^-107 <= max <= FLT_MAX keep fp32-class accuracy
+# and no value is ever clamped (the scale's exponent is, at +-120: smaller tensors lose low bits gradually, never to Inf or NaN).  Kernels
 # that already stream a tensor (warp gather, GroupNorm apply) fill the descriptor of their output for free; it rides on the
 # torch.Tensor object as an attribute, guarded by the tensor's version counter (an in-place write invalidates it).
 _RANGE_FLOATS = 4100  # MPHIP_RANGE_FLOATS (include/mphip.h): 4 + one partial maximum per producing workgroup
@@ -1131,8 +1132,9 @@ def conv3d_bwd_weight(x: torch.Tensor, dy: torch.Tensor, k: int, dy_scale: Optio
         raise RuntimeError(f"conv3d_bwd_weight: dy {tuple(dy.shape)} does not match x {tuple(x.shape)}")
     lib = _lib.load()
     prec = _default_precision if precision is None else precision
-    if prec != 0 and (dy_scale is None or not lib.mphip_conv3d_bwd_weight_supported(n, ci, co, d, h, w, k, prec)):
-        prec = 0  # the exact fp32 kernel covers every shape
+    if prec != 0 and (dy_scale is None or not lib.mphip_conv3d_bwd_weight_supported(n, ci, co, d, h, w, k, prec)
+                      or (x.data_ptr() | dy.data_ptr()) & 15):   # (the f16x3 kernels' 16-byte loads: the C entry refuses such pointers)
+        prec = 0  # the exact fp32 kernel covers every shape and any alignment
     ws_bytes = lib.mphip_conv3d_bwd_weight_workspace_bytes(n, ci, co, d, h, w, k, prec)
     if ws_bytes == 0:
         raise RuntimeError(f"conv3d_bwd_weight: unsupported shape {tuple(x.shape)} k={k}")

@@ -48,7 +48,7 @@ def test_library_exports_the_entries_inside_abi_25():
     lib = _lib.load()
     for name in ENTRIES:
         assert name in _lib.SIGNATURES and getattr(lib, name) is not None
-    assert lib.mphip_version() == _lib.EXPECTED_ABI_VERSION == _lib.header_abi_version() == 25
+    assert lib.mphip_version() == _lib.EXPECTED_ABI_VERSION == _lib.header_abi_version() >= 25
     header = open(os.path.join(ROOT, "include", "mphip.h")).read()
     assert all(name + "(" in header for name in ENTRIES)
     assert "added within ABI 25" in header and "probes for these entries" in header

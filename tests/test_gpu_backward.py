@@ -51,7 +51,8 @@ def rel_err(got, want):
 @pytest.mark.parametrize("shape", [
     (2, 96, 96, 4, 16, 16, 3),     # G3d L0-like
     (1, 96, 192, 2, 8, 8, 3),      # channel-changing block
-    (2, 40, 72, 3, 12, 20, 3),     # ragged channels (not multiples of 32 / 96) and H, W not multiples of 8
+    (2, 40, 72, 3, 12, 20, 3),     # ragged channels, H and W not multiples of 8: W = 20 keeps precision 1 off the f16x3 kernel (the fp32 one
+                                   # runs twice); the f16x3 kernels' ragged cases are in test_gpu_bwd_weight_f16x3_branches.py
     (1, 192, 96, 4, 8, 8, 1),      # 1x1x1 shortcut
     (3, 768, 384, 2, 4, 4, 3),     # deepest level of the 256px configuration (4x4 maps)
     (4, 64, 40, 4, 1, 1, 3),       # FlowField's first block (4x1x1 maps): the small-map MFMA kernel, one 8-voxel group per sample
@@ -60,8 +61,9 @@ def rel_err(got, want):
 ])
 @pytest.mark.parametrize("dy_mag", [1.0, 3e-8, 5e4])
 def test_conv3d_bwd_weight(dev, ops, shape, dy_mag):
-    """Both arithmetic paths (exact fp32 MFMA; f16x3 where its tiling applies) for gradients of any magnitude:
-    the f16x3 kernels scale dy by its own power of two (grad_prep), so 1e-8-sized gradients keep fp32-class accuracy."""
+    """Both arithmetic paths (exact fp32 MFMA; f16x3 where its tiling applies) for gradients of three magnitudes:
+    the f16x3 kernels scale dy by its own power of two (grad_prep), so 1e-8-sized gradients keep fp32-class accuracy.  (The supported
+    range, 2^-107 <= max|dy| <= FLT_MAX at full accuracy, is swept in tests/test_gpu_bwd_weight_f16x3_branches.py.)"""
     n, ci, co, d, h, w, k = shape
     x = R.seeded_tensor((n, ci, d, h, w), 11, scale=1.5)
     dy = R.seeded_tensor((n, co, d, h, w), 12) * dy_mag

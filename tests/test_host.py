@@ -78,6 +78,22 @@ def test_argument_validation_needs_no_gpu(lib):
     assert lib.mphip_groupnorm_workspace_bytes(2, 96, 65536, 32) == 2 * 32 * 12 * 16
     assert lib.mphip_warp_workspace_bytes(8, 16, 64, 64) == 8 * 65536 * 12 + 8 * 16 * 2 * 4   # coordinates + one int per 32x64 K2 tile
     assert lib.mphip_warp_corner_image_bytes(8, 96) == 8 * 6 * 216 * 18 * 4                # K2's optional corner image: [frame][group][6^3][channels + 2], largest grouping (6 x 16 channels)
+    # conv3d_bwd_weight(x, x_range, dy, dy_scale, dw, N, Ci, Co, D, H, W, k, precision, workspace, bytes, stream): the f16x3 kernels stage x
+    # and dy with 16-byte loads, so precision 1 refuses a pointer off that alignment before any launch; tiny volumes take the exact kernels
+    # at both precisions and precision 0 takes any alignment (neither is refused here: they would launch)
+    off = ctypes.c_void_p(20)
+    for k, vol in ((3, (2, 8, 16)), (1, (2, 8, 8))):
+        big = lib.mphip_conv3d_bwd_weight_workspace_bytes(1, 8, 8, *vol, k, 1)
+        assert big > 4100 * 4
+        for xp, dyp in ((off, one), (one, off)):
+            assert lib.mphip_conv3d_bwd_weight(xp, None, dyp, one, one, 1, 8, 8, *vol, k, 1, one, big, None) == -1
+            assert b"16-byte aligned" in lib.mphip_last_error()
+        assert lib.mphip_conv3d_bwd_weight_roi(off, None, one, one, one, one, 1, 8, 8, *vol, k, 1, one, big, None) == -1
+        assert b"16-byte aligned" in lib.mphip_last_error()
+        assert lib.mphip_conv3d_bwd_weight(off, None, one, one, one, 1, 8, 8, *vol, k, 1, one, big - 1, None) == -1    # (before the workspace check)
+        assert lib.mphip_conv3d_bwd_weight(one, None, one, one, one, 1, 8, 8, *vol, k, 1, one, big - 1, None) == -3
+    assert lib.mphip_conv3d_bwd_weight(one, None, one, None, one, 1, 8, 8, 2, 8, 16, 3, 1, one, 1 << 30, None) == -1
+    assert b"gradient scale" in lib.mphip_last_error()
     one_ = ctypes.c_void_p(16)
     assert lib.mphip_warp_volume_dsum(one_, one_, one_, one_, one_, one_, 1, 2, 4, 4, 4, 4, 4, 4, None, 0, None) == -3   # workspace too small
 
@@ -467,7 +483,7 @@ NOT_OPERATIONS = [
     "mphip_hot_slice_plan_create", "mphip_hot_slice_plan_set_tables", "mphip_hot_slice_plan_set_precision", "mphip_hot_slice_plan_profile",
     "mphip_hot_slice_plan_profile_read", "mphip_hot_slice_plan_refresh",
     "mphip_debug_conv3d_plan", "mphip_debug_mfma_sol", "mphip_debug_dma_stream",
-    "mphip_debug_conv3d_f32_plan", "mphip_debug_conv3d_bwd_weight_f32_kernel",
+    "mphip_debug_conv3d_f32_plan", "mphip_debug_conv3d_bwd_weight_f32_kernel", "mphip_debug_conv3d_bwd_weight_f16x3_plan",
 ]
 # operation entries that no test file names: entry -> (source file that calls it, the wrapper there, a test that runs the wrapper).
 # "csrc/plan.hip" entries are launched by the C plan only: the wrapper is the plan's forward, the test compares it bitwise with the Python schedule.
@@ -475,8 +491,6 @@ _PLAN = ("megaportrait-hack_amd/csrc/plan.hip", "mphip_hot_slice_forward", "test
 _OPS = "megaportrait-hack_amd/ops.py"
 COVERED_THROUGH_WRAPPER = {
     "mphip_conv3d_bwd_data": (_OPS, "conv3d_bwd_data", "tests/test_gpu_backward.py::test_conv3d_bwd_data"),
-    "mphip_conv3d_bwd_weight": (_OPS, "conv3d_bwd_weight", "tests/test_gpu_backward.py::test_conv3d_bwd_weight"),
-    "mphip_conv3d_bwd_weight_roi": (_OPS, "conv3d_bwd_weight", "tests/test_gpu_plan.py::test_demand_driven_conv_backward_equals_the_full_backward"),
     "mphip_conv3d_fwd_split": (_OPS, "conv3d_split", "tests/test_gpu_parity.py::test_split_aware_groupnorm_chain"),
     "mphip_conv3d_gn_table_fwd": _PLAN,
     "mphip_flowfield_compact_weight": _PLAN,
