@@ -41,7 +41,7 @@ extern "C" {
 
 /* ABI version of this header.  Bumped whenever an exported signature or a packed layout changes; mphip_version() returns the
  * value the LIBRARY was built with — compare the two after dlopen (the ctypes binding does, and refuses a mismatch). */
-#define MPHIP_ABI_VERSION 26
+#define MPHIP_ABI_VERSION 27
 int mphip_version(void);
 /* hipGraph hygiene (ABI 13).  On ROCm 7.x a MEMSET node of a captured hipGraph is not reliably ordered with its neighbouring kernel nodes
  * (observed twice: stale f16x3 pack headers, r03; a training step's loss that kept its previous value, r04-r05 — ATen's multi-block
@@ -799,6 +799,12 @@ int mphip_debug_conv3d_bwd_weight_f32_kernel(int N, int Ci, int Co, int D, int H
  * precisions.  `splits` slabs are folded in order by a second launch; the last split may hold fewer tiles.  It is the launcher's own
  * decision (one function).  Returns 1, or 0 with out zeroed for a shape the library refuses.  Host only: no GPU is touched.            */
 int mphip_debug_conv3d_bwd_weight_f16x3_plan(int N, int Ci, int Co, int D, int H, int W, int k, int out[4]);
+
+/* (ABI 27) Tests only: the launch geometry of a precision-1 1x1x1 conv (mphip_conv3d_fwd / _bwd_data, k = 1) of this shape, as the launchers
+ * read it.  out = { ks: waves that share one tile's input channels (1, 4 or 8), column tiles per wave (1 = 32 voxels, 2 = 64 voxels), grid
+ * x, grid y, workgroup size }.  Returns 1, or 0 with out zeroed where mphip_conv3d_supported(..., 1, 1) is 0 (precision 1 then takes the
+ * exact fp32 kernels).  Host only: no GPU is touched.  No kernel and no existing signature changed.                                   */
+int mphip_debug_conv3d_k1_plan(int N, int Ci, int Co, int D, int H, int W, int out[5]);
 
 /* Measurement only (tools/mfma_sol.py, bench.py `roofline.sustained_peak`): the f16x3 convs' MFMA stream and nothing else — three
  * v_mfma_f32_32x32x16_f16 per product on random hi/lo fragments, 3 x 2 accumulator tiles per wave, 8 waves per workgroup; mode 1 reads

@@ -137,6 +137,7 @@ SIGNATURES = {
     "mphip_debug_conv3d_f32_plan": (_i, [_i] * 7 + [ctypes.POINTER(ctypes.c_int)]),   # (ABI 18)
     "mphip_debug_conv3d_bwd_weight_f32_kernel": (_i, [_i] * 8 + [ctypes.POINTER(ctypes.c_int)]),   # (ABI 18)
     "mphip_debug_conv3d_bwd_weight_f16x3_plan": (_i, [_i] * 7 + [ctypes.POINTER(ctypes.c_int)]),   # (ABI 26)
+    "mphip_debug_conv3d_k1_plan": (_i, [_i] * 6 + [ctypes.POINTER(ctypes.c_int)]),   # (ABI 27)
     # G2d's exit (ABI 17)
     "mphip_g2d_final_workspace_bytes": (_sz, [_i] * 6),
     "mphip_g2d_final_fwd": (_i, [_p, _i, _p, _p, _p, _p, _p, _i, _p] + [_i] * 6 + [ctypes.c_float, _p, _sz, _p]),
@@ -190,7 +191,7 @@ _lib = None
 # The ABI version the SIGNATURES table above mirrors.  Checked against the library at load time, and against include/mphip.h by
 # tests/test_host.py — NOT read from the header at run time: a relocated / installed package ships libmphip.so without the repository's
 # include/ directory.
-EXPECTED_ABI_VERSION = 26
+EXPECTED_ABI_VERSION = 27
 
 
 def header_abi_version() -> int:

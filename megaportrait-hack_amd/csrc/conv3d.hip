@@ -885,6 +885,18 @@ extern "C" int mphip_debug_conv3d_plan(int N, int Ci, int Co, int D, int H, int 
     return 1;
 }
 
+// the launch geometry of a precision-1 1x1x1 conv (f16x3_k1_geometry, which the launchers read): out = {ks: waves sharing a tile, column
+// tiles per wave (1 or 2), grid x, grid y, workgroup size}.  0 (and zeros) when f16x3_supported(..., k = 1) is false.  Tests only; host only.
+extern "C" int mphip_debug_conv3d_k1_plan(int N, int Ci, int Co, int D, int H, int W, int out[5]) {
+    if (!out) return 0;
+    for (int i = 0; i < 5; ++i) out[i] = 0;
+    if (N <= 0 || Ci <= 0 || Co <= 0 || D <= 0 || H <= 0 || W <= 0) return 0;
+    const F16x3Switches sw = f16x3_switches();
+    if (!f16x3_supported(sw, N, Ci, Co, D, H, W, 1)) return 0;
+    f16x3_k1_plan_query(sw, N, Ci, Co, D * H * W, out);
+    return 1;
+}
+
 // the decision plan_conv takes for an exact-fp32 (precision 0) launch of this shape, under the environment as it stands (MPHIP_CONV_GATHER
 // is honoured: this IS plan_conv): out = {tiled (0 = gather kernel, 4 / 2 = conv3d_k3_tiled_kernel<4|2,8,8,3,2>), MT, NT, WCO, skip, splits,
 // channels (gather) or chunks (tiled) per split, grid x, y, z}; a tiled plan reports its kernel's template: MT 3, NT tiled / 2, WCO 1, no

@@ -596,7 +596,8 @@ conv3d_k3_f16x3_body(const float *__restrict__ x, const _Float16 *__restrict__ w
 
     const bool direct = gridDim.z == 1;
     float *dst = direct ? y : y + (size_t)bz * N * Co * DHW;
-    const float unscale = whdr[0] * x_unscale;
+    const float unscale = whdr[0] * x_unscale;   // (the GroupNorm partials' finalize kernel applies this one, in double)
+    const Unscale us{whdr[0], x_unscale};
     const int co0 = cot * F16X3_COT + mb * 32;
     if (gn_part) {
         // GroupNorm statistics of THIS conv's output without a pass over it: per-channel (sum, sum of squares) of the values about to
@@ -662,7 +663,7 @@ conv3d_k3_f16x3_body(const float *__restrict__ x, const _Float16 *__restrict__ w
 #pragma unroll
             for (int reg = 0; reg < 16; ++reg) {
                 const int co = co0 + m * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * kg + tz;
-                dv[(size_t)co * DHW] = acc[m][t][reg] * unscale + bv[reg];
+                dv[(size_t)co * DHW] = unscaled(acc[m][t][reg], us, bv[reg]);
             }
         }
     }
@@ -946,7 +947,7 @@ conv3d_k1_f16x3_kernel(const float *__restrict__ x, const _Float16 *__restrict__
     }
 #undef K1_LOAD
 #undef K1_MFMA
-    const float unscale = whdr[0] * x_unscale;
+    const Unscale us{whdr[0], x_unscale};
     unsigned mbits = 0;   // FIN: this thread's max|out|
     if (KS == 1 && FIN) {
         float yv[2][16][NT];   // y2 of row tile m in yv[m & 1]
@@ -964,7 +965,7 @@ conv3d_k1_f16x3_kernel(const float *__restrict__ x, const _Float16 *__restrict__
                 const float bv = fin_gb[2 * F16X3_COT + c];
                 float res[NT];
 #pragma unroll
-                for (int t = 0; t < NT; ++t) res[t] = acc[m][t][reg] * unscale + bv;
+                for (int t = 0; t < NT; ++t) res[t] = unscaled(acc[m][t][reg], us, bv);
                 mbits = max(mbits, k1_finish<FIN, NT>(fin, yv[m & 1][reg], res, K1_CHANNEL(c), live, plane0 + c, DHW, rl, tfloats, owner, pool_off));
             }
         }
@@ -978,7 +979,7 @@ conv3d_k1_f16x3_kernel(const float *__restrict__ x, const _Float16 *__restrict__
                 const float bv = bias ? bias[co] : 0.0f;
                 float *dv = y + ((size_t)n * Co + co) * DHW + r0 + j;
 #pragma unroll
-                for (int t = 0; t < NT; ++t) dv[t * 32] = acc[m][t][reg] * unscale + bv;
+                for (int t = 0; t < NT; ++t) dv[t * 32] = unscaled(acc[m][t][reg], us, bv);
             }
         }
     } else {
@@ -1016,7 +1017,7 @@ conv3d_k1_f16x3_kernel(const float *__restrict__ x, const _Float16 *__restrict__
                         float sum = red[0][(t * 16 + reg) * 64 + lane];
 #pragma unroll
                         for (int k = 1; k < KS; ++k) sum += red[k][(t * 16 + reg) * 64 + lane];
-                        res[t] = sum * unscale + bv;
+                        res[t] = unscaled(sum, us, bv);
                     }
                     mbits = max(mbits, k1_finish<FIN, NT>(fin, yq[i], res, K1_CHANNEL(c), live, plane0 + c, DHW, rl, tfloats, owner, pool_off));
                 }
@@ -1028,7 +1029,7 @@ conv3d_k1_f16x3_kernel(const float *__restrict__ x, const _Float16 *__restrict__
                     for (int k = 1; k < KS; ++k) sum += red[k][q * 64 + lane];
                     const int co = co0 + m * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * kg;
                     const float bv = bias ? bias[co] : 0.0f;
-                    y[((size_t)n * Co + co) * DHW + r0 + j + t * 32] = sum * unscale + bv;
+                    y[((size_t)n * Co + co) * DHW + r0 + j + t * 32] = unscaled(sum, us, bv);
                 }
             }
             __syncthreads();
@@ -1153,6 +1154,16 @@ static K1Geometry f16x3_k1_geometry(const F16x3Switches &sw, int N, int Ci, int 
     g.grid = dim3((unsigned)(g.ks > 1 ? waves : g.nt1 ? (2 * waves + 3) / 4 : (waves + 3) / 4), Co / F16X3_COT);
     g.block = g.ks > 1 ? 64u * g.ks : 256u;
     return g;
+}
+
+// what a k = 1 launch of this shape reads, for mphip_debug_conv3d_k1_plan: {ks, column tiles per wave, grid x, grid y, workgroup size}
+void f16x3_k1_plan_query(const F16x3Switches &sw, int N, int Ci, int Co, int DHW, int out[5]) {
+    const K1Geometry g = f16x3_k1_geometry(sw, N, Ci, Co, DHW);
+    out[0] = g.ks;
+    out[1] = g.nt1 ? 1 : 2;
+    out[2] = (int)g.grid.x;
+    out[3] = (int)g.grid.y;
+    out[4] = (int)g.block;
 }
 
 template <int FIN>

@@ -251,7 +251,8 @@ conv3d_k3_f16x3_wino_kernel(const float *__restrict__ x, const _Float16 *__restr
 #pragma unroll
     for (int t = 0; t < 2; ++t) bh[0][t] = *reinterpret_cast<const half8 *>(Xs + b_base[t]);
 
-    const float unscale = whdr[0] * x_unscale;
+    const float unscale = whdr[0] * x_unscale;   // (for the GroupNorm partials' finalize kernel)
+    const Unscale us{whdr[0], x_unscale};
     const int co0 = cot * WN_COT;
     const bool direct = gridDim.z == 1;
     WPROF_ADD(0)
@@ -414,7 +415,7 @@ conv3d_k3_f16x3_wino_kernel(const float *__restrict__ x, const _Float16 *__restr
             for (int t = 0; t < 2; ++t) {
                 f32x4 M[4], va, vb;
                 wino_gather_M(p, acc[m][t], Ex, 4 * ch, lane, t, M);
-                wino_out_pair(M, bv, unscale, odd, true, ssum, qsum, va, vb);
+                wino_out_pair(M, bv, us, odd, true, ssum, qsum, va, vb);
                 float *const dq = dsto + (size_t)(co0 + m * 32 + 8 * p + 4 * kgl + (odd ? 2 : 0) + tz) * DHW + (size_t)t * HW;
                 *reinterpret_cast<f32x4 *>(dq) = va;
                 *reinterpret_cast<f32x4 *>(dq + DHW) = vb;

@@ -304,7 +304,8 @@ conv3d_k3_f16x3_wino_bt_kernel(const float *__restrict__ x, const _Float16 *__re
     bt_for<3>([&](auto M) { al[decltype(M)::value] = ld_a(std::integral_constant<int, 0>{}, M, true); });
     bt_for<4>([&](auto T) { bh[decltype(T)::value] = ld_b(std::integral_constant<int, 0>{}, T, false); });
 
-    const float unscale = whdr[0] * x_unscale;
+    const float unscale = whdr[0] * x_unscale;   // (for the GroupNorm partials' finalize kernel)
+    const Unscale us{whdr[0], x_unscale};
     const int co0 = cot * PP_COT;
     const bool direct = gridDim.z == 1;
     int gp = 0;           // period being multiplied
@@ -477,7 +478,7 @@ conv3d_k3_f16x3_wino_bt_kernel(const float *__restrict__ x, const _Float16 *__re
                     for (int tt = 0; tt < 2; ++tt) {
                         f32x4 M[4], va, vb;
                         wino_gather_M(P, acc[m][2 * pair + tt], Ex, 0, lane, tt, M);
-                        wino_out_pair(M, bv, unscale, odd, gn_part != nullptr, ssum, qsum, va, vb);
+                        wino_out_pair(M, bv, us, odd, gn_part != nullptr, ssum, qsum, va, vb);
                         unsigned char *const dq = reinterpret_cast<unsigned char *>(ybase + (size_t)(m * 32 + tz) * DHW + pair * pair_stride + (size_t)tt * HW);   // (uniform)
                         if (pair == 0 || pair1_ok) {
                             *reinterpret_cast<f32x4 *>(dq + yoff) = va;

@@ -359,7 +359,8 @@ conv3d_k3_f16x3_wino_pp_kernel(const float *__restrict__ x, const _Float16 *__re
     lds_barrier();
 
     half8 ah[3], al[3], bh[2], bl[2];
-    const float unscale = whdr[0] * x_unscale;
+    const float unscale = whdr[0] * x_unscale;   // (for the GroupNorm partials' finalize kernel)
+    const Unscale us{whdr[0], x_unscale};
     const int co0 = cot * PP_COT;
     const bool direct = gridDim.z == 1;
     float *const Ex = reinterpret_cast<float *>(smem + (team == 0 ? PP_LDS_EX : PP_LDS_X + PP_XBUF_B));   // [position][slot 0..5][lane][4]
@@ -603,8 +604,8 @@ conv3d_k3_f16x3_wino_pp_kernel(const float *__restrict__ x, const _Float16 *__re
                             qsum[i] = __builtin_fmaf(r0, r0, qsum[i]);
                             qsum[i] = __builtin_fmaf(r1, r1, qsum[i]);
                         }
-                        y0[i] = r0 * unscale + bv[i];
-                        y1[i] = r1 * unscale + bv[i];
+                        y0[i] = unscaled(r0, us, bv[i]);
+                        y1[i] = unscaled(r1, us, bv[i]);
                     }
                     // 16-byte stores: a lane holds one output pair (2 voxels) of 4 channels; lanes 2k / 2k+1 hold neighbouring pairs of a row and
                     // trade halves (quad_perm [1,0,3,2]): the even lane ends up with 4 consecutive voxels of channels 0-1, the odd lane with

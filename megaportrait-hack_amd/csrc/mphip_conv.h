@@ -92,6 +92,7 @@ size_t f16x3_packed_bytes(int Co, int Ci);
 size_t f16x3_packed_bytes_k1(int Co, int Ci);
 int f16x3_launch_k1(const F16x3Switches &sw, const float *x, const void *wpacked, const float *bias, float *dst, int N, int Ci, int Co,
                     int DHW, const float *x_range, hipStream_t s);
+void f16x3_k1_plan_query(const F16x3Switches &sw, int N, int Ci, int Co, int DHW, int out[5]);   // f16x3_k1_geometry, for the debug query
 // the k = 1 launch that finishes its ResBlock3D: relu(GN(y2) + conv(x)) (+ AvgPool3d(2)) and the range descriptor of the result (mphip_gn.h)
 struct GnParams;
 bool f16x3_k1_finish_supported(const F16x3Switches &sw, int N, int Ci, int Co, int D, int H, int W, int groups, int pool2);

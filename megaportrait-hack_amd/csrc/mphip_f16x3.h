@@ -29,6 +29,14 @@ __device__ __forceinline__ float weight_scale(unsigned maxbits) {
     return ldexpf(1.0f, 15 - e);  // m*scale < 2^15 = 32768
 }
 
+// The unscale of an accumulator: 1 / scale_w, then 1 / scale_x, applied one after the other.  Their product can leave the fp32 range although
+// the result does not (max|w| = 2^-28 and max|x| = 2^-98 give 2^-42 * 2^-111 = 2^-153, which is 0 in fp32, for outputs up to 2^-117).  Each
+// step multiplies a value in range by a power of two, so the result carries the bits of the single product wherever that is representable.
+struct Unscale {
+    float w, x;
+};
+__device__ __forceinline__ float unscaled(float acc, Unscale u, float bias) { return (acc * u.w) * u.x + bias; }
+
 // LDS-DMA of 16 bytes per lane (1 KiB per wave): global `src` (per lane) -> LDS byte address `lds` + 16 * lane (wave-uniform
 // `lds`).  Issued as inline assembly ON PURPOSE: hipcc's waitcnt pass cannot prove that a later ds_read does not alias the
 // destination of __builtin_amdgcn_global_load_lds and puts `s_waitcnt vmcnt(0)` in front of the first LDS read that follows

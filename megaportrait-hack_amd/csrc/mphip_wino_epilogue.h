@@ -43,7 +43,7 @@ __device__ __forceinline__ void wino_gather_M(const int P, const f32x16 &a, cons
 // those of channels 2-3 — two dwordx4 stores per lane instead of four dwordx2 (the epilogue is store-ISSUE bound: 8-byte stores of
 // 32-byte row pieces ran at ~7 B/clk/CU, MI355X_MICROARCH.md "epilogue store tail").
 template <class B>
-__device__ __forceinline__ void wino_out_pair(const f32x4 (&M)[4], const B &bv, float unscale, bool odd, bool gn, float (&ssum)[4],
+__device__ __forceinline__ void wino_out_pair(const f32x4 (&M)[4], const B &bv, Unscale us, bool odd, bool gn, float (&ssum)[4],
                                               float (&qsum)[4], f32x4 &va, f32x4 &vb) {
     float y0[4], y1[4];
 #pragma unroll
@@ -55,8 +55,8 @@ __device__ __forceinline__ void wino_out_pair(const f32x4 (&M)[4], const B &bv, 
             qsum[i] = __builtin_fmaf(r0, r0, qsum[i]);
             qsum[i] = __builtin_fmaf(r1, r1, qsum[i]);
         }
-        y0[i] = r0 * unscale + bv[i];
-        y1[i] = r1 * unscale + bv[i];
+        y0[i] = unscaled(r0, us, bv[i]);
+        y1[i] = unscaled(r1, us, bv[i]);
     }
     auto swap = [](float v) { return __uint_as_float(__builtin_amdgcn_update_dpp(0, __float_as_uint(v), 0xB1, 0xf, 0xf, false)); };
     const float g0 = swap(odd ? y0[0] : y0[2]), g1 = swap(odd ? y1[0] : y1[2]);

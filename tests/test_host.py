@@ -483,7 +483,7 @@ NOT_OPERATIONS = [
     "mphip_hot_slice_plan_create", "mphip_hot_slice_plan_set_tables", "mphip_hot_slice_plan_set_precision", "mphip_hot_slice_plan_profile",
     "mphip_hot_slice_plan_profile_read", "mphip_hot_slice_plan_refresh",
     "mphip_debug_conv3d_plan", "mphip_debug_mfma_sol", "mphip_debug_dma_stream",
-    "mphip_debug_conv3d_f32_plan", "mphip_debug_conv3d_bwd_weight_f32_kernel", "mphip_debug_conv3d_bwd_weight_f16x3_plan",
+    "mphip_debug_conv3d_f32_plan", "mphip_debug_conv3d_bwd_weight_f32_kernel", "mphip_debug_conv3d_bwd_weight_f16x3_plan", "mphip_debug_conv3d_k1_plan",
 ]
 # operation entries that no test file names: entry -> (source file that calls it, the wrapper there, a test that runs the wrapper).
 # "csrc/plan.hip" entries are launched by the C plan only: the wrapper is the plan's forward, the test compares it bitwise with the Python schedule.
@@ -491,7 +491,6 @@ _PLAN = ("megaportrait-hack_amd/csrc/plan.hip", "mphip_hot_slice_forward", "test
 _OPS = "megaportrait-hack_amd/ops.py"
 COVERED_THROUGH_WRAPPER = {
     "mphip_conv3d_bwd_data": (_OPS, "conv3d_bwd_data", "tests/test_gpu_backward.py::test_conv3d_bwd_data"),
-    "mphip_conv3d_fwd_split": (_OPS, "conv3d_split", "tests/test_gpu_parity.py::test_split_aware_groupnorm_chain"),
     "mphip_conv3d_gn_table_fwd": _PLAN,
     "mphip_flowfield_compact_weight": _PLAN,
     "mphip_flowfield_conv_gn_compact": _PLAN,
