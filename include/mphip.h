@@ -41,7 +41,7 @@ extern "C" {
 
 /* ABI version of this header.  Bumped whenever an exported signature or a packed layout changes; mphip_version() returns the
  * value the LIBRARY was built with — compare the two after dlopen (the ctypes binding does, and refuses a mismatch). */
-#define MPHIP_ABI_VERSION 27
+#define MPHIP_ABI_VERSION 28
 int mphip_version(void);
 /* hipGraph hygiene (ABI 13).  On ROCm 7.x a MEMSET node of a captured hipGraph is not reliably ordered with its neighbouring kernel nodes
  * (observed twice: stale f16x3 pack headers, r03; a training step's loss that kept its previous value, r04-r05 — ATen's multi-block
@@ -653,6 +653,29 @@ size_t mphip_conv2d_s2_workspace_bytes(int N, int Ci, int Co, int H, int W);
 int mphip_conv2d_s2_fwd(const float *x, const float *x_range, const void *w_packed, const float *bias, const float *residual, float *y,
                         float *out_range, int N, int Ci, int Co, int H, int W, int relu, void *workspace, size_t workspace_bytes,
                         void *stream);
+/* Pointwise (ABI 28; csrc/conv2d_pw_f16x3.hip): nn.Conv2d(Ci, Co, 1, stride=s), s = 1 or 2, with mphip_conv2d_fwd's epilogue, for the 1x1
+ * convs of torchvision-layout ResNet bottlenecks (Eapp's custom_resnet50):
+ *     y[n,co,i,j] = act( sum_ci w[co,ci] * x[n,ci,s*i,s*j] + bias[co] (+ residual[n,co,i,j]) )
+ * x is [N,Ci,H,W]; y and residual are [N,Co,Ho,Wo] with Ho = (H+s-1)/s, Wo = (W+s-1)/s.  H and W in the signatures are the INPUT map's.
+ * At stride 2 the sub-sample is made by the kernel's load addresses: no sub-sampled copy is written.
+ * w_packed is a layout of its own: mphip_pack_conv2d_pw_weight packs w [Co,Ci] (an OIHW [Co,Ci,1,1] weight is the same memory) into a
+ * 16-byte header {1/scale, scale, max|w| bits, -}, the same function of max|w| as mphip_pack_conv2d_weight's, then per (64-channel tile,
+ * 16-channel chunk) a slab [part hi/lo][k group][co 64][8] of f16 (4096 bytes); 16-byte aligned, mphip_conv2d_pw_packed_weight_bytes long.
+ * x_range / out_range / workspace are mphip_conv2d_fwd's, and so is the arithmetic, term by term: with the same x, x_range and bias, and
+ * the pack of a 3x3 weight that is zero but for its centre tap w3[:,:,1,1] = w, this launch writes the bits of mphip_conv2d_fwd (stride
+ * 2: of mphip_conv2d_s2_fwd); and the stride-2 launch writes the bits of the stride-1 launch at the even rows and columns (a residual
+ * being the even sub-sample of that call's).  No floating-point atomics: the bits are reproducible.  fp32 maps and three products only.
+ * Shapes: stride 1 or 2, Ci % 16 == 0, Co % 32 == 0, N, H, W >= 1, N*Ci*H*W and N*Co*Ho*Wo below 2^31 (any other stride is an
+ * unsupported shape).  The call goes through the shared argument check of the entries above, in the same order, with the extents of y
+ * and residual taken from Ho*Wo; messages name conv2d_pw_fwd.  Saturation is counted in the unit's own counter
+ * (mphip_f16x3_saturation_count sums it). */
+int mphip_conv2d_pw_supported(int N, int Ci, int Co, int H, int W, int stride);
+size_t mphip_conv2d_pw_packed_weight_bytes(int Co, int Ci);
+int mphip_pack_conv2d_pw_weight(const float *w, void *w_packed, int Co, int Ci, void *stream);
+size_t mphip_conv2d_pw_workspace_bytes(int N, int Ci, int Co, int H, int W, int stride);
+int mphip_conv2d_pw_fwd(const float *x, const float *x_range, const void *w_packed, const float *bias, const float *residual, float *y,
+                        float *out_range, int N, int Ci, int Co, int H, int W, int stride, int relu, void *workspace,
+                        size_t workspace_bytes, void *stream);
 /* A bilinear x2 up-sample folded in (ABI 23; csrc/conv2d_up2_f16x3.hip), for G2d's three Sequential(nn.Upsample(scale_factor=2,
  * mode="bilinear", align_corners=True), ResBlock2D) stages: the up-sampled map is never written.
  * up2(x) for x [N,C,h,w] is [N,C,2h,2w].  For output row i:  num = i*(h-1), den = 2h-1 (h == 1: num = 0, den = 1),

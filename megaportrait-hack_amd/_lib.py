@@ -160,6 +160,12 @@ SIGNATURES = {
     "mphip_conv2d_s2_supported": (_i, [_i] * 5),
     "mphip_conv2d_s2_workspace_bytes": (_sz, [_i] * 5),
     "mphip_conv2d_s2_fwd": (_i, [_p] * 7 + [_i] * 6 + [_p, _sz, _p]),
+    # the pointwise form (ABI 28, csrc/conv2d_pw_f16x3.hip)
+    "mphip_conv2d_pw_supported": (_i, [_i] * 6),
+    "mphip_conv2d_pw_packed_weight_bytes": (_sz, [_i] * 2),
+    "mphip_pack_conv2d_pw_weight": (_i, [_p, _p, _i, _i, _p]),
+    "mphip_conv2d_pw_workspace_bytes": (_sz, [_i] * 6),
+    "mphip_conv2d_pw_fwd": (_i, [_p] * 7 + [_i] * 7 + [_p, _sz, _p]),
     # a bilinear x2 up-sample folded into the source or the residual (ABI 23, csrc/conv2d_up2_f16x3.hip)
     "mphip_conv2d_up2_supported": (_i, [_i] * 5),
     "mphip_conv2d_up2_workspace_bytes": (_sz, [_i] * 5),
@@ -191,7 +197,7 @@ _lib = None
 # The ABI version the SIGNATURES table above mirrors.  Checked against the library at load time, and against include/mphip.h by
 # tests/test_host.py — NOT read from the header at run time: a relocated / installed package ships libmphip.so without the repository's
 # include/ directory.
-EXPECTED_ABI_VERSION = 27
+EXPECTED_ABI_VERSION = 28
 
 
 def header_abi_version() -> int:

@@ -1,5 +1,6 @@
-// The host side of every 2-D 3x3 conv entry: conv2d_run, the dtype and product rules of the typed entries, and the table of forms that
-// says per C2Form what the entries differ in.  No kernels: each form's kernels, launcher and shape rule live in its own unit.
+// The host side of every 2-D conv entry (the 3x3 forms and the pointwise one): conv2d_run, the dtype and product rules of the typed
+// entries, and the table of forms that says per C2Form what the entries differ in.  No kernels: each form's kernels, launcher and shape
+// rule live in its own unit.
 #include "conv2d_f16x3_tile.h"
 
 namespace mphip {
@@ -55,6 +56,10 @@ static void c2_refuse_groups(const char *who, const C2Call &c) {
     set_error("%s: unsupported shape N=%d Ci=%d Co=%d H=%d W=%d groups=%d (groups >= 1; above 1: Ci and Co multiples of groups, (Ci / groups) "
               "%% 16 == 0, (Co / groups) %% 64 == 0; and the shape rule of conv2d_fwd)", who, c.N, c.C1, c.Co, c.H, c.W, c2_shown(c.groups));
 }
+static void c2_refuse_pw(const char *who, const C2Call &c) {
+    set_error("%s: unsupported shape N=%d Ci=%d Co=%d H=%d W=%d stride=%d (stride 1 or 2, Ci %% 16 == 0, Co %% 32 == 0, N, H, W >= 1, fewer "
+              "than 2^31 elements per tensor)", who, c.N, c.C1, c.Co, c.H, c.W, c.stride);
+}
 static void c2_refuse_splits(const char *who, const C2Call &c) {
     set_error("%s: unsupported shape N=%d Ci=%d Co=%d H=%d W=%d groups=%d splits=%d (the shape rule of conv2d_grouped_fwd; 1 <= splits <= %d, "
               "a divisor of the (Ci / groups) / 16 chunks)", who, c.N, c.C1, c.Co, c.H, c.W, c2_shown(c.groups), c2_shown(c.splits),
@@ -69,10 +74,11 @@ static void c2_typed_launch(const C2Call &c, const C2Grid &g) {
 }
 
 // an extent of y or of the residual from the same extent (H or W) of the call
-static int c2_same(int e) { return e; }
-static int c2_strided(int e) { return (e + 1) / 2; }
-static int c2_doubled(int e) { return 2 * e; }
-static int c2_halved(int e) { return e / 2; }
+static int c2_same(const C2Call &, int e) { return e; }
+static int c2_strided(const C2Call &, int e) { return (e + 1) / 2; }
+static int c2_doubled(const C2Call &, int e) { return 2 * e; }
+static int c2_halved(const C2Call &, int e) { return e / 2; }
+static int c2_by_stride(const C2Call &c, int e) { return (e + c.stride - 1) / c.stride; }   // (after the shape rule: stride is 1 or 2)
 
 // What the forms differ in; conv2d_run looks everything else up here.
 struct C2FormRow {
@@ -82,8 +88,8 @@ struct C2FormRow {
     bool lowres_residual;                               // the residual is required and lives on the halved map: H and W even
     bool (*shape)(const C2Call &);                      // the shape rule ...
     void (*refuse)(const char *who, const C2Call &);    // ... and the message of a call that fails it
-    int (*y_extent)(int), (*residual_extent)(int);
-    int th, tw;                                         // output pixels per workgroup
+    int (*y_extent)(const C2Call &, int), (*residual_extent)(const C2Call &, int);
+    int th, tw;                                         // output pixels per workgroup; th == 0: tw pixels of the FLAT index Ho * Wo
     bool partials;                                      // c.splits > 1: that many partial maps of y's size in the workspace
     void (*launch)(const C2Call &, const C2Grid &);
 };
@@ -102,6 +108,8 @@ static const C2FormRow C2_FORM_TABLE[] = {
                       c2_refuse_groups, c2_same, c2_same, C2_TH, C2_TW, false, conv2d_grouped_launch},
     /* C2_SPLIT   */ {false, nullptr, false, [](const C2Call &c) { return c2_split_supported(c.N, c.C1, c.Co, c.H, c.W, c.groups, c.splits); },
                       c2_refuse_splits, c2_same, c2_same, C2_TH, C2_TW, true, conv2d_split_launch},
+    /* C2_PW      */ {false, nullptr, false, [](const C2Call &c) { return c2_pw_supported(c.N, c.C1, c.Co, c.H, c.W, c.stride); },
+                      c2_refuse_pw, c2_by_stride, c2_by_stride, 0, C2PW_PIX, false, conv2d_pw_launch},
 };
 static_assert(sizeof(C2_FORM_TABLE) / sizeof(C2_FORM_TABLE[0]) == C2_FORMS, "one row per C2Form, in its order");
 
@@ -135,9 +143,9 @@ int conv2d_run(C2Call c) {
     // the bound of a normalised source is not the maximum of its raw values: a scan of x would give the wrong operand scale
     MPHIP_REQUIRE(!c.aff1 || c.x1_range, "%s: affine1 without x1_range (mphip_groupnorm_affine_table makes both)", who);
     MPHIP_REQUIRE(!c.aff2 || (c.x2 && c.x2_range), "%s: affine2 without x2 / x2_range (mphip_groupnorm_affine_table makes both)", who);
-    const int Ho = f.y_extent(c.H), Wo = f.y_extent(c.W);
+    const int Ho = f.y_extent(c, c.H), Wo = f.y_extent(c, c.W);
     const size_t hw = (size_t)c.H * c.W, n1 = (size_t)c.N * c.C1 * hw, n2 = (size_t)c.N * c.C2 * hw, ny = (size_t)c.N * c.Co * Ho * Wo;
-    const size_t nr = (size_t)c.N * c.Co * f.residual_extent(c.H) * f.residual_extent(c.W);
+    const size_t nr = (size_t)c.N * c.Co * f.residual_extent(c, c.H) * f.residual_extent(c, c.W);
     MPHIP_REQUIRE(!c2_overlap(c.y, ny * yb, c.x1, n1 * xb) && !c2_overlap(c.y, ny * yb, c.x2, n2 * sizeof(float)) &&
                       !c2_overlap(c.y, ny * yb, c.residual, nr * rb),
                   "%s: y must not alias a source or residual (a workgroup reads the halo of tiles other workgroups write)", who);
@@ -172,7 +180,8 @@ int conv2d_run(C2Call c) {
             c.x2_range = slot;
         }
     }
-    g.tiles_w = cdiv(Wo, f.tw), g.tiles_h = cdiv(Ho, f.th);
+    if (f.th) g.tiles_w = cdiv(Wo, f.tw), g.tiles_h = cdiv(Ho, f.th);
+    else g.tiles_w = cdiv((long)Ho * Wo, f.tw), g.tiles_h = 1;
     const long long tiles = (long long)c.N * g.tiles_h * g.tiles_w;   // (N * H * W < 2^31 by the shape rule: they fit grid.x)
     g.grid = dim3((unsigned)tiles, (unsigned)c2_cots(c.Co));
     g.nslots = (unsigned)std::min<long long>(g.part ? (long long)c2_split_finish_blocks(ny) : tiles * c2_cots(c.Co), (long long)RANGE_MAX_PARTS);

@@ -184,8 +184,11 @@ int conv2d_up2_saturation(unsigned long long *count, int reset);
 int conv2d_grp_saturation(unsigned long long *count, int reset);
 // conv2d_splitk_f16x3.hip: the split-K form (mphip_conv2d_split_fwd, splits > 1), likewise
 int conv2d_split_saturation(unsigned long long *count, int reset);
+// conv2d_pw_f16x3.hip: the pointwise (1x1) form (mphip_conv2d_pw_fwd), likewise
+int conv2d_pw_saturation(unsigned long long *count, int reset);
 
-// The forms of the 2-D 3x3 conv: what conv2d_run's table (conv2d_run.hip) is indexed by.  One C entry each, the first two a typed one too.
+// The forms of the 2-D conv (3x3 but for the last): what conv2d_run's table (conv2d_run.hip) is indexed by.  One C entry each, the first
+// two a typed one too.
 enum C2Form {
     C2_PLAIN,    // one source; x1, residual and y in their dtypes, one product or three
     C2_CAT,      // the two-source kernels (also with C2 == 0: they are kernels of their own); fp32 sources, typed residual and y
@@ -195,15 +198,18 @@ enum C2Form {
     C2_GROUPED,  // conv2d_grp_f16x3.hip: x1 [N,C1,H,W] in `groups` groups, the pack that of a [Co,C1/groups,3,3] weight; 1: the plain kernel
     C2_SPLIT,    // conv2d_splitk_f16x3.hip: the grouped form with the reduction in `splits` K ranges that leave partial maps in the
                  // workspace, behind the descriptor slot, and a finish launch; 1: the grouped form's launch
+    C2_PW,       // conv2d_pw_f16x3.hip: a 1x1 conv at `stride` 1 or 2 with a pack of its own; y and residual are
+                 // [N,Co,(H+stride-1)/stride,(W+stride-1)/stride]
     C2_FORMS
 };
-// One call of the 2-D 3x3 conv, as its nine C entries describe it to conv2d_run.  Zero-initialised it is the plain fp32 three-product
+// One call of the 2-D conv, as its ten C entries describe it to conv2d_run.  Zero-initialised it is the plain fp32 three-product
 // call: one source (C2 = 0, no tables), fp32 dtypes (MPHIP_DTYPE_F32 == 0); only `products` = 0 asks for the thread's policy.  Every
 // form but the first two is one source, fp32 maps and three products (c2_call_f32).
 struct C2Call {
     const char *who;        // the entry's name, for messages
     C2Form form;
     int groups, splits;     // the caller's counts (C2_GROUPED, C2_SPLIT), as they came: the form's shape rule refuses what is below 1
+    int stride;             // the caller's stride (C2_PW), as it came: the form's shape rule refuses what is neither 1 nor 2
     const void *x1, *x2;    // sources [N,C1,H,W] and [N,C2,H,W] or NULL; x1 in x_dtype (fp32 when C2_CAT), x2 fp32
     const float *aff1, *aff2, *x1_range, *x2_range;
     int relu1, relu2, C1, C2;
@@ -234,7 +240,7 @@ inline C2Call c2_call_f32(const char *who, C2Form form, const void *x, const flo
 }
 struct C2Grid {
     dim3 grid;
-    int tiles_w, tiles_h;
+    int tiles_w, tiles_h;   // (C2_PW: tiles_w tiles of the flat pixel index per image, tiles_h = 1)
     unsigned nslots;        // partial maxima of out_range
     float *part;            // C2_SPLIT with c.splits > 1: c.splits maps of y's size in the workspace; else NULL
 };
@@ -250,9 +256,14 @@ void conv2d_s2_launch(const C2Call &c, const C2Grid &g);      // conv2d_s2_f16x3
 void conv2d_up2_launch(const C2Call &c, const C2Grid &g);     // conv2d_up2_f16x3.hip: conv2d_k3_up2_f16x3_kernel / conv2d_k3_resup2_f16x3_kernel
 void conv2d_grouped_launch(const C2Call &c, const C2Grid &g); // conv2d_grp_f16x3.hip: conv2d_k3_grp_f16x3_kernel; c.groups == 1: the plain launch
 void conv2d_split_launch(const C2Call &c, const C2Grid &g);   // conv2d_splitk_f16x3.hip: its two launches; g.part == NULL: the grouped launch
+void conv2d_pw_launch(const C2Call &c, const C2Grid &g);      // conv2d_pw_f16x3.hip: conv2d_pw_f16x3_kernel; one grid dimension, channel tile fastest
 // conv2d_s2_f16x3.hip: its output tile (64 channels x 8 rows x 16 columns per workgroup) and its shape rule (H, W: the input map)
 constexpr int C2S2_TH = 8, C2S2_TW = 16;
 bool c2_s2_supported(int N, int Ci, int Co, int H, int W);
+// conv2d_pw_f16x3.hip: its tile (64 channels x 256 consecutive output pixels of an image per workgroup) and its shape rule (H, W: the
+// input map; stride 1 or 2)
+constexpr int C2PW_PIX = 256;
+bool c2_pw_supported(int N, int Ci, int Co, int H, int W, int stride);
 // conv2d_up2_f16x3.hip: the shape rule of its up-sampled-source form (h, w: the LOW-resolution input map): c2_supported on [2h, 2w]
 bool c2_up2_supported(int N, int Ci, int Co, int h, int w);
 // conv2d_grp_f16x3.hip: its shape rule: groups >= 1 and c2_supported; groups > 1: Ci and Co multiples of groups, (Ci / groups) % 16 == 0,

@@ -142,6 +142,15 @@ class Eapp(nn.Module):
         M.native_eapp_trunk(self, enable, half_precision)
         return self
 
+    def native_resnet50(self, enable: bool = True) -> "Eapp":
+        """Opt-in, inference only: run the thirteen bottlenecks of `custom_resnet50.layer1..layer3` as model.BottleneckFused —
+        BatchNorm folded, the 1x1 convs on csrc/conv2d_pw_f16x3.hip and the 3x3 convs on csrc/conv2d_f16x3.hip / conv2d_s2_f16x3.hip, three
+        or four matrix-core launches per block with fp32-class accuracy — over the blocks' own children: same Parameter objects, same
+        state-dict keys.  `enable=False` puts the original blocks back.  Under autograd, in train mode or on a half model the fused blocks
+        evaluate the original PyTorch expression.  The 7x7 stride-2 stem, the pools, conv_reduce and fc stay on PyTorch."""
+        M.native_eapp_resnet50(self, enable)
+        return self
+
     def trunk2d(self, x):
         """image [B,3,H,W] -> conv_1 output [B,1536,H/8,W/8] (model.py:248-268)."""
         out = self.avgpool(self.resblock_128(self.conv(x)))

@@ -75,6 +75,13 @@ class Gbase(M._HotSliceRunner, nn.Module):
         M.native_eapp_trunk(self.appearanceEncoder, enable, half_precision)
         return self
 
+    def native_resnet50(self, enable: bool = True) -> "Gbase":
+        """Opt-in, inference only: run the thirteen bottlenecks of the appearance encoder's `custom_resnet50` (the identity descriptor
+        `es`) on the matrix cores (model.native_eapp_resnet50); `enable=False` restores the original blocks.  Same parameters and
+        state-dict keys."""
+        M.native_eapp_resnet50(self.appearanceEncoder, enable)
+        return self
+
     def native_motion_encoder(self, enable: bool = True, fuse_stem: bool = False, rotation_net: bool = False,
                               split_small_maps: bool = False) -> "Gbase":
         """Opt-in (off by default), inference only: the BasicBlocks of the motion encoder's two ResNet-18s (`head_pose_net`,

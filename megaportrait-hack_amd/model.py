@@ -1167,6 +1167,121 @@ class BasicBlockFused(_FusedBlock2D):
         return ops.conv2d(y1, p2, residual=idt, relu=True, want_range=True, **split)
 
 
+class BottleneckFused(_FusedBlock2D):
+    """A torchvision-layout ResNet bottleneck — encoders2d._Bottleneck, torchvision's Bottleneck: 1x1 conv, BatchNorm, ReLU, 3x3 conv (the
+    block's stride is here), BatchNorm, ReLU, 1x1 conv, BatchNorm, add, ReLU; `downsample` is None or Sequential(1x1 conv at conv2's
+    stride, BatchNorm) — with an opt-in inference path on the matrix cores, as BasicBlockFused has it: BatchNorm folded into the
+    (bias-less) convs, every conv one launch with bias, ReLU and the residual add in its epilogue, f16x3 arithmetic (fp32-class accuracy):
+        y1  = conv2d_pw(x,  conv1', relu)
+        y2  = conv2d(y1, conv2', relu)                       stride 2: conv2d_s2
+        idt = x                                              or conv2d_pw(x, downsample', stride = conv2's)
+        out = conv2d_pw(y2, conv3', residual = idt, relu)
+    — three launches, four with a `downsample`.  The 1x1 convs run on csrc/conv2d_pw_f16x3.hip; a stride-2 `downsample` sub-samples in
+    the kernel's loads (no copy of x).  The children are the original block's own `conv1, bn1, conv2, bn2, conv3, bn3, relu, downsample`:
+    the same Parameter and buffer objects, the same state-dict keys.
+
+    The native path runs only in eval mode, without autograd, on an fp32 module and a supported shape (channels % 16 in, % 32 out);
+    otherwise forward evaluates the original block's expression in PyTorch.  There are NO backward kernels, NO half-model path and NO
+    half_precision form.  fp16 / bf16 inputs are widened and the result is fp32; channels_last inputs are copied to NCHW once.  Every
+    launch leaves the range descriptor of its output on the tensor, so only the first block of a net scans its input (once: conv1 and
+    the downsample share the descriptor, which bounds the sub-sample as well)."""
+
+    _CHILDREN = ("conv1", "bn1", "conv2", "bn2", "conv3", "bn3", "relu", "downsample")
+    _EXPECTED = ("a torchvision-layout ResNet bottleneck (conv1 and conv3 1x1 at stride 1, conv2 3x3 with padding 1 at stride 1 or 2, no "
+                 "groups or dilation, BatchNorm2d with running statistics, downsample None or Conv2d 1x1 at conv2's stride + BatchNorm2d, no "
+                 "`shortcut`)")
+    _EVAL_ONLY = True
+    _CUDA_FLOAT_INPUT = True   # a CPU map takes the original expression
+
+    def __init__(self, inplanes: int, planes: int, stride: int = 1, expansion: int = 4):
+        super().__init__()
+        out = planes * expansion
+        self.conv1 = nn.Conv2d(inplanes, planes, 1, bias=False)
+        self.bn1 = nn.BatchNorm2d(planes)
+        self.conv2 = nn.Conv2d(planes, planes, 3, stride=stride, padding=1, bias=False)
+        self.bn2 = nn.BatchNorm2d(planes)
+        self.conv3 = nn.Conv2d(planes, out, 1, bias=False)
+        self.bn3 = nn.BatchNorm2d(out)
+        self.relu = nn.ReLU(inplace=True)
+        self.downsample = None
+        if stride != 1 or inplanes != out:
+            self.downsample = nn.Sequential(nn.Conv2d(inplanes, out, 1, stride=stride, bias=False), nn.BatchNorm2d(out))
+
+    @classmethod
+    def from_block(cls, block: nn.Module, half_precision: bool = False):
+        if half_precision:
+            raise TypeError("BottleneckFused has no half_precision form")
+        return super().from_block(block, False)
+
+    @staticmethod
+    def matches(block) -> bool:
+        """Duck-typed: is `block` a bottleneck the fused path can stand in for?  (The v1 layout, with the stride on conv1, is not.)"""
+        if isinstance(block, _FusedBlock2D) or not isinstance(block, nn.Module) or hasattr(block, "shortcut"):
+            return False
+        conv1, bn1, conv2, bn2, conv3, bn3, relu = (getattr(block, n, None) for n in ("conv1", "bn1", "conv2", "bn2", "conv3", "bn3", "relu"))
+        if not isinstance(relu, nn.ReLU) or not hasattr(block, "downsample"):
+            return False
+        stride = 2 if isinstance(conv2, nn.Conv2d) and conv2.stride == (2, 2) else 1
+        if not (_is_conv2d_at(conv1, 1, 1) and _is_conv2d_at(conv2, 3, stride) and _is_conv2d_at(conv3, 1, 1)):
+            return False
+        ci, mid, co = conv1.in_channels, conv1.out_channels, conv3.out_channels
+        if (conv2.in_channels, conv2.out_channels, conv3.in_channels) != (mid, mid, mid):
+            return False
+        if not (_is_bn2d(bn1, mid) and _is_bn2d(bn2, mid) and _is_bn2d(bn3, co)):
+            return False
+        ds = block.downsample
+        if ds is None:
+            return stride == 1 and ci == co
+        return (isinstance(ds, nn.Sequential) and len(ds) == 2 and _is_conv2d_at(ds[0], 1, stride) and ds[0].in_channels == ci
+                and ds[0].out_channels == co and _is_bn2d(ds[1], co))
+
+    def _adopt(self, block):
+        pass
+
+    def _stride(self) -> int:
+        return self.conv2.stride[0]
+
+    def _shape_ok(self, x) -> bool:
+        (n, ci, h, w), mid, co, s = x.shape, self.conv1.out_channels, self.conv3.out_channels, self._stride()
+        if ci != self.conv1.in_channels:
+            return False
+        ho, wo = (h + s - 1) // s, (w + s - 1) // s
+        mid_ok = ops.conv2d_supported(n, mid, mid, h, w) if s == 1 else ops.conv2d_s2_supported(n, mid, mid, h, w)
+        return (mid_ok and ops.conv2d_pw_supported(n, ci, mid, h, w, 1) and ops.conv2d_pw_supported(n, mid, co, ho, wo, 1)
+                and (self.downsample is None or ops.conv2d_pw_supported(n, ci, co, h, w, s)))
+
+    def _dtypes(self, half_path: bool):
+        return {self.conv1.weight.dtype}
+
+    def _fold_pairs(self):
+        return ([(self.conv1, self.bn1), (self.conv2, self.bn2), (self.conv3, self.bn3)]
+                + ([tuple(self.downsample)] if self.downsample is not None else []))
+
+    _fold_tensors = BasicBlockFused._fold_tensors
+
+    def _fold(self, wide):
+        """(conv1', conv2', conv3', downsample' or None): BatchNorm folded and packed (a 1x1 weight makes a pointwise pack)."""
+        packs = [ops.PackedConv2d(*fold_batchnorm(conv, bn, wide)) for conv, bn in self._fold_pairs()]
+        return tuple(packs) if len(packs) == 4 else (*packs, None)
+
+    def _reference(self, x):
+        idt = x if self.downsample is None else self.downsample(x)
+        y = self.relu(self.bn1(self.conv1(x)))
+        y = self.relu(self.bn2(self.conv2(y)))
+        return self.relu(self.bn3(self.conv3(y)) + idt)
+
+    def _launch(self, x, packs, out_dtype, products):
+        p1, p2, p3, pd = packs
+        xc = _f32(x).contiguous()   # (the kernels read NCHW: a channels_last map is copied once)
+        s = self._stride()
+        # two launches read x: one descriptor serves both (of the whole map: a valid bound of its sub-sample); else the library scans
+        xr = ops._range_for(xc) if pd is not None else None
+        y1 = ops.conv2d_pw(xc, p1, relu=True, x_range=xr, want_range=True)
+        y2 = ops.conv2d_s2(y1, p2, relu=True, want_range=True) if s == 2 else ops.conv2d(y1, p2, relu=True, want_range=True)
+        idt = xc if pd is None else ops.conv2d_pw(xc, pd, stride=s, x_range=xr)
+        return ops.conv2d_pw(y2, p3, residual=idt, relu=True, want_range=True)
+
+
 def _swap_slot(cls, cur, enable: bool, half_precision: bool):
     """One slot of native_g2d_body / native_eapp_trunk -> (the module the slot holds now, whether anything changed): a matching block
     becomes a `cls` over the same children, a fused one takes the keyword's value, or (enable off) the very object it replaced comes back."""
@@ -1662,6 +1777,28 @@ def native_eapp_trunk(eapp: nn.Module, enable: bool = True, half_precision: bool
         if new is not cur:
             setattr(eapp, name, new)
         changed |= did
+    return changed
+
+
+_RESNET50_STAGES = ("layer1", "layer2", "layer3")
+
+
+def native_eapp_resnet50(eapp: nn.Module, enable: bool = True) -> bool:
+    """Swaps every matching bottleneck of `eapp.custom_resnet50.layer1 / layer2 / layer3` (this package's Eapp or the reference's,
+    model.py:136-173: thirteen blocks) for a BottleneckFused over the same children, or puts the very objects it replaced back.
+    Returns whether anything changed.  Off by default everywhere; opt-in, inference only.  What stays on PyTorch: the 7x7 stride-2 stem
+    with its BatchNorm, ReLU and max-pool, the adaptive pool, `conv_reduce` and Eapp's `fc`."""
+    net = getattr(eapp, "custom_resnet50", None)
+    changed = False
+    for name in _RESNET50_STAGES:
+        stage = getattr(net, name, None)
+        if not isinstance(stage, nn.Sequential):
+            continue
+        for i in range(len(stage)):
+            new, did = _swap_slot(BottleneckFused, stage[i], enable, False)
+            if new is not stage[i]:
+                stage[i] = new
+            changed |= did
     return changed
 
 

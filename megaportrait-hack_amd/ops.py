@@ -1255,15 +1255,20 @@ class PackedConv2d:
     include/mphip.h (mphip_pack_conv2d_weight).  `key` = (data_ptr, _version, device, weight_epoch()) of the tensors it was built from,
     like the other packs: an owner re-creates the object when `PackedConv2d.key_of(weight, bias) != pack.key`.
     groups > 1: the weight is torch's grouped [Co, Ci / groups, 3, 3]; `ci` stays the conv's input channel count, the pack is the ordinary
-    one of a [Co, Ci / groups] weight, and only ops.conv2d_grouped takes it."""
+    one of a [Co, Ci / groups] weight, and only ops.conv2d_grouped takes it.
+    A 1x1 weight ([Co, Ci, 1, 1], groups == 1) makes a `pointwise` pack: the layout of mphip_pack_conv2d_pw_weight, which only
+    ops.conv2d_pw takes (PackedConv2dPW is this class under the name its users read); key and lazy packing are the same."""
 
-    __slots__ = ("weight", "bias", "co", "ci", "groups", "key", "_packed")
+    __slots__ = ("weight", "bias", "co", "ci", "groups", "key", "pointwise", "_packed")
 
     def __init__(self, weight: torch.Tensor, bias: torch.Tensor, groups: int = 1):
         self.key = PackedConv2d.key_of(weight, bias)
         weight = _req(weight.detach(), "conv2d weight")
-        if weight.dim() != 4 or tuple(weight.shape[2:]) != (3, 3):
-            raise RuntimeError(f"PackedConv2d: expected an OIHW 3x3 weight, got {tuple(weight.shape)}")
+        if weight.dim() != 4 or tuple(weight.shape[2:]) not in ((3, 3), (1, 1)):
+            raise RuntimeError(f"PackedConv2d: expected an OIHW 3x3 or 1x1 weight, got {tuple(weight.shape)}")
+        self.pointwise = tuple(weight.shape[2:]) == (1, 1)
+        if self.pointwise and int(groups) != 1:
+            raise RuntimeError(f"PackedConv2d: a 1x1 weight with groups = {groups!r}: the pointwise form has no groups")
         if bias is None or tuple(bias.shape) != (weight.shape[0],):
             raise RuntimeError("PackedConv2d: a bias of Co elements is required")
         self.groups = int(groups)
@@ -1286,9 +1291,11 @@ class PackedConv2d:
         if self._packed is None:
             lib = _lib.load()
             cig = self.ci // self.groups
-            nbytes = lib.mphip_conv2d_packed_weight_bytes(self.co, cig)
-            wp = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=self.weight.device)
-            _lib.check(lib.mphip_pack_conv2d_weight(_ptr(self.weight), _ptr(wp), self.co, cig, _stream()), "mphip_pack_conv2d_weight")
+            size, pack, name = ((lib.mphip_conv2d_pw_packed_weight_bytes, lib.mphip_pack_conv2d_pw_weight, "mphip_pack_conv2d_pw_weight")
+                                if self.pointwise else
+                                (lib.mphip_conv2d_packed_weight_bytes, lib.mphip_pack_conv2d_weight, "mphip_pack_conv2d_weight"))
+            wp = torch.empty((size(self.co, cig) + 3) // 4, dtype=torch.float32, device=self.weight.device)
+            _lib.check(pack(_ptr(self.weight), _ptr(wp), self.co, cig, _stream()), name)
             self._packed = wp
         return self._packed
 
@@ -1365,7 +1372,7 @@ def conv2d(x: torch.Tensor, pack: PackedConv2d, residual: Optional[torch.Tensor]
 
 
 class _Conv2dForm(NamedTuple):
-    """One form of the 2-D 3x3 conv: what its wrapper and _conv2d_launch look up, keyed as the library's own table of forms
+    """One form of the 2-D conv (3x3, or the pointwise one): what its wrapper and _conv2d_launch look up, keyed as the library's own table of forms
     (csrc/conv2d_run.hip).  The entry is mphip_<who>_fwd, with a _typed twin where `typed`."""
     who: str                 # the wrapper's name, in messages
     rule: str                # mphip_<rule>_supported and mphip_<rule>_workspace_bytes take (n, ci, co, h, w, *counts)
@@ -1374,6 +1381,7 @@ class _Conv2dForm(NamedTuple):
     lowres_residual: bool    # the residual is required and lives on the halved map, h and w even
     grouped: bool            # takes a grouped pack; the entry takes pack.groups (the split-K entry: then the split count) after W
     typed: bool              # half maps, out_dtype and products are allowed
+    strided: bool = False    # the wrapper takes a stride: rule, entry and y_hw take it after W
 
 
 _SAME_MAP = lambda h, w: (h, w)
@@ -1386,6 +1394,8 @@ _CONV2D_FORMS = {
     "grouped": _Conv2dForm("conv2d_grouped", "conv2d_grouped", "H={h} W={w} groups={groups} (there is no fallback)", _SAME_MAP, False, True, False),
     # what ops.conv2d and ops.conv2d_grouped launch with splits > 1, under their own name: it always takes a workspace
     "split": _Conv2dForm("conv2d_split", "conv2d_split", "", _SAME_MAP, False, True, False),
+    "pw": _Conv2dForm("conv2d_pw", "conv2d_pw", "H={h} W={w} stride={stride} (there is no fallback)",
+                      lambda h, w, s: ((h + s - 1) // s, (w + s - 1) // s), False, False, False, True),
 }
 
 
@@ -1401,7 +1411,7 @@ def _conv2d_entries(form):
     return got
 
 
-def _conv2d_one_source(form, x, pack, residual, relu, x_range, want_range, out_dtype=None, products=None, splits=None):
+def _conv2d_one_source(form, x, pack, residual, relu, x_range, want_range, out_dtype=None, products=None, splits=None, stride=None):
     """The one-source wrappers: the checks of x against the pack and the form's shape rule, the choice of its descriptor, the launch."""
     typed = form.typed and _conv2d_typed(out_dtype, products, x)
     x = _req_typed(x, "x") if typed else _req(x, "x")
@@ -1409,30 +1419,32 @@ def _conv2d_one_source(form, x, pack, residual, relu, x_range, want_range, out_d
         raise RuntimeError(f"{form.who}: input {tuple(x.shape)} does not match Ci={pack.ci}")
     n, ci, h, w = x.shape
     groups = pack.groups if form.grouped else 1
-    counts = (groups,) if form.grouped else ()
+    counts = (groups,) if form.grouped else (int(stride),) if form.strided else ()
     if (form.lowres_residual and (h % 2 or w % 2)) or not _conv2d_entries(form)[0](n, ci, pack.co, h, w, *counts):
-        raise RuntimeError(f"{form.who}: unsupported shape N={n} Ci={ci} Co={pack.co} " + form.unsupported.format(h=h, w=w, groups=groups))
+        raise RuntimeError(f"{form.who}: unsupported shape N={n} Ci={ci} Co={pack.co} " + form.unsupported.format(h=h, w=w, groups=groups, stride=stride))
     if form.lowres_residual and residual is None:
         raise RuntimeError(f"{form.who}: residual_lowres is required")
     xr = x_range if x_range is not None else current_range(x)   # None: the library scans x
     ns = _conv2d_splits(form.who, splits, typed, (n, ci, pack.co, h, w), groups)
-    return _conv2d_launch(form, typed, pack, x, xr, residual, relu, want_range, out_dtype, products, ns)
+    return _conv2d_launch(form, typed, pack, x, xr, residual, relu, want_range, out_dtype, products, ns, stride=stride)
 
 
-def _conv2d_launch(form, typed, pack, x1, r1, residual, relu, want_range, out_dtype=None, products=None, splits=1, second=None):
+def _conv2d_launch(form, typed, pack, x1, r1, residual, relu, want_range, out_dtype=None, products=None, splits=1, second=None, stride=None):
     """What the wrappers of every form share once their sources are checked and the descriptors chosen: the residual check, the
     workspace, y and out_range, and the call of the fp32 or (`typed`) the typed entry.  second = (affine1, relu1, x2, affine2, r2, relu2):
     what ops.conv2d_cat brings.  splits > 1 (ops.conv2d, ops.conv2d_grouped): the split-K form's entry and workspace."""
     who = form.who
+    if pack.pointwise != form.strided:   # (the two layouts differ: a kernel would read past, or misread, the other's slabs)
+        raise RuntimeError(f"{who}: the pack is that of a {'1x1' if pack.pointwise else '3x3'} conv")
     if pack.groups != 1 and not form.grouped:   # (its slabs hold Ci / groups channels: any other kernel would read past them)
         raise RuntimeError(f"{who}: the pack is that of a grouped conv (groups = {pack.groups}): only ops.conv2d_grouped takes it")
     entry_form = _CONV2D_FORMS["split"] if splits > 1 else form
-    counts = (pack.groups, splits) if splits > 1 else (pack.groups,) if form.grouped else ()
+    counts = (pack.groups, splits) if splits > 1 else (pack.groups,) if form.grouped else (int(stride),) if form.strided else ()
     aff1, relu1, x2, aff2, r2, relu2 = second or (None, False, None, None, None, False)
     _, workspace_bytes, forward = _conv2d_entries(entry_form)
     n, c1, h, w = x1.shape
     c2 = 0 if x2 is None else int(x2.shape[1])
-    ho, wo = form.y_hw(h, w)
+    ho, wo = form.y_hw(h, w, *((int(stride),) if form.strided else ()))
     if residual is not None:
         residual = _req_typed(residual, "residual") if typed else _req(residual, "residual")
         rshape = (n, pack.co, h // 2, w // 2) if form.lowres_residual else (n, pack.co, ho, wo)
@@ -1472,6 +1484,24 @@ def conv2d_s2(x: torch.Tensor, pack: PackedConv2d, residual: Optional[torch.Tens
     [N, Co, (H+1)//2, (W+1)//2].  The pack, the f16x3 arithmetic and the descriptors are ops.conv2d's: with the same x, x_range and pack
     the result is, bit for bit, conv2d(...)[:, :, ::2, ::2] (a residual being the even sub-sample of that call's).  fp32 only."""
     return _conv2d_one_source(_CONV2D_FORMS["s2"], x, pack, residual, relu, x_range, want_range)
+
+
+PackedConv2dPW = PackedConv2d   # the pack of a [Co, Ci, 1, 1] weight (PackedConv2d.pointwise), for ops.conv2d_pw
+
+
+def conv2d_pw_supported(n: int, ci: int, co: int, h: int, w: int, stride: int = 1) -> bool:
+    """Does ops.conv2d_pw take an [n, ci, h, w] input (h, w: the INPUT map) with co output channels at this stride
+    (mphip_conv2d_pw_supported)?"""
+    return bool(_lib.load().mphip_conv2d_pw_supported(int(n), int(ci), int(co), int(h), int(w), int(stride)))
+
+
+def conv2d_pw(x: torch.Tensor, pack: PackedConv2d, residual: Optional[torch.Tensor] = None, relu: bool = False, stride: int = 1,
+              x_range: Optional[torch.Tensor] = None, want_range: bool = False) -> torch.Tensor:
+    """y = act(conv1x1(x, stride) + bias (+ residual)) on NCHW fp32, stride 1 or 2 (mphip_conv2d_pw_fwd): y and residual are
+    [N, Co, ceil(H / stride), ceil(W / stride)]; the stride-2 sub-sample is made by the kernel's loads.  `pack` is the PackedConv2d of a
+    [Co, Ci, 1, 1] weight.  The f16x3 arithmetic and the descriptors are ops.conv2d's: the result has the bits of ops.conv2d (stride 2:
+    ops.conv2d_s2) with the 3x3 weight whose only non-zero tap is the centre.  fp32 maps and three products only."""
+    return _conv2d_one_source(_CONV2D_FORMS["pw"], x, pack, residual, relu, x_range, want_range, stride=stride)
 
 
 def conv2d_grouped_supported(n: int, ci: int, co: int, h: int, w: int, groups: int) -> bool:

@@ -55,6 +55,9 @@ def parse(argv=None):
     ap.add_argument("--native-eapp-trunk", action="store_true",
                     help="run the appearance encoder's three 2-D ResBlock_Custom blocks on the matrix cores, GroupNorm, ReLU and the skip "
                          "conv folded into two conv launches per block (gbase.Gbase.native_trunk; inference only, fp32 models; off by default)")
+    ap.add_argument("--native-eapp-resnet50", action="store_true",
+                    help="run the thirteen bottlenecks of the appearance encoder's ResNet-50 (the identity descriptor) with BatchNorm folded, "
+                         "their 1x1 and 3x3 convs on the matrix cores (gbase.Gbase.native_resnet50; inference only, fp32 models; off by default)")
     ap.add_argument("--native-motion-encoder", action="store_true",
                     help="run the BasicBlocks of the motion encoder's two ResNet-18s with BatchNorm folded and their 3x3 convs on the "
                          "matrix cores (gbase.Gbase.native_motion_encoder; inference only, fp32 models; off by default)")
@@ -199,6 +202,8 @@ def run(job: dict, args, rank: int, world: int) -> List[str]:
         g.native_body(**half, **({"fuse_upsample": True} if args.native_fuse_upsample else {}))
     if args.native_eapp_trunk:
         g.native_trunk(**half)
+    if args.native_eapp_resnet50:
+        g.native_resnet50()
     if args.native_motion_encoder:
         g.native_motion_encoder(**({"fuse_stem": True} if args.native_fuse_stem else {}),
                                 **({"rotation_net": True} if args.native_rotation_net else {}),
