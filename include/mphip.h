@@ -41,7 +41,7 @@ extern "C" {
 
 /* ABI version of this header.  Bumped whenever an exported signature or a packed layout changes; mphip_version() returns the
  * value the LIBRARY was built with — compare the two after dlopen (the ctypes binding does, and refuses a mismatch). */
-#define MPHIP_ABI_VERSION 28
+#define MPHIP_ABI_VERSION 29
 int mphip_version(void);
 /* hipGraph hygiene (ABI 13).  On ROCm 7.x a MEMSET node of a captured hipGraph is not reliably ordered with its neighbouring kernel nodes
  * (observed twice: stale f16x3 pack headers, r03; a training step's loss that kept its previous value, r04-r05 — ATen's multi-block
@@ -727,6 +727,39 @@ int mphip_conv2d_resup2_fwd(const float *x, const float *x_range, const void *w_
 int mphip_conv2d_stem_supported(int N, int Ci, int Co, int H, int W, int pool);
 int mphip_conv2d_stem_fwd(const float *x, const float *w_oihw, const float *bias, float *y, float *out_range, int N, int Ci, int Co,
                           int H, int W, int relu, int pool, void *stream);
+
+/* The 7x7 stems of Eapp on the matrix cores (ABI 29; csrc/conv2d_stem7_f16x3.hip): nn.Conv2d(3, Co, 7, stride=s, padding=3), s = 1 or 2,
+ * with a bias (or a folded BatchNorm), an optional ReLU and an optional nn.MaxPool2d(3, stride=2, padding=1), in one launch:
+ *     c[n,co,i,j] = sum_{ci,dy,dx} w[co,ci,dy,dx] * x[n,ci,s*i+dy-3,s*j+dx-3]         zero padding 3, Ci = 3, Ho = (H+s-1)/s, Wo = (W+s-1)/s
+ *     v           = c + bias[co];   relu != 0: v = ReLU(v)
+ *     pool == 0:  y = v                                                               y is [N,Co,Ho,Wo]
+ *     pool != 0:  y[n,co,p,q] = max of v over (2p+a-1, 2q+b-1), a, b in {0,1,2}, inside the Ho x Wo map;  y is [N,Co,(Ho+1)/2,(Wo+1)/2]
+ * x and y are NCHW fp32; H and W in the signatures are the INPUT map's.  The arithmetic is mphip_conv2d_fwd's f16x3, term by term: the
+ * power-of-two operand scale of x from x_range (NULL: the library scans x into `workspace`, mphip_conv2d_stem7_workspace_bytes; with
+ * x_range the workspace is not read and may be NULL), the scale of w from the pack header, v*S = hi + lo split while staging, per 16-wide
+ * K chunk the products Wlo*Xhi, Whi*Xhi, Whi*Xlo in that order on v_mfma_f32_32x32x16_f16, chunks ascending from a +0 accumulator; unscale,
+ * bias, ReLU and the max in fp32.  K is ordered as rows (ci, dy) of 8 slots dx = 0..7 with a zero weight AND a zero operand at dx = 7:
+ * 21 rows and one zero row, 11 chunks.  That mapping is the pack's and does not depend on the pixel, the tile, the stride or the pool flag,
+ * so with the same x, x_range, pack and bias the stride-2 launch writes the bits of the stride-1 launch at the even rows and columns, the
+ * pooled launch writes max_pool2d(3, 2, 1) of the flat launch's bits, and an image placed in a zero canvas gives the translated bits.
+ * The pool follows mphip_conv2d_stem_fwd: conv positions outside the map enter the max as -inf, NaN wins the ReLU and the max (a pooled
+ * NaN is the quiet NaN 0x7fc00000), ReLU maps negatives and zeros to +0; the sign of a pooled zero without ReLU is left open.
+ * w_packed: mphip_pack_conv2d_stem7_weight packs the OIHW weight [Co,3,7,7] into a 16-byte header {1/scale, scale, max|w| bits, -}, the
+ * same function of max|w| as mphip_pack_conv2d_weight's, then [chunk 11][part hi/lo][k group][co 64][8] of f16 (channels past Co are
+ * zeros); 16-byte aligned, mphip_conv2d_stem7_packed_weight_bytes(Co) long (the same for every admissible Co; 0 for any other).
+ * out_range (optional): a derive-mode descriptor whose partial maxima fold to the exact max|y|.  No floating-point atomics: the bits are
+ * reproducible.  Saturation is counted in the unit's own counter (mphip_f16x3_saturation_count sums it).
+ * Shapes: Ci == 3, Co % 16 == 0, Co <= 64, N, H, W >= 1, stride 1 or 2, fewer than 2^31 elements in x and in y.  The rules in the order
+ * they are checked, all before the first HIP call and MPHIP_EINVAL each, messages naming conv2d_stem7_fwd: null pointer (x, w_packed,
+ * bias or y), unsupported shape, alignment (w_packed 16 bytes, every other pointer 4), "y must not alias x"; then MPHIP_EWORKSPACE for
+ * a missing or short workspace when x_range is NULL. */
+int mphip_conv2d_stem7_supported(int N, int Ci, int Co, int H, int W, int stride, int pool);
+size_t mphip_conv2d_stem7_packed_weight_bytes(int Co);
+int mphip_pack_conv2d_stem7_weight(const float *w_oihw, void *w_packed, int Co, void *stream);
+size_t mphip_conv2d_stem7_workspace_bytes(int N, int Ci, int Co, int H, int W, int stride, int pool);
+int mphip_conv2d_stem7_fwd(const float *x, const float *x_range, const void *w_packed, const float *bias, float *y, float *out_range,
+                           int N, int Ci, int Co, int H, int W, int stride, int relu, int pool, void *workspace, size_t workspace_bytes,
+                           void *stream);
 
 /* Groups (ABI 25; csrc/conv2d_grp_f16x3.hip): nn.Conv2d(Ci, Co, 3, stride=1, padding=1, groups=groups) with mphip_conv2d_fwd's epilogue,
  * for the thirteen groups = 2 blocks of 6DRepNet's RepVGG-B1g2 backbone in deploy form:

@@ -174,6 +174,12 @@ SIGNATURES = {
     # the ResNet-18 stem conv + bias + ReLU + max-pool in one launch, exact fp32 (ABI 24, csrc/conv2d_stem.hip)
     "mphip_conv2d_stem_supported": (_i, [_i] * 6),
     "mphip_conv2d_stem_fwd": (_i, [_p] * 5 + [_i] * 7 + [_p]),
+    # Eapp's two 7x7 stems on the matrix cores, f16x3 (ABI 29, csrc/conv2d_stem7_f16x3.hip)
+    "mphip_conv2d_stem7_supported": (_i, [_i] * 7),
+    "mphip_conv2d_stem7_packed_weight_bytes": (_sz, [_i]),
+    "mphip_pack_conv2d_stem7_weight": (_i, [_p, _p, _i, _p]),
+    "mphip_conv2d_stem7_workspace_bytes": (_sz, [_i] * 7),
+    "mphip_conv2d_stem7_fwd": (_i, [_p] * 6 + [_i] * 8 + [_p, _sz, _p]),
     # the grouped form (ABI 25, csrc/conv2d_grp_f16x3.hip): groups after W
     "mphip_conv2d_grouped_supported": (_i, [_i] * 6),
     "mphip_conv2d_grouped_workspace_bytes": (_sz, [_i] * 6),
@@ -197,7 +203,7 @@ _lib = None
 # The ABI version the SIGNATURES table above mirrors.  Checked against the library at load time, and against include/mphip.h by
 # tests/test_host.py — NOT read from the header at run time: a relocated / installed package ships libmphip.so without the repository's
 # include/ directory.
-EXPECTED_ABI_VERSION = 28
+EXPECTED_ABI_VERSION = 29
 
 
 def header_abi_version() -> int:

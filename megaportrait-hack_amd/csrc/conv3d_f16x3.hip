@@ -1300,7 +1300,7 @@ extern "C" int mphip_f16x3_saturation_count(unsigned long long *count, int reset
     for (auto other : {mphip::f16x3_wino_saturation, mphip::f16x3_wino_pp_saturation, mphip::f16x3_wino_bt_saturation,
                        mphip::conv2d_f16x3_saturation, mphip::conv2d_gn_f16x3_saturation, mphip::conv2d_lp_saturation,
                        mphip::conv2d_s2_saturation, mphip::conv2d_up2_saturation, mphip::conv2d_grp_saturation,
-                       mphip::conv2d_split_saturation, mphip::conv2d_pw_saturation}) {
+                       mphip::conv2d_split_saturation, mphip::conv2d_pw_saturation, mphip::conv2d_stem7_saturation}) {
         unsigned long long wn = 0;   // the transformed-domain and 2-D kernels keep their own counters (separate translation units)
         if (other(&wn, reset) != 0) {
             mphip::set_error("f16x3_saturation_count: reading the counter failed");

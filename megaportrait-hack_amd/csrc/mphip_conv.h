@@ -186,6 +186,8 @@ int conv2d_grp_saturation(unsigned long long *count, int reset);
 int conv2d_split_saturation(unsigned long long *count, int reset);
 // conv2d_pw_f16x3.hip: the pointwise (1x1) form (mphip_conv2d_pw_fwd), likewise
 int conv2d_pw_saturation(unsigned long long *count, int reset);
+// conv2d_stem7_f16x3.hip: the 7x7 stem (mphip_conv2d_stem7_fwd), likewise
+int conv2d_stem7_saturation(unsigned long long *count, int reset);
 
 // The forms of the 2-D conv (3x3 but for the last): what conv2d_run's table (conv2d_run.hip) is indexed by.  One C entry each, the first
 // two a typed one too.

@@ -135,8 +135,9 @@ class Eapp(nn.Module):
         """Opt-in, inference only: run `resblock_128 / _256 / _512` as model.ResBlockCustomFused — two launches per block on the matrix
         cores with fp32-class accuracy (csrc/conv2d_gn_f16x3.hip): GroupNorm + ReLU folded into the convs' input staging, the skip conv
         folded into the last conv — over the blocks' own children: same Parameter objects, same state-dict keys.  `enable=False` puts the
-        original blocks back.  Under autograd or on a half model the fused blocks evaluate the original PyTorch expression.  The 7x7
-        stem, the average pools and conv_1 stay on PyTorch.  half_precision (off by default): inside torch.autocast(float16), and as a
+        original blocks back.  Under autograd or on a half model the fused blocks evaluate the original PyTorch expression.  The
+        average pools and conv_1 stay on PyTorch; the 7x7 stem has a switch of its own (native_stems).
+        half_precision (off by default): inside torch.autocast(float16), and as a
         .half() / .bfloat16() model, the fused blocks run one f16 product per multiply and return the half dtype
         (model.ResBlockCustomFused)."""
         M.native_eapp_trunk(self, enable, half_precision)
@@ -147,8 +148,19 @@ class Eapp(nn.Module):
         BatchNorm folded, the 1x1 convs on csrc/conv2d_pw_f16x3.hip and the 3x3 convs on csrc/conv2d_f16x3.hip / conv2d_s2_f16x3.hip, three
         or four matrix-core launches per block with fp32-class accuracy — over the blocks' own children: same Parameter objects, same
         state-dict keys.  `enable=False` puts the original blocks back.  Under autograd, in train mode or on a half model the fused blocks
-        evaluate the original PyTorch expression.  The 7x7 stride-2 stem, the pools, conv_reduce and fc stay on PyTorch."""
+        evaluate the original PyTorch expression.  The pools, conv_reduce and fc stay on PyTorch; the 7x7 stride-2 stem has a switch of
+        its own (native_stems)."""
         M.native_eapp_resnet50(self, enable)
+        return self
+
+    def native_stems(self, enable: bool = True) -> "Eapp":
+        """Opt-in, inference only: run the two 7x7 convs that read the source image on the matrix cores with fp32-class accuracy
+        (csrc/conv2d_stem7_f16x3.hip): `conv` as model.ConvStem7Fused, one launch whose output carries its range descriptor, and
+        `custom_resnet50`'s `conv1 -> bn1 -> relu -> maxpool` as model.Stem7Fused, one launch with the BatchNorm folded and ReLU and
+        max-pool in the epilogue.  Same Parameter and buffer objects, same state-dict keys; `enable=False` puts the original modules
+        back.  Under autograd, in train mode or on a half model the original PyTorch expression runs.  Independent of native_trunk and
+        native_resnet50."""
+        M.native_eapp_stems(self, enable)
         return self
 
     def trunk2d(self, x):

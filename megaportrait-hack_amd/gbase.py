@@ -82,6 +82,13 @@ class Gbase(M._HotSliceRunner, nn.Module):
         M.native_eapp_resnet50(self.appearanceEncoder, enable)
         return self
 
+    def native_stems(self, enable: bool = True) -> "Gbase":
+        """Opt-in, inference only: run the appearance encoder's two 7x7 stems (`conv`, and `custom_resnet50`'s conv1-bn1-relu-maxpool)
+        on the matrix cores, one launch each (model.native_eapp_stems); `enable=False` restores the original modules.  Same parameters
+        and state-dict keys."""
+        M.native_eapp_stems(self.appearanceEncoder, enable)
+        return self
+
     def native_motion_encoder(self, enable: bool = True, fuse_stem: bool = False, rotation_net: bool = False,
                               split_small_maps: bool = False) -> "Gbase":
         """Opt-in (off by default), inference only: the BasicBlocks of the motion encoder's two ResNet-18s (`head_pose_net`,

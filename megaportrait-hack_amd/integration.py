@@ -78,7 +78,7 @@ def patch_functions(model_module) -> List[str]:
 def install(gbase: nn.Module, model_module: Optional[object] = None, eapp_tail: bool = True, g2d_final: bool = False,
             g2d_body: bool = False, eapp_trunk: bool = False, half_precision: bool = False, fuse_upsample: bool = False,
             motion_encoder: bool = False, fuse_stem: bool = False, rotation_net: bool = False,
-            split_small_maps: bool = False) -> List[str]:
+            split_small_maps: bool = False, eapp_stems: bool = False) -> List[str]:
     """swap_hot_path + patch_functions.  `model_module` is the imported reference `model` module (the one that defines
     Gbase); pass it so the two `apply_warping_field` call sites inside Gbase.forward use the HIP kernel too.
     g2d_final (off by default): also swap `gbase.G2d.final_conv` (model.py:747-752) for model.G2dFinalConv, which shares the
@@ -99,7 +99,9 @@ def install(gbase: nn.Module, model_module: Optional[object] = None, eapp_tail: 
     (`gbase.motionEncoder.rotation_net`) become model.RepVGGBlockFused, one matrix-core launch each (inference only;
     model.native_rotation_net).  Without motion_encoder it is a ValueError, like fuse_stem.
     split_small_maps (off by default): with motion_encoder, the stride-1 convs of the blocks fused there take the split-K launch where the
-    library recommends one (ops.conv2d_splits).  Without motion_encoder it is a ValueError, like fuse_stem."""
+    library recommends one (ops.conv2d_splits).  Without motion_encoder it is a ValueError, like fuse_stem.
+    eapp_stems (off by default): also swap the two 7x7 stems of `gbase.appearanceEncoder` (`conv`, and `custom_resnet50`'s
+    conv1-bn1-relu-maxpool) for their one-launch matrix-core forms (inference only; model.native_eapp_stems).  Independent of eapp_trunk."""
     if split_small_maps and not motion_encoder:
         raise ValueError("install: split_small_maps=True needs motion_encoder=True")
     if fuse_stem and not motion_encoder:
@@ -113,6 +115,8 @@ def install(gbase: nn.Module, model_module: Optional[object] = None, eapp_tail: 
         done.append("G2d.body")
     if eapp_trunk and M.native_eapp_trunk(getattr(gbase, "appearanceEncoder", None), True, half_precision):
         done.append("Eapp.trunk2d")
+    if eapp_stems and M.native_eapp_stems(getattr(gbase, "appearanceEncoder", None), True):
+        done.append("Eapp.stems")
     emtn = getattr(gbase, "motionEncoder", None)
     if motion_encoder and M.native_emtn_resnets(emtn, True, split_small_maps):
         done.append("Emtn.resnets")

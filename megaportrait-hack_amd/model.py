@@ -1786,8 +1786,9 @@ _RESNET50_STAGES = ("layer1", "layer2", "layer3")
 def native_eapp_resnet50(eapp: nn.Module, enable: bool = True) -> bool:
     """Swaps every matching bottleneck of `eapp.custom_resnet50.layer1 / layer2 / layer3` (this package's Eapp or the reference's,
     model.py:136-173: thirteen blocks) for a BottleneckFused over the same children, or puts the very objects it replaced back.
-    Returns whether anything changed.  Off by default everywhere; opt-in, inference only.  What stays on PyTorch: the 7x7 stride-2 stem
-    with its BatchNorm, ReLU and max-pool, the adaptive pool, `conv_reduce` and Eapp's `fc`."""
+    Returns whether anything changed.  Off by default everywhere; opt-in, inference only.  What stays on PyTorch: the adaptive pool,
+    `conv_reduce` and Eapp's `fc`; the 7x7 stride-2 stem with its BatchNorm, ReLU and max-pool has a switch of its own
+    (native_eapp_stems)."""
     net = getattr(eapp, "custom_resnet50", None)
     changed = False
     for name in _RESNET50_STAGES:
@@ -1799,6 +1800,193 @@ def native_eapp_resnet50(eapp: nn.Module, enable: bool = True) -> bool:
             if new is not stage[i]:
                 stage[i] = new
             changed |= did
+    return changed
+
+
+def _is_stem7_conv(m, stride: int) -> bool:
+    """Conv2d(3, Co, 7, stride, padding=3) with Co a multiple of 16 up to 64: what csrc/conv2d_stem7_f16x3.hip computes."""
+    return _is_conv2d_at(m, 7, stride) and m.in_channels == 3 and m.out_channels % 16 == 0 and 16 <= m.out_channels <= 64
+
+
+def _stem7_input_ok(x, tensors, co: int, stride: int, pool: bool) -> bool:
+    """The call conditions the two 7x7 stems share: fp32 parameters, a CUDA floating-point [N, 3, H, W] image on their device, a shape
+    the kernel takes."""
+    if {t.dtype for t in tensors} != {torch.float32}:
+        return False
+    if not (isinstance(x, torch.Tensor) and x.is_cuda and x.is_floating_point() and x.dim() == 4 and x.numel() > 0):
+        return False
+    n, ci, h, w = x.shape
+    return ci == 3 and all(t.device == x.device for t in tensors) and ops.conv2d_stem7_supported(n, ci, co, h, w, stride, pool)
+
+
+class ConvStem7Fused(_StemSlot):
+    """`Eapp.conv`, Conv2d(3, 64, 7, stride=1, padding=3) with a bias at full resolution (model.py:209), as ONE launch of
+    csrc/conv2d_stem7_f16x3.hip on the matrix cores (f16x3 arithmetic: fp32-class accuracy).  The result carries the range descriptor of
+    its exact max|y|: ResBlockCustomFused's second launch, which reads this map as its second source, finds one (ops.current_range) and
+    does not scan 64 channels at full resolution; the scan of the 3-channel image stays on the image, so Eapp's other stem does not repeat
+    it.  Opt-in, inference only.  The Parameters are the conv's own, registered under their own names (_StemSlot): the same state-dict
+    keys, the same `named_modules()` name; `native_eapp_stems(eapp, False)` puts the very conv back.
+
+    The native path runs in eval mode, without autograd, on an fp32 conv, a CUDA image and a supported shape; an fp16 / bf16 image is
+    widened, a channels_last one copied once, the result is fp32.  Otherwise the original conv runs: bit for bit on the CPU, in train
+    mode, under autograd and on half modules."""
+
+    def __init__(self, conv: nn.Module):
+        super().__init__()
+        self._take(conv, self)
+
+    @staticmethod
+    def matches(conv) -> bool:
+        return _is_stem7_conv(conv, 1) and conv.bias is not None
+
+    def _native_ok(self, x) -> bool:
+        if self.training or ag.needs_grad(self, x):
+            return False
+        return _stem7_input_ok(x, [self._orig.weight, self._orig.bias], self._orig.out_channels, 1, False)
+
+    def _pack(self):
+        w, b = self._orig.weight, self._orig.bias
+        hit = self.__dict__.get("_mphip_pack")
+        if hit is None or hit.key != ops.PackedConv2dStem7.key_of(w, b) or ops.repacking():
+            hit = self.__dict__["_mphip_pack"] = ops.PackedConv2dStem7(w, b)
+        return hit
+
+    def forward(self, x):
+        if not self._native_ok(x):
+            return self._orig(x)
+        return ops.conv2d_stem7(_f32(x), self._pack(), stride=1, relu=False, pool=False, want_range=True)
+
+
+class _Stem7Pass(_StemSlot):
+    """The `bn1` and `maxpool` slots of a fused 7x7 stem.  Between them CustomResNet50.forward calls F.relu, not a module, so no mark on
+    the tensor survives; the shape does.  Stem7Fused returns its pooled map as a 5-D view [1, N, C, Hp, Wp] carrying its mark: `bn1`
+    hands a marked 5-D tensor through, F.relu keeps shape and bits (the map is >= +0 or NaN already), and `maxpool` turns a 5-D tensor
+    with a leading 1 back into the 4-D view and puts the descriptor the head kept for a map of that shape on it.  nn.MaxPool2d raises
+    on a 5-D input, so nothing else reaches that branch.  No tensor contents are compared and the device is not synchronised.  A 4-D
+    tensor goes through the original module."""
+
+    def __init__(self, orig: nn.Module, head: "Stem7Fused", last: bool):
+        super().__init__()
+        self._take(orig, head)
+        self.__dict__["_last"] = last
+
+    def forward(self, x):
+        if isinstance(x, torch.Tensor) and x.dim() == 5 and x.shape[0] == 1:
+            if not self._last:
+                if x.__dict__.get("_mphip_stem7") is self._head:
+                    return x
+            else:
+                kept = self._head.__dict__.pop("_mphip_kept", None)   # (used once: the descriptor of the launch this map came from)
+                y = x[0]
+                if kept is not None and kept[1] == tuple(y.shape) and kept[2] == y.device:
+                    ops.tag_range(y, kept[0])
+                return y
+        return self._orig(x)
+
+
+class Stem7Fused(_StemSlot):
+    """The stem of Eapp's `custom_resnet50` (model.py:140-160): `conv1` (3 -> 64, 7x7, stride 2, padding 3, no bias) -> `bn1` -> F.relu ->
+    `maxpool` (3, stride 2, padding 1), as ONE launch of csrc/conv2d_stem7_f16x3.hip: the BatchNorm folded into the conv (fold_batchnorm),
+    bias, ReLU and the max-pool in the kernel's epilogue, the 64-channel half-resolution map never written.  `Stem7Fused.swap(net)` puts a
+    Stem7Fused into the `conv1` slot and _Stem7Pass stand-ins into `bn1` and `maxpool`; `swap(net, False)` puts the very objects back.
+    State-dict keys and their order, `named_modules()` names and the Parameter and buffer objects are the net's own; the net's forward is
+    not touched.  The functional ReLU between `bn1` and `maxpool` still runs, over the pooled map (a sixteenth of the conv's map).
+
+    The native path runs in eval mode, without autograd, on an fp32 module, a CUDA image and a supported shape; an fp16 / bf16 image is
+    widened, a channels_last one copied once; the map entering `layer1` is fp32, 4-D and carries the range descriptor of its exact
+    max|y|.  Otherwise this slot runs the original conv and returns a 4-D tensor, so the originals of the other slots run: the original
+    expression, bit for bit."""
+
+    _SLOTS = ("conv1", "bn1", "maxpool")
+
+    def __init__(self, conv: nn.Module, bn: nn.Module, pool: nn.Module):
+        super().__init__()
+        self._take(conv, self)
+        self.__dict__["_bn"], self.__dict__["_pool"] = bn, pool
+
+    @classmethod
+    def _find(cls, net):
+        mods = [getattr(net, name, None) for name in cls._SLOTS] if isinstance(net, nn.Module) else [None]
+        return mods if all(isinstance(m, nn.Module) for m in mods) else None
+
+    @classmethod
+    def matches(cls, net) -> bool:
+        from torch.nn.modules.utils import _pair
+
+        mods = cls._find(net)
+        if mods is None or any(isinstance(m, _StemSlot) for m in mods):
+            return False
+        conv, bn, pool = mods
+        if not (_is_stem7_conv(conv, 2) and _is_bn2d(bn, conv.out_channels)):
+            return False
+        return (isinstance(pool, nn.MaxPool2d) and _pair(pool.kernel_size) == (3, 3) and _pair(pool.stride) == (2, 2)
+                and _pair(pool.padding) == (1, 1) and _pair(pool.dilation) == (1, 1) and not pool.ceil_mode and not pool.return_indices)
+
+    @classmethod
+    def swap(cls, net, enable: bool = True) -> bool:
+        """Fuses the stem of `net` (matches) or, enable off, puts the three original modules back -> whether anything changed."""
+        mods = cls._find(net)
+        if mods is None:
+            return False
+        if enable:
+            if not cls.matches(net):
+                return False
+            head = cls(*mods)
+            for i, (name, m) in enumerate(zip(cls._SLOTS, mods)):
+                setattr(net, name, head if i == 0 else _Stem7Pass(m, head, last=i == 2))
+            return True
+        changed = False
+        for name, m in zip(cls._SLOTS, mods):
+            if isinstance(m, (Stem7Fused, _Stem7Pass)):
+                setattr(net, name, m._orig)
+                changed = True
+        return changed
+
+    _fold_tensors = StemFused._fold_tensors
+
+    def _native_ok(self, x) -> bool:
+        if self.training or self._bn.training or ag.needs_grad(self, x) or ag.needs_grad(self._bn):
+            return False
+        return _stem7_input_ok(x, self._fold_tensors(), self._orig.out_channels, 2, True)
+
+    def _pack(self):
+        """The pack of fold_batchnorm(conv1, bn1), cached until a parameter or a running buffer changes (StemFused._folded's key)."""
+        ts = self._fold_tensors()
+        key = tuple((t.data_ptr(), t._version) for t in ts) + (str(ts[0].device), ops.weight_epoch())
+        hit = self.__dict__.get("_mphip_fold")
+        if hit is None or hit[0] != key or ops.repacking():
+            with torch.no_grad():
+                hit = (key, ops.PackedConv2dStem7(*fold_batchnorm(self._orig, self._bn)))
+            self.__dict__["_mphip_fold"] = hit
+        return hit[1]
+
+    def forward(self, x):
+        if not self._native_ok(x):
+            return self._orig(x)   # 4-D: bn1 and maxpool run as the modules they are
+        y = ops.conv2d_stem7(_f32(x), self._pack(), stride=2, relu=True, pool=True, want_range=True)
+        self.__dict__["_mphip_kept"] = (ops.tensor_range(y), tuple(y.shape), y.device)
+        y5 = y.unsqueeze(0)
+        y5._mphip_stem7 = self   # bn1 hands it through; F.relu drops the mark and keeps the shape, which maxpool recognises
+        return y5
+
+
+def native_eapp_stems(eapp: nn.Module, enable: bool = True) -> bool:
+    """Swaps the two 7x7 convs that read Eapp's source image (this package's Eapp or the reference's, model.py:209 and 140-160) for their
+    matrix-core forms, or puts the very objects it replaced back: `eapp.conv` becomes a ConvStem7Fused, and the stem `conv1, bn1, maxpool`
+    of `eapp.custom_resnet50` a Stem7Fused with its two stand-ins.  Returns whether anything changed.  Off by default everywhere; opt-in,
+    inference only; independent of native_eapp_trunk and native_eapp_resnet50.  What stays on PyTorch in Eapp's 2-D part: the average and
+    adaptive pools, `conv_1`, `conv_reduce`, `fc`, and the functional ReLU over the pooled stem map."""
+    changed = False
+    conv = getattr(eapp, "conv", None)
+    if enable and ConvStem7Fused.matches(conv):
+        eapp.conv = ConvStem7Fused(conv)
+        changed = True
+    elif not enable and isinstance(conv, ConvStem7Fused):
+        eapp.conv = conv._orig
+        changed = True
+    net = getattr(eapp, "custom_resnet50", None)
+    if isinstance(net, nn.Module):
+        changed |= Stem7Fused.swap(net, enable)
     return changed
 
 

@@ -1574,6 +1574,86 @@ def conv2d_stem(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, relu:
     return tag_range(y, out_range)
 
 
+# ------------------------------------------------------------------ the 7x7 stems on the matrix cores (csrc/conv2d_stem7_f16x3.hip)
+class PackedConv2dStem7:
+    """One 7x7, padding 3 Conv2d from a 3-channel image for ops.conv2d_stem7: OIHW fp32 weight [Co, 3, 7, 7] + bias [Co] (a BatchNorm
+    folded in by the caller), packed lazily into the layout of mphip_pack_conv2d_stem7_weight (include/mphip.h).  The stride is the
+    call's, not the pack's.  `key` is PackedConv2d.key_of(weight, bias): an owner re-creates the object when it differs."""
+
+    __slots__ = ("weight", "bias", "co", "ci", "key", "_packed")
+
+    def __init__(self, weight: torch.Tensor, bias: torch.Tensor):
+        self.key = PackedConv2d.key_of(weight, bias)
+        weight = _req(weight.detach(), "conv2d_stem7 weight")
+        if weight.dim() != 4 or tuple(weight.shape[1:]) != (3, 7, 7):
+            raise RuntimeError(f"PackedConv2dStem7: expected an OIHW [Co, 3, 7, 7] weight, got {tuple(weight.shape)}")
+        if bias is None or tuple(bias.shape) != (weight.shape[0],):
+            raise RuntimeError("PackedConv2dStem7: a bias of Co elements is required")
+        self.co, self.ci = int(weight.shape[0]), 3
+        if _lib.load().mphip_conv2d_stem7_packed_weight_bytes(self.co) == 0:
+            raise RuntimeError(f"PackedConv2dStem7: Co={self.co} unsupported (a multiple of 16, at most 64)")
+        self.weight = weight
+        self.bias = _req(bias.detach(), "conv2d_stem7 bias")
+        self._packed = None
+
+    key_of = staticmethod(PackedConv2d.key_of)
+
+    def packed(self) -> torch.Tensor:
+        if self._packed is None:
+            lib = _lib.load()
+            wp = torch.empty((lib.mphip_conv2d_stem7_packed_weight_bytes(self.co) + 3) // 4, dtype=torch.float32, device=self.weight.device)
+            _lib.check(lib.mphip_pack_conv2d_stem7_weight(_ptr(self.weight), _ptr(wp), self.co, _stream()), "mphip_pack_conv2d_stem7_weight")
+            self._packed = wp
+        return self._packed
+
+
+def conv2d_stem7_supported(n: int, ci: int, co: int, h: int, w: int, stride: int = 1, pool: bool = False) -> bool:
+    """Does ops.conv2d_stem7 take an [n, ci, h, w] image (h, w: the INPUT map) with co output channels (mphip_conv2d_stem7_supported:
+    ci == 3, co % 16 == 0, co <= 64, stride 1 or 2, fewer than 2^31 elements in x and in y)?"""
+    return bool(_lib.load().mphip_conv2d_stem7_supported(int(n), int(ci), int(co), int(h), int(w), int(stride), int(bool(pool))))
+
+
+def conv2d_stem7(x: torch.Tensor, pack: PackedConv2dStem7, stride: int = 1, relu: bool = False, pool: bool = False,
+                 x_range: Optional[torch.Tensor] = None, want_range: bool = False) -> torch.Tensor:
+    """y = conv7x7(x, stride, padding=3) + bias, then an optional ReLU and an optional max_pool2d(3, 2, 1), in one launch on the matrix
+    cores in the f16x3 arithmetic of ops.conv2d (mphip_conv2d_stem7_fwd): x is an NCHW fp32 image with 3 channels, y is
+    [N, Co, ceil(H / stride), ceil(W / stride)], halved (rounding up) once more by the pool.  The operand scale of x comes from x_range,
+    else from the descriptor riding on x, else from one scan of x, which then stays on x as its descriptor: a second stem of the same
+    image does not scan it again.  A channels_last image is copied to NCHW once.  want_range: y comes back tagged with the descriptor of
+    its exact max|y|.  fp32 CUDA tensors only; there is no fallback."""
+    if not isinstance(pack, PackedConv2dStem7):
+        raise RuntimeError(f"conv2d_stem7: expected a PackedConv2dStem7, got {type(pack).__name__}")
+    given = x
+    x = _req(x, "x")
+    if x.dim() != 4 or x.shape[1] != 3:
+        raise RuntimeError(f"conv2d_stem7: input {tuple(x.shape)} is not an [N, 3, H, W] image")
+    if stride not in (1, 2):
+        raise RuntimeError(f"conv2d_stem7: stride = {stride!r} (1 or 2)")
+    lib = _lib.load()
+    (n, ci, h, w), co = x.shape, pack.co
+    if not lib.mphip_conv2d_stem7_supported(n, ci, co, h, w, int(stride), int(bool(pool))):
+        raise RuntimeError(f"conv2d_stem7: unsupported shape N={n} Ci={ci} Co={co} H={h} W={w} stride={stride} pool={bool(pool)} "
+                           f"(there is no fallback)")
+    scanned = None
+    if x_range is None:
+        x_range = current_range(given)   # (x is `given` or its NCHW copy: the same values)
+        if x_range is None:
+            scanned = new_range(x.device)   # the library scans x into the call's workspace: that IS the descriptor of x (any alignment)
+    else:
+        x_range = _req(x_range, "x_range")
+    ho, wo = (h + stride - 1) // stride, (w + stride - 1) // stride
+    if pool:
+        ho, wo = (ho + 1) // 2, (wo + 1) // 2
+    y = torch.empty((n, co, ho, wo), dtype=torch.float32, device=x.device)
+    out_range = new_range(x.device) if want_range else None
+    _lib.check(lib.mphip_conv2d_stem7_fwd(_ptr(x), _ptr(x_range), _ptr(pack.packed()), _ptr(pack.bias), _ptr(y), _ptr(out_range), n, ci, co,
+                                          h, w, int(stride), int(bool(relu)), int(bool(pool)), _ptr(scanned), 0 if scanned is None else scanned.numel() * 4, _stream()),
+               "mphip_conv2d_stem7_fwd")
+    if scanned is not None:
+        tag_range(given, scanned)
+    return tag_range(y, out_range)
+
+
 _GN_UNIT = {}   # (device, C) -> (ones, zeros): gamma and beta of a GroupNorm without parameters
 
 

@@ -58,6 +58,9 @@ def parse(argv=None):
     ap.add_argument("--native-eapp-resnet50", action="store_true",
                     help="run the thirteen bottlenecks of the appearance encoder's ResNet-50 (the identity descriptor) with BatchNorm folded, "
                          "their 1x1 and 3x3 convs on the matrix cores (gbase.Gbase.native_resnet50; inference only, fp32 models; off by default)")
+    ap.add_argument("--native-eapp-stems", action="store_true",
+                    help="run the appearance encoder's two 7x7 stems (conv, and the ResNet-50's conv1-bn1-relu-maxpool) on the matrix cores, "
+                         "one launch each (gbase.Gbase.native_stems; inference only, fp32 models; off by default)")
     ap.add_argument("--native-motion-encoder", action="store_true",
                     help="run the BasicBlocks of the motion encoder's two ResNet-18s with BatchNorm folded and their 3x3 convs on the "
                          "matrix cores (gbase.Gbase.native_motion_encoder; inference only, fp32 models; off by default)")
@@ -204,6 +207,8 @@ def run(job: dict, args, rank: int, world: int) -> List[str]:
         g.native_trunk(**half)
     if args.native_eapp_resnet50:
         g.native_resnet50()
+    if args.native_eapp_stems:
+        g.native_stems()
     if args.native_motion_encoder:
         g.native_motion_encoder(**({"fuse_stem": True} if args.native_fuse_stem else {}),
                                 **({"rotation_net": True} if args.native_rotation_net else {}),
