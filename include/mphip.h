@@ -571,6 +571,9 @@ int mphip_g2d_final_bwd(const float *x, const float *y, const float *dy, const f
  *     y = act( conv(x, w) + bias[co] (+ residual[n,co,h,w]) ),   act = ReLU (relu != 0) or identity
  * The arithmetic is the precision-1 ("f16x3") arithmetic of the 3-D convs: each operand tensor scaled by its own power of two, split
  * into two f16 halves, three f16 products per multiply accumulated in fp32 (~2^-21 relative per term); bias, residual and ReLU in fp32.
+ * Magnitudes: as for the 3-D convs, fp32-class results for 2^-107 <= max|x| <= FLT_MAX, in every 2-D entry below (3x3, two-source, typed,
+ * stride 2, up2, grouped, split-K, pointwise, 7x7 stem): the accumulator is unscaled by 1/scale_w and then by 1/scale_x, never by their
+ * single product, which can underflow where the result is a normal fp32 number (max|w| = 2^-28, max|x| = 2^-98: 2^-153).
  * Out-of-range and non-finite inputs are passed through, not clamped, and counted by mphip_f16x3_saturation_count.  Bitwise
  * reproducible: no floating-point atomics.
  * Shapes: Ci % 16 == 0, Co % 32 == 0, any N, H, W >= 1 (edges are masked), N*Ci*H*W and N*Co*H*W below 2^31 elements; everything else

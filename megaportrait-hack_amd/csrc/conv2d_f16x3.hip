@@ -3,8 +3,8 @@
 //     y = act( conv(x, w) + bias[co] (+ residual[n,co,h,w]) ),   act = ReLU or identity
 //
 // Arithmetic (the 3-D direct kernel's): each operand tensor is scaled by its own power of two and split v*S = hi + lo with split_f16;
-// the product is Wlo*Xhi + Whi*Xhi + Whi*Xlo in the fp32 accumulator of v_mfma_f32_32x32x16_f16; the accumulator is unscaled (a power
-// of two: exact) and bias, residual and ReLU are applied in fp32.  Out-of-range and non-finite inputs are not clamped (split_f16), they
+// the product is Wlo*Xhi + Whi*Xhi + Whi*Xlo in the fp32 accumulator of v_mfma_f32_32x32x16_f16; the accumulator is unscaled (by 1/scale_w,
+// then by 1/scale_x: two powers of two, each exact; their single product can underflow) and bias, residual and ReLU are applied in fp32.  Out-of-range and non-finite inputs are not clamped (split_f16), they
 // are counted in this unit's saturation counter, which mphip_f16x3_saturation_count sums with the others.
 //
 // Tile: a workgroup of 4 waves computes 64 output channels x (16 rows x 16 columns); a wave owns all 64 channels of 4 rows = 2 x 2

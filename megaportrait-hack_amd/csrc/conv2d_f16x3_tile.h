@@ -414,8 +414,9 @@ __device__ __forceinline__ void conv2d_k3_tile(const dtype_t<XDT> *__restrict__ 
 #undef C2_PARK_AFFINE
 #undef C2_WRITE_CHUNK
 
-    // epilogue: unscale (a power of two), bias, residual, ReLU in fp32; stores masked at the ragged edge and past Co
-    const float unscale = SPLIT ? 0.0f : whdr[0] * x_unscale;   // (SPLIT: no header is read)
+    // epilogue: unscale (two powers of two, one after the other: their product can underflow where the result does not), bias, residual,
+    // ReLU in fp32; stores masked at the ragged edge and past Co
+    const Unscale u = {SPLIT ? 0.0f : whdr[0], x_unscale};   // (SPLIT: no header is read)
     unsigned ymax = 0;
     unsigned ro[2][4];          // UP = 2: this lane's four offsets into a channel of r, per column tile, ...
     float rlam[2], rmu = 0.0f;  // ... and its weights
@@ -447,7 +448,7 @@ __device__ __forceinline__ void conv2d_k3_tile(const dtype_t<XDT> *__restrict__ 
                             y[(size_t)blockIdx.z * part_stride + oi] = acc[m][t][reg];
                             continue;
                         }
-                        float v = acc[m][t][reg] * unscale + bias[co0 + 4 * kg + row];
+                        float v = unscaled(acc[m][t][reg], u, bias[co0 + 4 * kg + row]);
                         if constexpr (UP == 2) {   // + up2(r): the blend, then one add
                             const float *const rc = residual + ((size_t)n * Co + co0 + 4 * kg + row) * ((size_t)xh * xw);
                             v += up2_blend(rc[ro[t][0]], rc[ro[t][1]], rc[ro[t][2]], rc[ro[t][3]], rmu, rlam[t]);

@@ -260,8 +260,9 @@ conv2d_pw_f16x3_kernel(const float *__restrict__ x, const float *__restrict__ x_
 #undef PW_STAGE
 #undef PW_WRITE_CHUNK
 
-    // epilogue (the 3x3 kernels'): unscale (a power of two), bias, residual, ReLU in fp32; stores masked past the image's last pixel and past Co
-    const float unscale = whdr[0] * x_unscale;
+    // epilogue (the 3x3 kernels'): unscale (two powers of two, one after the other), bias, residual, ReLU in fp32; stores masked past the
+    // image's last pixel and past Co
+    const Unscale u = {whdr[0], x_unscale};
     unsigned ymax = 0;
 #pragma unroll
     for (int m = 0; m < 2; ++m) {
@@ -276,7 +277,7 @@ conv2d_pw_f16x3_kernel(const float *__restrict__ x, const float *__restrict__ x_
                     for (int reg = 0; reg < 16; ++reg) {
                         const int row = (reg & 3) + 8 * (reg >> 2);
                         const size_t oi = o + (size_t)row * HWo;
-                        float v = acc[m][t][reg] * unscale + bias[co0 + 4 * kg + row];
+                        float v = unscaled(acc[m][t][reg], u, bias[co0 + 4 * kg + row]);
                         if (residual) v += residual[oi];
                         if (relu) v = v < 0.0f ? 0.0f : v;   // (keeps NaN, like torch's relu)
                         y[oi] = v;

@@ -173,8 +173,9 @@ conv2d_k3s2_f16x3_kernel(const float *__restrict__ x, const float *__restrict__ 
 #undef S2_LOAD_CHUNK
 #undef S2_WRITE_CHUNK
 
-    // epilogue (the stride-1 kernel's): unscale (a power of two), bias, residual, ReLU in fp32; stores masked at the ragged edge and past Co
-    const float unscale = whdr[0] * x_unscale;
+    // epilogue (the stride-1 kernel's): unscale (two powers of two, one after the other), bias, residual, ReLU in fp32; stores masked at the
+    // ragged edge and past Co
+    const Unscale u = {whdr[0], x_unscale};
     unsigned ymax = 0;
     const int gh = h0 + prow, gw = w0 + pcol;
 #pragma unroll
@@ -186,7 +187,7 @@ conv2d_k3s2_f16x3_kernel(const float *__restrict__ x, const float *__restrict__ 
             for (int reg = 0; reg < 16; ++reg) {
                 const int row = (reg & 3) + 8 * (reg >> 2);
                 const size_t oi = o + (size_t)row * HWo;
-                float v = acc[m][reg] * unscale + bias[co0 + 4 * kg + row];
+                float v = unscaled(acc[m][reg], u, bias[co0 + 4 * kg + row]);
                 if (residual) v += residual[oi];
                 if (relu) v = v < 0.0f ? 0.0f : v;   // (keeps NaN, like torch's relu)
                 y[oi] = v;

@@ -9,7 +9,8 @@
 //             index of the unsplit kernels, and stores its raw fp32 accumulators to part[z][N,Co,H,W], masked at the ragged edge and past
 //             Co.  Nothing is unscaled; bias, residual, ReLU and out_range are the finish kernel's.
 //   finish    elementwise over N * Co * H * W:  a = part[0];  a = a + part[z] for z = 1 .. splits - 1, in that order;  then the plain
-//             epilogue term by term (-ffp-contract=off):  v = a * unscale + bias[co],  v += residual,  ReLU that keeps NaN,  the store.
+//             epilogue term by term (-ffp-contract=off):  v = (a * 1/scale_w) * 1/scale_x + bias[co]  (unscaled(): two powers of two, one
+//             after the other),  v += residual,  ReLU that keeps NaN,  the store.
 //             out_range as conv2d_run makes it for every entry: an init launch, then one integer atomicMax per workgroup into
 //             min(workgroups, 4096) slots.  A 16-byte path (H * W % 4 == 0 and part, residual, y on 16-byte boundaries) and a scalar one.
 // Contract.  Power-of-two scales commute with fp32 rounding away from underflow and overflow, so with one descriptor of x and one header
@@ -34,8 +35,8 @@ conv2d_k3_split_f16x3_kernel(const float *__restrict__ x, const float *__restric
 
 constexpr int C2F_NTHR = 256, C2F_PER = 4;   // the finish kernel: elements per thread
 
-__device__ __forceinline__ float c2_finish_one(float a, float unscale, float b, const float *__restrict__ residual, unsigned i, int relu) {
-    float v = a * unscale + b;
+__device__ __forceinline__ float c2_finish_one(float a, Unscale u, float b, const float *__restrict__ residual, unsigned i, int relu) {
+    float v = unscaled(a, u, b);
     if (residual) v += residual[i];
     if (relu) v = v < 0.0f ? 0.0f : v;   // (keeps NaN, like torch's relu)
     return v;
@@ -52,7 +53,7 @@ conv2d_split_finish_kernel(const float *__restrict__ part, size_t part_stride, i
     __shared__ unsigned red[C2F_NTHR / 64];
     float x_scale, x_unscale;
     range_scale_block(x_range, x_scale, x_unscale);   // the descriptor the partial launch staged x with
-    const float unscale = whdr[0] * x_unscale;
+    const Unscale u = {whdr[0], x_unscale};   // two powers of two, applied one after the other (csrc/mphip_f16x3.h)
     const unsigned tid = threadIdx.x;
     unsigned ymax = 0;
     if constexpr (VEC) {
@@ -70,7 +71,7 @@ conv2d_split_finish_kernel(const float *__restrict__ part, size_t part_stride, i
             f32x4 v;
 #pragma unroll
             for (int e = 0; e < C2F_PER; ++e) {
-                float t = a[e] * unscale + b;
+                float t = unscaled(a[e], u, b);
                 if (residual) t += r[e];
                 if (relu) t = t < 0.0f ? 0.0f : t;   // (keeps NaN, like torch's relu)
                 v[e] = t;
@@ -85,7 +86,7 @@ conv2d_split_finish_kernel(const float *__restrict__ part, size_t part_stride, i
             if (i < n) {
                 float a = part[i];
                 for (int z = 1; z < splits; ++z) a = a + part[(size_t)z * part_stride + i];
-                const float v = c2_finish_one(a, unscale, bias[(i / HW) % Co], residual, i, relu);
+                const float v = c2_finish_one(a, u, bias[(i / HW) % Co], residual, i, relu);
                 y[i] = v;
                 ymax = max(ymax, range_bits(v));
             }

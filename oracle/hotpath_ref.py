@@ -68,6 +68,67 @@ def round_f16_at_scale(x: torch.Tensor, top: int = 14) -> torch.Tensor:
     return (x.detach().float() * s).half().double() / s
 
 
+def split_f16_at_scale(v: torch.Tensor, top: int = 14, scale: float = None):
+    """(hi, lo, s): the two f16 halves of v * s as the split-f16 kernels form them (csrc/mphip_f16x3.h split_f16: hi = rne_f16(v * s),
+    lo = rne_f16(v * s - hi), both in fp32), returned UNSCALED in float64, and the power-of-two operand scale s (pow2_operand_scale of
+    max|v| unless `scale` is given: a descriptor that bounds the tensor fixes it)."""
+    s = pow2_operand_scale(v.detach().abs().max().item(), top) if scale is None else float(scale)
+    vs = v.detach().float() * s
+    hi = vs.half()
+    lo = (vs - hi.float()).half()
+    return hi.double() / s, lo.double() / s, s
+
+
+def conv_f16x3_contract(x, w, conv, products: int = 3, x_scale: float = None):
+    """The arithmetic contract of the direct-domain split-f16 convs (the 2-D forms), without any implementation's accumulation order:
+    x split at the activations' scale (top 14, or `x_scale`), w at the weights' (top 15), the products Wlo*Xhi + Whi*Xhi + Whi*Xlo
+    (products = 1: Whi*Xhi alone, the autocast policy) summed exactly in float64, the unscale exact.  `conv(x64, w64)` is the form's own
+    bilinear map (stride, padding, groups), without bias."""
+    assert products in (1, 3)
+    xh, xl, _ = split_f16_at_scale(x, 14, x_scale)
+    wh, wl, _ = split_f16_at_scale(w, 15)
+    if products == 1:
+        return conv(xh, wh)
+    return conv(xh, wl) + conv(xh, wh) + conv(xl, wh)
+
+
+def _exact_gen(seed: int) -> torch.Generator:
+    return torch.Generator().manual_seed(seed)
+
+
+def exact_ints(shape, top: int, seed: int) -> torch.Tensor:
+    """Integers in [-top, top] that contain `top` (the operand scale is fixed whatever the draw), fp32."""
+    t = torch.randint(-top, top + 1, tuple(shape), generator=_exact_gen(seed)).float()
+    t.view(-1)[0] = float(top)
+    return t
+
+
+def lo_plane_operand(shape, frac_bits: int, seed: int) -> torch.Tensor:
+    """a + b * 2^-frac_bits with a integers in [-4, 4] containing a 4 and b integers in (-2^(frac_bits-1), 2^(frac_bits-1)), fp32:
+    max|v| lies in [4, 4.5), so v * 2^frac_bits is an integer of up to frac_bits + 3 bits that one f16 cannot hold and hi + lo holds
+    exactly.  frac_bits = 11 is the "X-lo" activation (scale 2^11), 12 the "W-lo" weight (scale 2^12)."""
+    g = _exact_gen(seed)
+    a = torch.randint(-4, 5, tuple(shape), generator=g).double()
+    m = 2 ** (frac_bits - 1) - 1
+    b = torch.randint(-m, m + 1, tuple(shape), generator=g).double()
+    a.view(-1)[0] = 4.0
+    v = (a + b * 2.0 ** -frac_bits).float()
+    assert torch.equal(v.double(), a + b * 2.0 ** -frac_bits)
+    return v
+
+
+def lo_plane_pair(kind: str, x_shape, w_shape, x_top: int, seed: int):
+    """(x, w) of one of the two data kinds that make the lo planes of the split-f16 2-D convs exact:
+      "xlo": x = lo_plane_operand(11 fractional bits), w integers in [-x_top, x_top]  -> Whi*Xlo carries bits, Wlo = 0;
+      "wlo": w = lo_plane_operand(12 fractional bits), x integers in [-x_top, x_top]  -> Wlo*Xhi carries bits, Xlo = 0.
+    `x_top` is the bound of the INTEGER operand (Wm or Xm), chosen by the caller so that sum |w||x| stays below 2^24 units of 2^-11
+    ("xlo") or 2^-12 ("wlo")."""
+    if kind == "xlo":
+        return lo_plane_operand(x_shape, 11, seed), exact_ints(w_shape, x_top, seed + 1)
+    assert kind == "wlo", kind
+    return exact_ints(x_shape, x_top, seed), lo_plane_operand(w_shape, 12, seed + 1)
+
+
 def conv3d_wino_f16_contract(x, w, b=None, padding=1):
     """The arithmetic contract of the F(2,3) conv kernels under the autocast policy (mphip_conv3d_set_half_products), stated without any
     implementation's accumulation order: k = 3, padding = 1, W even.  Along W the 3-tap filter runs in the Winograd F(2,3) domain; what
