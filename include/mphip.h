@@ -41,7 +41,7 @@ extern "C" {
 
 /* ABI version of this header.  Bumped whenever an exported signature or a packed layout changes; mphip_version() returns the
  * value the LIBRARY was built with — compare the two after dlopen (the ctypes binding does, and refuses a mismatch). */
-#define MPHIP_ABI_VERSION 29
+#define MPHIP_ABI_VERSION 30
 int mphip_version(void);
 /* hipGraph hygiene (ABI 13).  On ROCm 7.x a MEMSET node of a captured hipGraph is not reliably ordered with its neighbouring kernel nodes
  * (observed twice: stale f16x3 pack headers, r03; a training step's loss that kept its previous value, r04-r05 — ATen's multi-block
@@ -810,6 +810,35 @@ size_t mphip_conv2d_split_workspace_bytes(int N, int Ci, int Co, int H, int W, i
 int mphip_conv2d_split_fwd(const float *x, const float *x_range, const void *w_packed, const float *bias, const float *residual, float *y,
                            float *out_range, int N, int Ci, int Co, int H, int W, int groups, int splits, int relu, void *workspace,
                            size_t workspace_bytes, void *stream);
+
+/* The backward of nn.Conv2d(Ci, Co, 3, stride=1, padding=1) on the matrix cores (ABI 30; csrc/conv2d_bwd_f16x3.hip), NCHW fp32, f16x3
+ * arithmetic (three f16 products per multiply, fp32 accumulation), for training through G2d's ResBlock2D body.
+ *   backward-weight: dW[co][ci][kh][kw] = sum_{n,h,w} dY[n][co][h][w] * X[n][ci][h+kh-1][w+kw-1] (zero padding) -> dw [Co,Ci,3,3].
+ *          x is scaled from x_range (NULL: the library scans x into the workspace, as mphip_conv2d_fwd does), dy by dy_scale, the 4
+ *          floats mphip_grad_prep(dy, dbias, dy_scale, N, Co, H * W, ...) writes (the same pass yields the bias gradient).  Non-finite
+ *          values propagate unclamped.  The sum over pixels is split into fp32 slabs in the workspace (plain stores, every element; no
+ *          atomics, no memset) that a second launch adds in order and unscales by 1 / scale_dy, then 1 / scale_x: results are
+ *          bit-reproducible, and both launches go to `stream`, so the call can be captured.
+ *          Shapes (mphip_conv2d_bwd_weight_supported): mphip_conv2d_supported's rule, Ci % 16 == 0, Co % 32 == 0, N, H, W >= 1, fewer
+ *          than 2^31 elements per tensor; edges, ragged tiles and ragged channel blocks are masked.
+ *          Workspace: mphip_conv2d_bwd_weight_workspace_bytes (0 for a refused shape), 4-byte aligned, always required.
+ *          Refusals, all before the first HIP call: null x, dy, dy_scale or dw, a refused shape (MPHIP_EINVAL); a null or short workspace
+ *          (MPHIP_EWORKSPACE); pointers off 4-byte alignment, and, when W % 8 == 0 (rows are read with 16-byte loads), x or dy off
+ *          16-byte alignment (MPHIP_EINVAL).  Messages name conv2d_bwd_weight.
+ *   backward-data: mphip_conv2d_fwd itself on dy with the pack mphip_pack_conv2d_weight_bwd_data makes, a zero bias of Ci floats, no
+ *          residual, no ReLU, and x_range = dy_scale (an explicit-scale descriptor: 4 floats suffice).
+ *   mphip_pack_conv2d_weight_bwd_data: w_oihw [Co,Ci,3,3] -> the ordinary pack (mphip_pack_conv2d_weight's layout) of the flipped,
+ *          transposed weight wT[ci][co][2-kh][2-kw], mphip_conv2d_packed_weight_bytes(Ci, Co) bytes.  The roles swap: it needs
+ *          Co % 16 == 0 and Ci % 32 == 0 (that size is 0 otherwise, the call MPHIP_EINVAL).
+ *   mphip_debug_conv2d_bwd_weight_plan (tests only): the launcher's own decision, out = { kernel, splits, pixel tiles per split, pixel
+ *          tiles }; kernel 0: the shape is refused, 1: the 16-byte-load instantiation (W % 8 == 0), 2: the masked one.  Pixel tiles are
+ *          8 x 8, per sample; (channel blocks of 64 x 64) x splits fills 512 workgroups.  Returns 1 (0: out is NULL).             */
+int mphip_conv2d_bwd_weight_supported(int N, int Ci, int Co, int H, int W);
+size_t mphip_conv2d_bwd_weight_workspace_bytes(int N, int Ci, int Co, int H, int W);
+int mphip_conv2d_bwd_weight(const float *x, const float *x_range, const float *dy, const float *dy_scale, float *dw, int N, int Ci, int Co,
+                            int H, int W, void *workspace, size_t workspace_bytes, void *stream);
+int mphip_pack_conv2d_weight_bwd_data(const float *w_oihw, void *w_packed, int Co, int Ci, void *stream);
+int mphip_debug_conv2d_bwd_weight_plan(int N, int Ci, int Co, int H, int W, int out[4]);
 
 /* The reference's reduced-precision policy for the convs (train.py:145,188: the generator step runs under torch.cuda.amp.autocast(), its
  * conv3d calls take f16 operands with fp32 accumulation).  mphip_conv3d_set_half_products(1) makes the CALLING THREAD's subsequent precision-1

@@ -189,6 +189,12 @@ SIGNATURES = {
     "mphip_conv2d_splits": (_i, [_i] * 6),
     "mphip_conv2d_split_workspace_bytes": (_sz, [_i] * 7),
     "mphip_conv2d_split_fwd": (_i, [_p] * 7 + [_i] * 8 + [_p, _sz, _p]),
+    # the backward of the 3x3 conv (ABI 30, csrc/conv2d_bwd_f16x3.hip)
+    "mphip_conv2d_bwd_weight_supported": (_i, [_i] * 5),
+    "mphip_conv2d_bwd_weight_workspace_bytes": (_sz, [_i] * 5),
+    "mphip_conv2d_bwd_weight": (_i, [_p] * 5 + [_i] * 5 + [_p, _sz, _p]),
+    "mphip_pack_conv2d_weight_bwd_data": (_i, [_p, _p, _i, _i, _p]),
+    "mphip_debug_conv2d_bwd_weight_plan": (_i, [_i] * 5 + [ctypes.POINTER(ctypes.c_int)]),
     "mphip_build_flags": (_i, []),
     "mphip_graph_memsets_to_kernels": (_i, [_p, ctypes.POINTER(ctypes.c_int)]),
     "mphip_graph_memset_nodes_left": (_i, [_p, ctypes.POINTER(ctypes.c_int)]),
@@ -203,7 +209,7 @@ _lib = None
 # The ABI version the SIGNATURES table above mirrors.  Checked against the library at load time, and against include/mphip.h by
 # tests/test_host.py — NOT read from the header at run time: a relocated / installed package ships libmphip.so without the repository's
 # include/ directory.
-EXPECTED_ABI_VERSION = 29
+EXPECTED_ABI_VERSION = 30
 
 
 def header_abi_version() -> int:

@@ -74,6 +74,73 @@ class Conv3dFn(torch.autograd.Function):
         return dx, dw, db, None, None, None
 
 
+def conv2d_packs(conv, need_dx: bool):
+    """(forward pack, backward-data pack or None) of an nn.Conv2d 3x3 for Conv2dFn, cached on the module per weight version like the
+    other packs (PackedConv2d.key_of) and rebuilt when a parameter changes.  The backward-data pack is the flipped, transposed weight's
+    (`PackedConv2d(W, None, transposed=True)`); it is only built when dx is wanted."""
+    out = []
+    for attr, transposed in (("_mphip_pack2d", False), ("_mphip_bwd_pack2d", True)):
+        if transposed and not need_dx:
+            out.append(None)
+            continue
+        key = ops.PackedConv2d.key_of(conv.weight, None if transposed else conv.bias)
+        hit = conv.__dict__.get(attr)
+        if hit is None or hit.key != key or ops.repacking():
+            hit = ops.PackedConv2d(conv.weight, None if transposed else conv.bias, transposed=transposed)
+            conv.__dict__[attr] = hit
+        out.append(hit)
+    return tuple(out)
+
+
+class Conv2dFn(torch.autograd.Function):
+    """y = act(conv3x3(x, W) + b (+ residual)), act = ReLU or identity: nn.Conv2d(Ci, Co, 3, stride=1, padding=1) with the epilogue of
+    ops.conv2d, forward (the fp32 entry, three products) and backward on the matrix cores (csrc/conv2d_bwd_f16x3.hip).  fp32 only.
+    `weight` and `bias` are the tensors the gradients go to (parameters, or a differentiable BatchNorm fold of them); fwd_pack is the
+    PackedConv2d of the same values, bwd_pack the transposed one or None (then it is packed from `weight` when dx is asked for).
+    Precondition: the forward reads weight and bias from fwd_pack, not from the tensors, so the pack must hold THEIR values (a pack of
+    other values would give a y, and with it gradients, of another conv); the channel counts are checked, the values are the caller's."""
+
+    @staticmethod
+    @_fwd
+    def forward(ctx, x, weight, bias, residual, relu, fwd_pack, bwd_pack):
+        x = x.contiguous()
+        if (fwd_pack.co, fwd_pack.ci, fwd_pack.transposed) != (weight.shape[0], weight.shape[1], False) or tuple(bias.shape) != (weight.shape[0],):
+            raise RuntimeError(f"Conv2dFn: fwd_pack (Co={fwd_pack.co}, Ci={fwd_pack.ci}) is not a pack of weight {tuple(weight.shape)} and bias {tuple(bias.shape)}")
+        if bwd_pack is not None and (bwd_pack.co, bwd_pack.ci, bwd_pack.transposed) != (weight.shape[1], weight.shape[0], True):
+            raise RuntimeError(f"Conv2dFn: bwd_pack is not the transposed pack of weight {tuple(weight.shape)}")
+        x_range = ops._range_for(x)   # the operand scale of x: kept, so that the backward-weight launch reuses the forward's
+        y = ops.conv2d(x, fwd_pack, residual=residual, relu=relu, x_range=x_range, want_range=True)
+        ctx.relu, ctx.x_range, ctx.bwd_pack = bool(relu), x_range, bwd_pack
+        if relu:
+            ctx.save_for_backward(x, weight, y)
+        else:
+            ctx.save_for_backward(x, weight)
+        return y
+
+    @staticmethod
+    @once_differentiable  # no double backward (the reference's losses need none): asking for one raises instead of returning zeros
+    @_bwd
+    def backward(ctx, dy):
+        x, weight = ctx.saved_tensors[:2]
+        need = ctx.needs_input_grad
+        g = dy.contiguous()
+        if ctx.relu:
+            g = g * (ctx.saved_tensors[2] > 0)
+        dx = dw = db = None
+        if need[0] or need[1] or need[2]:
+            db, scale = ops.grad_prep(g, want_bias=need[2])
+            if need[1]:
+                dw = ops.conv2d_bwd_weight(x, g, scale, ctx.x_range)
+            if need[0]:
+                pack_t = ctx.bwd_pack if ctx.bwd_pack is not None else ops.PackedConv2d(weight, None, transposed=True)
+                dx = ops.conv2d_bwd_data(g, pack_t, scale)
+        return dx, dw, db, (g if need[3] else None), None, None, None
+
+
+def conv2d(x, weight, bias, fwd_pack, bwd_pack=None, residual=None, relu=False):
+    return Conv2dFn.apply(x, weight, bias, residual, relu, fwd_pack, bwd_pack)
+
+
 class GroupNormFn(torch.autograd.Function):
     """y = act(GroupNorm(x) * gamma + beta [then * w2 + b2] (+ residual)); act: 0 none, 1 ReLU, 2 tanh(ReLU(.)).
     w2/b2 = AdaptiveGroupNorm's second affine ([1,C,1,1,1], model.py:304-316) or None."""

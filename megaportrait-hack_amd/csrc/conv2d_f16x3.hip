@@ -38,10 +38,12 @@ __global__ void __launch_bounds__(256) conv2d_absmax_kernel(const float *__restr
     }
 }
 
-// one thread = one 16-byte fragment (8 consecutive ci of one co and tap), hi and lo; output channels past Co are zeros
+// one thread = one 16-byte fragment (8 consecutive ci of one co and tap), hi and lo; output channels past Co are zeros.
+// transposed: Co, Ci are the PACK's (the conv it serves maps Ci -> Co) and w is the OIHW weight [Ci][Co][3][3] of the conv whose
+// backward-data that is: element (co, ci, tap) is w[ci][co][8 - tap], the flipped, transposed weight.
 __global__ void __launch_bounds__(256)
 conv2d_pack_kernel(const float *__restrict__ w, _Float16 *__restrict__ out, const unsigned *__restrict__ hdr_in, float *__restrict__ hdr_out,
-                   int Co, int Ci, int total) {
+                   int Co, int Ci, int total, int transposed) {
     const float scale = weight_scale(hdr_in[2]);
     const int nchunks = Ci / C2_KC;
     const int i = blockIdx.x * 256 + threadIdx.x;
@@ -57,7 +59,7 @@ conv2d_pack_kernel(const float *__restrict__ w, _Float16 *__restrict__ out, cons
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
             const int ci = chunk * C2_KC + kg * 8 + e;
-            const float v = cog < Co ? w[((size_t)cog * Ci + ci) * 9 + tap] : 0.0f;
+            const float v = cog >= Co ? 0.0f : transposed ? w[((size_t)ci * Co + cog) * 9 + (8 - tap)] : w[((size_t)cog * Ci + ci) * 9 + tap];
             _Float16 h, l;
             split_f16(v * scale, h, l);
             hi[e] = h; lo[e] = l;
@@ -126,21 +128,33 @@ extern "C" size_t mphip_conv2d_packed_weight_bytes(int Co, int Ci) {
     return c2_packed_bytes(Co, Ci);
 }
 
-extern "C" int mphip_pack_conv2d_weight(const float *w_oihw, void *w_packed, int Co, int Ci, void *stream) {
-    MPHIP_REQUIRE(w_oihw && w_packed, "pack_conv2d_weight: null pointer");
+// the pack of w (transposed == 0) or of its flipped transpose; Co, Ci: the pack's
+static int pack_conv2d_weight(const char *who, const float *w_oihw, void *w_packed, int Co, int Ci, int transposed, void *stream) {
+    MPHIP_REQUIRE(w_oihw && w_packed, "%s: null pointer", who);
     MPHIP_REQUIRE(Ci >= C2_KC && Co >= 32 && Ci % C2_KC == 0 && Co % 32 == 0 && c2_cots(Co) <= 65535,
-                  "pack_conv2d_weight: Co = %d, Ci = %d: Ci must be a multiple of 16 and Co a multiple of 32", Co, Ci);
-    MPHIP_REQUIRE(((uintptr_t)w_packed & 15) == 0, "pack_conv2d_weight: w_packed must be 16-byte aligned");
+                  transposed ? "%s: Co = %d, Ci = %d: Co must be a multiple of 16 and Ci a multiple of 32 (the roles swap)"
+                             : "%s: Co = %d, Ci = %d: Ci must be a multiple of 16 and Co a multiple of 32",
+                  who, transposed ? Ci : Co, transposed ? Co : Ci);
+    MPHIP_REQUIRE(((uintptr_t)w_packed & 15) == 0, "%s: w_packed must be 16-byte aligned", who);
     const long long total = (long long)c2_cots(Co) * (Ci / C2_KC) * 9 * 2 * C2_COT;
-    MPHIP_REQUIRE(total < (1ll << 31) - 256, "pack_conv2d_weight: Co = %d, Ci = %d is too large", Co, Ci);
+    MPHIP_REQUIRE(total < (1ll << 31) - 256, "%s: Co = %d, Ci = %d is too large", who, transposed ? Ci : Co, transposed ? Co : Ci);
     hipStream_t s = (hipStream_t)stream;
     zero_fill(w_packed, 16, s);   // header: the absmax kernel accumulates with atomicMax
     const size_t n = (size_t)Co * Ci * 9;
     hipLaunchKernelGGL(conv2d_absmax_kernel, dim3((unsigned)std::min<size_t>(1024, (n + 2047) / 2048)), dim3(256), 0, s, w_oihw, n,
                        (unsigned *)w_packed);
     hipLaunchKernelGGL(conv2d_pack_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, w_oihw,
-                       (_Float16 *)((char *)w_packed + 16), (const unsigned *)w_packed, (float *)w_packed, Co, Ci, (int)total);
-    return check_launch("pack_conv2d_weight");
+                       (_Float16 *)((char *)w_packed + 16), (const unsigned *)w_packed, (float *)w_packed, Co, Ci, (int)total, transposed);
+    return check_launch(who);
+}
+
+extern "C" int mphip_pack_conv2d_weight(const float *w_oihw, void *w_packed, int Co, int Ci, void *stream) {
+    return pack_conv2d_weight("pack_conv2d_weight", w_oihw, w_packed, Co, Ci, 0, stream);
+}
+
+// Co, Ci: those of the conv w_oihw [Co,Ci,3,3] belongs to; the pack is the one of a Co -> Ci conv (mphip_conv2d_packed_weight_bytes(Ci, Co))
+extern "C" int mphip_pack_conv2d_weight_bwd_data(const float *w_oihw, void *w_packed, int Co, int Ci, void *stream) {
+    return pack_conv2d_weight("pack_conv2d_weight_bwd_data", w_oihw, w_packed, Ci, Co, 1, stream);
 }
 
 extern "C" size_t mphip_conv2d_workspace_bytes(int N, int Ci, int Co, int H, int W) {

@@ -396,16 +396,19 @@ class G2d(M.G2dHead):
         M.native_final_conv(self, enable)
         return self
 
-    def native_body(self, enable: bool = True, half_precision: bool = False, fuse_upsample: bool = False) -> "G2d":
-        """Opt-in, inference only: run every ResBlock2D of the body (`res_blocks`, `upsample1/2/3[1]`) as model.ResBlock2DFused —
+    def native_body(self, enable: bool = True, half_precision: bool = False, fuse_upsample: bool = False, trainable: bool = False) -> "G2d":
+        """Opt-in (inference; training with trainable=True): run every ResBlock2D of the body (`res_blocks`, `upsample1/2/3[1]`) as model.ResBlock2DFused —
         BatchNorm folded, the 3x3 convs on the matrix cores with fp32-class accuracy (csrc/conv2d_f16x3.hip) — over the blocks' own
         children: same Parameter objects, same state-dict keys.  `enable=False` puts the original blocks back.  In train mode, under
         autograd or on a half model the fused blocks evaluate the original PyTorch expression.  half_precision (off by default):
         inside torch.autocast(float16), and as a .half() / .bfloat16() model, the fused blocks run one f16 product per multiply and
         return the half dtype (model.ResBlock2DFused).  fuse_upsample (off by default): the three `upsampleK` stages run as
         model.Up2ResBlock2DFused, the bilinear x2 up-sample folded into the block's convs (csrc/conv2d_up2_f16x3.hip) and the 1x1
-        shortcut at low resolution; with half_precision=True the stages keep the materialised up-sample."""
-        M.native_g2d_body(self, enable, half_precision, fuse_upsample)
+        shortcut at low resolution; with half_precision=True the stages keep the materialised up-sample.  trainable (off by default):
+        under autograd the fused blocks stay on the matrix cores, forward and backward (ag.Conv2dFn, csrc/conv2d_bwd_f16x3.hip), in
+        eval mode with the BatchNorms folded differentiably and in train mode around the blocks' own BatchNorm modules; fp32 outside
+        autocast only (model.ResBlock2DFused).  With fuse_upsample a stage under autograd runs its nn.Upsample in PyTorch, then the block."""
+        M.native_g2d_body(self, enable, half_precision, fuse_upsample, trainable)
         return self
 
     def body(self, x):

@@ -58,13 +58,15 @@ class Gbase(M._HotSliceRunner, nn.Module):
         M.native_final_conv(self.G2d, enable)
         return self
 
-    def native_body(self, enable: bool = True, half_precision: bool = False, fuse_upsample: bool = False) -> "Gbase":
-        """Opt-in (off by default), inference only: G2d's ResBlock2D body as model.ResBlock2DFused — BatchNorm folded, 3x3 convs on the
+    def native_body(self, enable: bool = True, half_precision: bool = False, fuse_upsample: bool = False, trainable: bool = False) -> "Gbase":
+        """Opt-in (off by default; inference, and training with trainable=True): G2d's ResBlock2D body as model.ResBlock2DFused — BatchNorm folded, 3x3 convs on the
         matrix cores (model.native_g2d_body); `enable=False` restores the original blocks.  Same parameters and state-dict keys.
         half_precision (off by default): the blocks' one-product form for autocast(float16) regions and half models.
         fuse_upsample (off by default): the three up-sampling stages fold their bilinear x2 up-sample into the block's convs
-        (model.Up2ResBlock2DFused); with half_precision=True they keep the materialised up-sample."""
-        M.native_g2d_body(self.G2d, enable, half_precision, fuse_upsample)
+        (model.Up2ResBlock2DFused); with half_precision=True they keep the materialised up-sample.
+        trainable (off by default): under autograd the fused blocks run forward and backward on the matrix cores (ag.Conv2dFn), fp32
+        outside autocast only; with fuse_upsample an up-sampling stage under autograd runs its nn.Upsample in PyTorch, then the block."""
+        M.native_g2d_body(self.G2d, enable, half_precision, fuse_upsample, trainable)
         return self
 
     def native_trunk(self, enable: bool = True, half_precision: bool = False) -> "Gbase":

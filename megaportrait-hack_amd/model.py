@@ -771,6 +771,37 @@ def _set_half(block: nn.Module, half_precision: bool) -> bool:
     return True
 
 
+def _set_trainable(block: nn.Module, trainable: bool) -> bool:
+    """Records the trainable keyword on a ResBlock2DFused (nothing is stored when it is off: the flag, the block's backward packs and
+    the packs ag.conv2d_packs cached on conv1 and conv2 all go) -> whether it changed."""
+    if bool(block.__dict__.get("_mphip_trainable", False)) == bool(trainable):
+        return False
+    if trainable:
+        block.__dict__["_mphip_trainable"] = True
+    else:
+        block.__dict__.pop("_mphip_trainable", None)
+        block.__dict__.pop("_mphip_fold_bwd", None)
+        for conv in (getattr(block, "conv1", None), getattr(block, "conv2", None)):   # the train-mode packs ag.conv2d_packs left on the convs
+            if conv is not None:
+                conv.__dict__.pop("_mphip_pack2d", None)
+                conv.__dict__.pop("_mphip_bwd_pack2d", None)
+    return True
+
+
+def fold_batchnorm_autograd(conv: nn.Module, bn: nn.Module):
+    """fold_batchnorm's (w', b') with the same operations in the same order (the same bits), but as differentiable functions of
+    conv.weight, conv.bias, bn.weight and bn.bias: the running statistics are constants (eval mode, the fine-tuning case)."""
+    s = bn.weight / torch.sqrt(bn.running_var.detach() + bn.eps)
+    return (conv.weight * s[:, None, None, None]).contiguous(), ((conv.bias - bn.running_mean.detach()) * s + bn.bias).contiguous()
+
+
+class _FoldedConv:
+    """What ag.Conv3dFn asks of its `conv` argument, for a folded 1x1 shortcut: the tensors and a __dict__ for the backward pack."""
+
+    def __init__(self, weight, bias):
+        self.weight, self.bias = weight, bias
+
+
 def _is_conv2d(m, k: int) -> bool:
     return (isinstance(m, nn.Conv2d) and m.kernel_size == (k, k) and m.stride == (1, 1) and m.padding == ((k - 1) // 2,) * 2
             and m.dilation == (1, 1) and m.groups == 1 and m.padding_mode == "zeros" and m.bias is not None)
@@ -853,9 +884,9 @@ class ResBlock2DFused(_FusedBlock2D):
     and buffer objects, the same state-dict keys — built over an existing block by `from_block`.
 
     The native path runs only in eval mode, without autograd (ag.needs_grad false), on an fp32 module and a supported shape (Ci % 16,
-    Co % 32); otherwise forward evaluates the original block's expression in PyTorch, exactly encoders2d.ResBlock2D.forward.  There are
-    NO backward kernels and NO half-model path for this block: training, fine-tuning and .half() / .bfloat16() instances take the
-    PyTorch expression.  fp16 / bf16 inputs (torch.autocast upstream) are widened (model._f32) and the result is fp32; channels_last
+    Co % 32); otherwise forward evaluates the original block's expression in PyTorch, exactly encoders2d.ResBlock2D.forward.  Without
+    `trainable=True` (below) training and fine-tuning take the PyTorch expression, and there is NO half-model path for this block:
+    .half() / .bfloat16() instances take it too.  fp16 / bf16 inputs (torch.autocast upstream) are widened (model._f32) and the result is fp32; channels_last
     inputs are copied to NCHW once.  A 1x1 shortcut runs through the existing k = 1 conv with its BatchNorm folded.  Each conv leaves
     the range descriptor of its output on the tensor, so a fused block that directly follows does not scan its input again.
 
@@ -864,7 +895,19 @@ class ResBlock2DFused(_FusedBlock2D):
     launches, reads its input in the dtype it arrives in and returns float16, bitwise `.half()` of what it computes from `x.float()`
     under ops.half_products(True) outside the region.  A .half() / .bfloat16() block folds its BatchNorms in fp32 from the widened
     parameters, runs one product, reads input and residual and writes the output in the model dtype (y1 stays fp32): bitwise its fp32
-    twin under ops.half_products(True), rounded once.  Everything else takes the paths above."""
+    twin under ops.half_products(True), rounded once.  Everything else takes the paths above.
+
+    `from_block(block, trainable=True)` (off by default; recorded on the block and removed again when off) trains through the block on
+    the matrix cores: a call that ag.needs_grad sends to the PyTorch expression takes ag.Conv2dFn instead (csrc/conv2d_bwd_f16x3.hip:
+    the backward-weight kernel; backward-data is the forward kernel on the flipped, transposed pack).  fp32 modules and fp32 CUDA maps
+    outside autocast only, where ops.conv2d_bwd_supported takes both convs; every other call keeps its path.
+      eval mode (frozen statistics, fine-tuning): each BatchNorm is folded into its conv by differentiable torch ops on every call
+        and the inference path's two launches run, with bias, ReLU and the residual in the epilogue: the output carries the bits of
+        the inference path, and the gradients reach conv.weight, conv.bias, bn.weight and bn.bias through the fold.  A 1x1 shortcut
+        is folded the same way and runs the inference path's k = 1 launch with ag.Conv3dFn's backward kernels.
+      train mode (batch statistics): conv1 and conv2 go through ag.Conv2dFn with their own bias, the block's bn1 / bn2 modules run
+        as they are (running statistics update as before), ReLU, the add and the whole shortcut (1x1 conv + BatchNorm) stay in PyTorch.
+    Half, bf16 and one-product training are not built: inside torch.autocast and on a half block the keyword changes nothing."""
 
     _CHILDREN = ("conv1", "bn1", "conv2", "bn2", "shortcut")
     _EXPECTED = ("a ResBlock2D without downsampling (3x3 stride-1 convs with bias, BatchNorm2d with running statistics, Identity or "
@@ -931,6 +974,80 @@ class ResBlock2DFused(_FusedBlock2D):
         y = F.relu(self.bn1(self.conv1(x)))
         y = self.bn2(self.conv2(y))
         return F.relu(y + self.shortcut(x))
+
+    @classmethod
+    def from_block(cls, block: nn.Module, half_precision: bool = False, trainable: bool = False):
+        new = super().from_block(block, half_precision)
+        _set_trainable(new, trainable)
+        return new
+
+    def _trainable_ok(self, x) -> bool:
+        """trainable=True: does this call take ag.Conv2dFn?  Under autograd only (every other call keeps the paths it has), an fp32
+        module and an fp32 CUDA map outside autocast, and shapes whose forward, backward-weight and (where dx is wanted) backward-data
+        launches the library takes."""
+        if "_mphip_trainable" not in self.__dict__ or not ag.needs_grad(self, x) or self._dtypes(False) != {torch.float32}:
+            return False
+        if not (isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.float32 and x.dim() == 4 and x.numel() > 0):
+            return False
+        if torch.is_autocast_enabled() or ops.half_products_active():
+            return False
+        (n, ci, h, w), co = x.shape, self.conv1.out_channels
+        if not (ci == self.conv1.in_channels and ops.conv2d_bwd_supported(n, ci, co, h, w, bool(x.requires_grad))
+                and ops.conv2d_bwd_supported(n, co, co, h, w, True)):
+            return False
+        if self.training or not isinstance(self.shortcut, nn.Sequential):
+            return True
+        # eval mode runs the 1x1 shortcut through ag.Conv3dFn (k = 1), which raises where the library has no kernel: ask first.  (Where
+        # the f16x3 kernels do not take a shape the exact fp32 ones do, so this holds wherever the 3x3 rules above hold.)
+        lib = ops._lib.load()
+        return bool(lib.mphip_conv3d_supported(n, ci, co, 1, h, w, 1, 0) and lib.mphip_conv3d_supported(n, co, ci, 1, h, w, 1, 0)
+                    and lib.mphip_conv3d_bwd_weight_workspace_bytes(n, ci, co, 1, h, w, 1, 0) and lib.mphip_packed_weight_bytes(ci, co, 1, 0))
+
+    def _folded_bwd(self):
+        """(conv1', conv2', shortcut') backward-data packs of the folded weights (None where the transposed pack's rule refuses the
+        channels, and for an identity shortcut), cached like _folded.  The shortcut's is ag.Conv3dFn's transposed k = 1 PackedConv."""
+        ts = self._fold_tensors()
+        key = tuple((t.data_ptr(), t._version) for t in ts) + (str(ts[0].device), ops.weight_epoch())
+        hit = self.__dict__.get("_mphip_fold_bwd")
+        if hit is None or hit[0] != key or ops.repacking():
+            with torch.no_grad():
+                ws = [fold_batchnorm(conv, bn)[0] for conv, bn in self._fold_pairs()]
+            t3 = ops.PackedConv(ws[2].view(ws[2].shape[0], ws[2].shape[1], 1, 1, 1), None, transposed=True) if len(ws) > 2 else None
+            hit = (key, tuple(ops.PackedConv2d(w, None, transposed=True) if w.shape[0] % 16 == 0 and w.shape[1] % 32 == 0 else None
+                              for w in ws[:2]) + (t3,))
+            self.__dict__["_mphip_fold_bwd"] = hit
+        return hit[1]
+
+    def _train_forward(self, x):
+        """The two paths of trainable=True (class docstring)."""
+        xc = x.contiguous()
+        if self.training:   # batch statistics: the block's own BatchNorm modules run as they are; ReLU, add and shortcut stay in torch
+            f1, b1 = ag.conv2d_packs(self.conv1, bool(x.requires_grad))
+            y = F.relu(self.bn1(ag.conv2d(xc, self.conv1.weight, self.conv1.bias, f1, b1)))
+            f2, b2 = ag.conv2d_packs(self.conv2, True)
+            y = self.bn2(ag.conv2d(y, self.conv2.weight, self.conv2.bias, f2, b2))
+            return F.relu(y + self.shortcut(x))
+        # frozen statistics: the inference path's two launches, on weights folded by differentiable torch ops (the same bits as the
+        # cached fold the packs were made from), so the gradients reach conv.weight, conv.bias, bn.weight and bn.bias through the fold
+        p1, p2, ps = self._folded()
+        t1, t2, ts_ = self._folded_bwd()
+        pairs = self._fold_pairs()
+        (w1, c1), (w2, c2) = (fold_batchnorm_autograd(conv, bn) for conv, bn in pairs[:2])
+        idt = xc
+        if ps is not None:   # the 1x1 shortcut: the inference path's k = 1 launch, with ag.Conv3dFn's backward kernels
+            ws, cs = fold_batchnorm_autograd(*pairs[2])
+            n, c, h, w = xc.shape
+            folded = _FoldedConv(ws.view(ws.shape[0], ws.shape[1], 1, 1, 1), cs)
+            if not ops.repacking():   # the cached backward pack, under the key ag.Conv3dFn's backward looks it up with
+                folded.__dict__["_mphip_bwd_pack"] = (ops._pack_cache_key(folded, "_mphip_bwd_pack"), ts_)
+            idt = ag.conv3d(xc.reshape(n, c, 1, h, w), folded, ps).reshape(n, ps.co, h, w)
+        y1 = ag.conv2d(xc, w1, c1, p1, t1 if x.requires_grad else None, relu=True)
+        return ag.conv2d(y1, w2, c2, p2, t2, residual=idt, relu=True)
+
+    def forward(self, x):
+        if self._trainable_ok(x):
+            return self._train_forward(x)
+        return super().forward(x)
 
     def _launch(self, x, packs, out_dtype, products):
         """Both 3x3 launches and the 1x1 shortcut.  products None: the fp32 path (a half input is widened, the fp32 entry); 0: the
@@ -1282,16 +1399,20 @@ class BottleneckFused(_FusedBlock2D):
         return ops.conv2d_pw(y2, p3, residual=idt, relu=True, want_range=True)
 
 
-def _swap_slot(cls, cur, enable: bool, half_precision: bool):
+def _swap_slot(cls, cur, enable: bool, half_precision: bool, trainable=None):
     """One slot of native_g2d_body / native_eapp_trunk -> (the module the slot holds now, whether anything changed): a matching block
-    becomes a `cls` over the same children, a fused one takes the keyword's value, or (enable off) the very object it replaced comes back."""
+    becomes a `cls` over the same children, a fused one takes the keywords' values, or (enable off) the very object it replaced comes
+    back.  trainable: None for a class without the keyword, else ResBlock2DFused's."""
     if enable and isinstance(cur, cls):
-        return cur, _set_half(cur, half_precision)
+        did = _set_half(cur, half_precision)
+        return cur, (_set_trainable(cur, trainable) or did) if trainable is not None else did
     if enable and cls.matches(cur):
-        new = cls.from_block(cur, half_precision)
+        new = cls.from_block(cur, half_precision) if trainable is None else cls.from_block(cur, half_precision, trainable=trainable)
         new.__dict__["_replaced"] = cur   # (not a registered child: the module tree and the state-dict keys stay as they were)
         return new, True
     if not enable and isinstance(cur, cls) and "_replaced" in cur.__dict__:
+        if trainable is not None:
+            _set_trainable(cur, False)   # (the packs it cached on the children, which the original block shares)
         return cur.__dict__.pop("_replaced"), True
     return cur, False
 
@@ -1299,7 +1420,8 @@ def _swap_slot(cls, cur, enable: bool, half_precision: bool):
 _G2D_BODY_SLOTS = (("upsample1", 1), ("upsample2", 1), ("upsample3", 1))
 
 
-def native_g2d_body(g2d: nn.Module, enable: bool = True, half_precision: bool = False, fuse_upsample: bool = False) -> bool:
+def native_g2d_body(g2d: nn.Module, enable: bool = True, half_precision: bool = False, fuse_upsample: bool = False,
+                    trainable: bool = False) -> bool:
     """Swaps every matching ResBlock2D of `g2d.res_blocks`, `g2d.upsample1[1]`, `upsample2[1]`, `upsample3[1]` (this package's G2d or
     the reference's, model.py:720-746) for a ResBlock2DFused over the same children, or puts the very objects it replaced back.
     Returns whether anything changed.  Off by default everywhere.  half_precision: the blocks' half-precision form (ResBlock2DFused);
@@ -1307,7 +1429,10 @@ def native_g2d_body(g2d: nn.Module, enable: bool = True, half_precision: bool = 
     fuse_upsample (off by default): each matching `Sequential(Upsample x2 bilinear align_corners, block)` of `upsample1/2/3` also becomes
     an Up2ResBlock2DFused over the same two objects, which folds the up-sample into the block's convs; without the keyword (or with
     enable off) the very Sequential objects come back.  With half_precision=True the three stages keep the materialised up-sample:
-    there is no typed or one-product form of the up2 kernels."""
+    there is no typed or one-product form of the up2 kernels.
+    trainable (off by default): under autograd the fused blocks run ag.Conv2dFn, forward and backward on the matrix cores
+    (ResBlock2DFused); blocks that are fused already take the keyword's value.  Up2ResBlock2DFused is not touched: under autograd a
+    stage evaluates its two modules in order as before, the nn.Upsample in PyTorch and then the block, which takes its own path."""
     fuse = bool(enable and fuse_upsample and not half_precision)
     changed = False
     if not fuse:   # (first: the slots below are looked up in the Sequentials that hold them)
@@ -1321,7 +1446,7 @@ def native_g2d_body(g2d: nn.Module, enable: bool = True, half_precision: bool = 
         if not isinstance(seq, nn.Sequential):
             continue
         for i in (range(len(seq)) if only is None else [only] if len(seq) > only else []):
-            new, did = _swap_slot(ResBlock2DFused, seq[i], enable, half_precision)
+            new, did = _swap_slot(ResBlock2DFused, seq[i], enable, half_precision, bool(trainable))
             if new is not seq[i]:
                 seq[i] = new
             changed |= did

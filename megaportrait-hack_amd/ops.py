@@ -1257,24 +1257,34 @@ class PackedConv2d:
     groups > 1: the weight is torch's grouped [Co, Ci / groups, 3, 3]; `ci` stays the conv's input channel count, the pack is the ordinary
     one of a [Co, Ci / groups] weight, and only ops.conv2d_grouped takes it.
     A 1x1 weight ([Co, Ci, 1, 1], groups == 1) makes a `pointwise` pack: the layout of mphip_pack_conv2d_pw_weight, which only
-    ops.conv2d_pw takes (PackedConv2dPW is this class under the name its users read); key and lazy packing are the same."""
+    ops.conv2d_pw takes (PackedConv2dPW is this class under the name its users read); key and lazy packing are the same.
+    transposed=True (3x3, groups == 1, bias ignored): the pack of the flipped, transposed weight wT[ci][co][2-kh][2-kw]
+    (mphip_pack_conv2d_weight_bwd_data) with a zero bias: the conv Co -> Ci that ops.conv2d_bwd_data runs on dy.  `co` and `ci` are
+    those of THAT conv (the roles swap: the weight's Co % 16 == 0 and Ci % 32 == 0 are required); `weight` stays the OIHW tensor."""
 
-    __slots__ = ("weight", "bias", "co", "ci", "groups", "key", "pointwise", "_packed")
+    __slots__ = ("weight", "bias", "co", "ci", "groups", "key", "pointwise", "transposed", "_packed")
 
-    def __init__(self, weight: torch.Tensor, bias: torch.Tensor, groups: int = 1):
-        self.key = PackedConv2d.key_of(weight, bias)
+    def __init__(self, weight: torch.Tensor, bias: Optional[torch.Tensor], groups: int = 1, transposed: bool = False):
+        self.transposed = bool(transposed)
+        if self.transposed:
+            if weight.dim() != 4 or tuple(weight.shape[2:]) != (3, 3) or int(groups) != 1:
+                raise RuntimeError(f"PackedConv2d: transposed=True takes an OIHW 3x3 weight with groups = 1, got {tuple(weight.shape)}, groups = {groups!r}")
+            bias = torch.zeros(weight.shape[1], dtype=torch.float32, device=weight.device)
+        self.key = PackedConv2d.key_of(weight, None if self.transposed else bias)
         weight = _req(weight.detach(), "conv2d weight")
         if weight.dim() != 4 or tuple(weight.shape[2:]) not in ((3, 3), (1, 1)):
             raise RuntimeError(f"PackedConv2d: expected an OIHW 3x3 or 1x1 weight, got {tuple(weight.shape)}")
         self.pointwise = tuple(weight.shape[2:]) == (1, 1)
         if self.pointwise and int(groups) != 1:
             raise RuntimeError(f"PackedConv2d: a 1x1 weight with groups = {groups!r}: the pointwise form has no groups")
-        if bias is None or tuple(bias.shape) != (weight.shape[0],):
+        if bias is None or tuple(bias.shape) != (weight.shape[1 if self.transposed else 0],):
             raise RuntimeError("PackedConv2d: a bias of Co elements is required")
         self.groups = int(groups)
         if self.groups < 1:
             raise RuntimeError(f"PackedConv2d: groups = {groups!r}")
         self.co, self.ci = int(weight.shape[0]), int(weight.shape[1]) * self.groups
+        if self.transposed:
+            self.co, self.ci = self.ci, self.co
         if _lib.load().mphip_conv2d_packed_weight_bytes(self.co, self.ci // self.groups) == 0:
             raise RuntimeError(f"PackedConv2d: Co={self.co} Ci={self.ci} groups={self.groups} unsupported (Ci / groups % 16 == 0 and Co % 32 == 0 "
                                f"are required)")
@@ -1295,7 +1305,11 @@ class PackedConv2d:
                                 if self.pointwise else
                                 (lib.mphip_conv2d_packed_weight_bytes, lib.mphip_pack_conv2d_weight, "mphip_pack_conv2d_weight"))
             wp = torch.empty((size(self.co, cig) + 3) // 4, dtype=torch.float32, device=self.weight.device)
-            _lib.check(pack(_ptr(self.weight), _ptr(wp), self.co, cig, _stream()), name)
+            if self.transposed:   # (the entry takes the WEIGHT's Co, Ci)
+                _lib.check(lib.mphip_pack_conv2d_weight_bwd_data(_ptr(self.weight), _ptr(wp), self.ci, self.co, _stream()),
+                           "mphip_pack_conv2d_weight_bwd_data")
+            else:
+                _lib.check(pack(_ptr(self.weight), _ptr(wp), self.co, cig, _stream()), name)
             self._packed = wp
         return self._packed
 
@@ -1720,6 +1734,61 @@ def conv2d_cat(x1: torch.Tensor, pack: PackedConv2d, x2: Optional[torch.Tensor] 
     r2 = x2_range if (x2_range is not None or affine2 is not None or x2 is None) else current_range(x2)
     return _conv2d_launch(_CONV2D_FORMS["cat"], typed, pack, x1, r1, residual, relu, want_range, out_dtype, products,
                           second=(affine1, relu1, x2, affine2, r2, relu2))
+
+
+# ------------------------------------------------------------------ the 3x3 conv's backward (csrc/conv2d_bwd_f16x3.hip)
+def conv2d_bwd_weight_supported(n: int, ci: int, co: int, h: int, w: int) -> bool:
+    """Does ops.conv2d_bwd_weight take x [n, ci, h, w] and dy [n, co, h, w] (mphip_conv2d_bwd_weight_supported: the forward's rule)?"""
+    return bool(_lib.load().mphip_conv2d_bwd_weight_supported(int(n), int(ci), int(co), int(h), int(w)))
+
+
+def conv2d_bwd_supported(n: int, ci: int, co: int, h: int, w: int, need_dx: bool) -> bool:
+    """Can a conv Ci -> Co on an [n, ci, h, w] map run forward and backward on the matrix cores: the forward's rule, the
+    backward-weight rule and, when dx is wanted, the transposed pack's (the roles swap: co % 16 == 0 and ci % 32 == 0) with the forward's
+    rule for the backward-data conv Co -> Ci?"""
+    lib = _lib.load()
+    n, ci, co, h, w = int(n), int(ci), int(co), int(h), int(w)
+    if not (lib.mphip_conv2d_supported(n, ci, co, h, w) and lib.mphip_conv2d_bwd_weight_supported(n, ci, co, h, w)):
+        return False
+    return not need_dx or bool(lib.mphip_conv2d_packed_weight_bytes(ci, co) and lib.mphip_conv2d_supported(n, co, ci, h, w))
+
+
+def _aligned16(t: torch.Tensor) -> torch.Tensor:
+    """t, or a copy that starts on a 16-byte boundary (a contiguous view at an odd storage offset is copied once)"""
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
+def conv2d_bwd_weight(x: torch.Tensor, dy: torch.Tensor, dy_scale: torch.Tensor, x_range: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """dW [Co,Ci,3,3] of y = conv2d(x, W, b, padding=1) given dy (mphip_conv2d_bwd_weight: f16x3 arithmetic, an ordered split over
+    pixels: the same bits on every run).  dy_scale: the scale ops.grad_prep(dy) returns.  x_range: the descriptor the forward used for
+    x; without one the descriptor tagged on x is used, else the library scans x.  There is no fallback: a shape outside
+    conv2d_bwd_weight_supported is a RuntimeError."""
+    x, dy, dy_scale = _req(x, "x"), _req(dy, "dy"), _req(dy_scale, "dy_scale")
+    if x.dim() != 4 or dy.dim() != 4 or (dy.shape[0],) + tuple(dy.shape[2:]) != (x.shape[0],) + tuple(x.shape[2:]):
+        raise RuntimeError(f"conv2d_bwd_weight: dy {tuple(dy.shape)} does not match x {tuple(x.shape)}")
+    if dy_scale.numel() < 4:
+        raise RuntimeError("conv2d_bwd_weight: dy_scale is the 4-float scale of ops.grad_prep")
+    n, ci, h, w = x.shape
+    co = dy.shape[1]
+    lib = _lib.load()
+    ws_bytes = lib.mphip_conv2d_bwd_weight_workspace_bytes(n, ci, co, h, w)
+    if ws_bytes == 0:
+        raise RuntimeError(f"conv2d_bwd_weight: unsupported shape N={n} Ci={ci} Co={co} H={h} W={w} (there is no fallback)")
+    xr = x_range if x_range is not None else current_range(x)   # None: the library scans x
+    x, dy = _aligned16(x), _aligned16(dy)   # (W % 8 == 0: the kernel reads rows with 16-byte loads and the entry refuses other pointers)
+    ws = torch.empty((ws_bytes + 3) // 4, dtype=torch.float32, device=x.device)
+    dw = torch.empty((co, ci, 3, 3), dtype=torch.float32, device=x.device)
+    _lib.check(lib.mphip_conv2d_bwd_weight(_ptr(x), _ptr(xr), _ptr(dy), _ptr(dy_scale), _ptr(dw), n, ci, co, h, w, _ptr(ws), ws_bytes,
+                                           _stream()), "mphip_conv2d_bwd_weight")
+    return dw
+
+
+def conv2d_bwd_data(dy: torch.Tensor, pack_t: PackedConv2d, dy_scale: torch.Tensor) -> torch.Tensor:
+    """dx of y = conv2d(x, W, b, padding=1): ops.conv2d on dy with the pack of the flipped, transposed weight
+    (`PackedConv2d(W, None, transposed=True)`: a zero bias), no residual, no ReLU, and the gradient's own explicit operand scale."""
+    if not pack_t.transposed:
+        raise RuntimeError("conv2d_bwd_data: the pack must be built with transposed=True")
+    return conv2d(dy, pack_t, x_range=_req(dy_scale, "dy_scale"))
 
 
 def avgpool2_bwd(dout: torch.Tensor) -> torch.Tensor:
