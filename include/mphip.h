@@ -840,6 +840,54 @@ int mphip_conv2d_bwd_weight(const float *x, const float *x_range, const float *d
 int mphip_pack_conv2d_weight_bwd_data(const float *w_oihw, void *w_packed, int Co, int Ci, void *stream);
 int mphip_debug_conv2d_bwd_weight_plan(int N, int Ci, int Co, int H, int W, int out[4]);
 
+/* Between the convs of a VGG19 perceptual loss (added within ABI 30: exports only, no signature or layout above changed; a caller that
+ * may meet an older ABI-30 library probes for these entries, e.g. dlsym of mphip_maxpool2_supported; csrc/feature_loss.hip).  The
+ * reference's PerceptualLoss.compute_vgg19_loss (model.py:1981-2017) pushes the predicted and the target image through
+ * vgg19.features[0:30] and adds mean |p - t| after layers 1, 6, 11, 20, 29; the thirteen convs are mphip_conv2d_stem_fwd / mphip_conv2d_fwd
+ * and, backward, mphip_conv2d_fwd on the transposed packs; the entries below are everything else, forward and backward to the predicted
+ * image (the weights are frozen: no weight or bias gradient).  NCHW fp32.  No atomics, no memset nodes: a workgroup leaves its partial
+ * in its own slot with a plain store and a second small launch folds the slots in index order, so two calls give the same bits.  Rows
+ * are read with 16-byte accesses when W % 4 == 0 and the maps lie on 16-byte boundaries, element by element otherwise.  Every refusal
+ * comes before the first HIP call, in the order: null pointer, shape, 4-byte alignment, aliasing (MPHIP_EINVAL each), a missing or short
+ * workspace (MPHIP_EWORKSPACE), a workspace off a 16-byte boundary (MPHIP_EINVAL); messages name the entry without its mphip_ prefix.
+ *   maxpool2_fwd: y [NC,H/2,W/2] = nn.MaxPool2d(2, 2)(x [NC,H,W]), floor mode: an odd last row or column belongs to no window.  ATen's
+ *          rule: the window is scanned in (row, column) order from -inf and an element replaces the maximum when val > max or val is NaN,
+ *          so NaN wins (the window's last NaN, payload kept).  out_range (optional, MPHIP_RANGE_FLOATS floats): a derive-mode descriptor
+ *          of y with the exact max|y|.  NC >= 1, H, W >= 2, fewer than 2^31 elements; y must not alias x.
+ *   feature_l1: y holds 2N samples of M floats, predicted first, then target: loss_out[0] = coeff * sum_{n<N, i<M} |y[n][i] - y[N+n][i]|.
+ *          Difference and |.| in fp32; every term is widened and added in fp64, per thread, then per workgroup, in a fixed order; a
+ *          finish launch adds the workgroups' sums in index order, multiplies by coeff in fp64 and rounds once to fp32.  With T = N * M
+ *          terms: |result - exact| <= 2^-23 * exact up to the fp64 sum's 2^-53 * T.  An Inf gives Inf (or NaN from Inf - Inf), a NaN NaN.
+ *          loss_out is one float anywhere in device memory (an element of a vector of taps).  N, M >= 1, 2 * N * M < 2^31.
+ *          Workspace: mphip_feature_l1_workspace_bytes (0 for a refused shape), always required.
+ *   feature_grad_assemble: the gradient at the output of a conv whose post-ReLU map y [2N,C,H,W] (predicted, then target) was saved:
+ *              g[n,c,h,w] = y_pred > 0 ? upstream + tap : 0                                           g is [N,C,H,W]
+ *          upstream (`upstream` = 0 / 1 / 2): nothing; upstream_grad [N,C,H,W], the dx of the next conv; or upstream_grad [N,C,H/2,W/2], the
+ *          gradient of maxpool2_fwd(y_pred), routed to the element of its window that the rule above makes the maximum (the FIRST of equal
+ *          maxima in (row, column) order), 0 elsewhere and in a dropped odd row or column.  tap: absent (coeff == NULL), else
+ *          coeff[0] * sgn(y_pred - y_target) with sgn(0) = sgn(NaN) = 0, coeff one float of DEVICE memory (the loss's incoming gradient
+ *          times 1 / count never visits the host).  With both terms the one fp32 add is the only rounding.  A NaN y_pred masks to 0.
+ *          scale: the 4 floats mphip_grad_prep(g, NULL, scale, N, C, H * W, ...) would write, (s, 1/s, max|g|) bit for bit (a NaN does not
+ *          enter the maximum there either), and scale[3] = 0: the explicit-scale descriptor mphip_conv2d_fwd takes as x_range for the
+ *          backward-data conv.  N, C, H, W >= 1 (upstream 2: H, W >= 2), 2 * N * C * H * W < 2^31, upstream 0 needs a tap; g must not
+ *          alias y.  Workspace: mphip_feature_grad_assemble_workspace_bytes (0 for a refused shape), always required.
+ *   conv2d_stem_bwd_data: dx [N,3,H,W] of nn.Conv2d(3, Co, 3, padding=1) given dy [N,Co,H,W] and the plain OIHW weight [Co,3,3,3]:
+ *              dx[n,ci,h,w] = sum_{co,kh,kw} w[co,ci,kh,kw] * dy[n,co,h+1-kh,w+1-kw]                  dy is zero outside the map
+ *          Exact fp32 on the vector units, the order part of the contract like mphip_conv2d_stem_fwd's: acc = +0, then fmaf(w, dy, acc)
+ *          over co = 0 .. Co-1, kh = 0..2, kw = 0..2 in that nesting.  No pack, no range descriptor, no workspace.  Co % 16 == 0,
+ *          N, H, W >= 1, fewer than 2^31 elements in dy; dx must not alias dy.                                                          */
+int mphip_maxpool2_supported(int NC, int H, int W);
+int mphip_maxpool2_fwd(const float *x, float *y, float *out_range, int NC, int H, int W, void *stream);
+int mphip_feature_l1_supported(int N, int M);
+size_t mphip_feature_l1_workspace_bytes(int N, int M);
+int mphip_feature_l1(const float *y, int N, int M, double coeff, float *loss_out, void *workspace, size_t workspace_bytes, void *stream);
+int mphip_feature_grad_assemble_supported(int N, int C, int H, int W, int upstream);
+size_t mphip_feature_grad_assemble_workspace_bytes(int N, int C, int H, int W);
+int mphip_feature_grad_assemble(const float *y, const float *upstream_grad, int upstream, const float *coeff, float *g, float *scale, int N,
+                                int C, int H, int W, void *workspace, size_t workspace_bytes, void *stream);
+int mphip_conv2d_stem_bwd_data_supported(int N, int Co, int H, int W);
+int mphip_conv2d_stem_bwd_data(const float *dy, const float *w_oihw, float *dx, int N, int Co, int H, int W, void *stream);
+
 /* The reference's reduced-precision policy for the convs (train.py:145,188: the generator step runs under torch.cuda.amp.autocast(), its
  * conv3d calls take f16 operands with fp32 accumulation).  mphip_conv3d_set_half_products(1) makes the CALLING THREAD's subsequent precision-1
  * 3x3x3 launches that run in the F(2,3) domain (mphip_conv3d_kernel_variant == 5: G3d's levels 0-2, Eapp's 3-D tail, their bwd-data

@@ -195,6 +195,17 @@ SIGNATURES = {
     "mphip_conv2d_bwd_weight": (_i, [_p] * 5 + [_i] * 5 + [_p, _sz, _p]),
     "mphip_pack_conv2d_weight_bwd_data": (_i, [_p, _p, _i, _i, _p]),
     "mphip_debug_conv2d_bwd_weight_plan": (_i, [_i] * 5 + [ctypes.POINTER(ctypes.c_int)]),
+    # between the convs of a VGG19 perceptual loss (added within ABI 30, csrc/feature_loss.hip)
+    "mphip_maxpool2_supported": (_i, [_i] * 3),
+    "mphip_maxpool2_fwd": (_i, [_p] * 3 + [_i] * 3 + [_p]),
+    "mphip_feature_l1_supported": (_i, [_i] * 2),
+    "mphip_feature_l1_workspace_bytes": (_sz, [_i] * 2),
+    "mphip_feature_l1": (_i, [_p, _i, _i, ctypes.c_double, _p, _p, _sz, _p]),
+    "mphip_feature_grad_assemble_supported": (_i, [_i] * 5),
+    "mphip_feature_grad_assemble_workspace_bytes": (_sz, [_i] * 4),
+    "mphip_feature_grad_assemble": (_i, [_p, _p, _i, _p, _p, _p] + [_i] * 4 + [_p, _sz, _p]),
+    "mphip_conv2d_stem_bwd_data_supported": (_i, [_i] * 4),
+    "mphip_conv2d_stem_bwd_data": (_i, [_p] * 3 + [_i] * 4 + [_p]),
     "mphip_build_flags": (_i, []),
     "mphip_graph_memsets_to_kernels": (_i, [_p, ctypes.POINTER(ctypes.c_int)]),
     "mphip_graph_memset_nodes_left": (_i, [_p, ctypes.POINTER(ctypes.c_int)]),

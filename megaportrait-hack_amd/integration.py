@@ -127,3 +127,21 @@ def install(gbase: nn.Module, model_module: Optional[object] = None, eapp_tail: 
     if model_module is not None:
         done += [f"{getattr(model_module, '__name__', 'model')}.{n}" for n in patch_functions(model_module)]
     return done
+
+
+def install_vgg19_loss(perceptual) -> List[str]:
+    """Binds the VGG19 terms of the reference's `PerceptualLoss` (model.py:1928-2017: an object with `.vgg19` and `.vgg19_layers`) to
+    losses.VGG19FeatureLoss.from_sequential(perceptual.vgg19): `compute_vgg19_loss(predicted, target)` and
+    `compute_feature_matching_loss(predicted, target)` (the same sum with the target detached) become instance attributes that run the
+    loss, forward and gradient, on the HIP kernels.  The Sequential's modules and Parameters are shared and their requires_grad is left
+    alone: torchvision's weights come with requires_grad=True, and such weights take the module's plain-PyTorch path, so call
+    `perceptual.vgg19.requires_grad_(False)` (the reference's optimizers never hold them).  Returns the names it replaced.  `install`
+    itself does not call this."""
+    from .losses import VGG19FeatureLoss
+
+    loss = VGG19FeatureLoss.from_sequential(perceptual.vgg19, taps=tuple(perceptual.vgg19_layers))
+    # (kept off the Module's registry: the loss shares perceptual.vgg19, a second registration would double its state-dict keys)
+    perceptual.__dict__["_mphip_vgg19_loss"] = loss
+    perceptual.compute_vgg19_loss = lambda predicted, target: loss(predicted, target)
+    perceptual.compute_feature_matching_loss = lambda predicted, target: loss(predicted, target.detach())
+    return ["compute_vgg19_loss", "compute_feature_matching_loss"]

@@ -1791,6 +1791,104 @@ def conv2d_bwd_data(dy: torch.Tensor, pack_t: PackedConv2d, dy_scale: torch.Tens
     return conv2d(dy, pack_t, x_range=_req(dy_scale, "dy_scale"))
 
 
+# ------------------------------------------------------------------ between the convs of a perceptual loss (csrc/feature_loss.hip)
+def maxpool2(x: torch.Tensor, want_range: bool = False) -> torch.Tensor:
+    """nn.MaxPool2d(2, 2) of an NCHW fp32 map (mphip_maxpool2_fwd): floor mode, ATen's scan (the first of equal maxima, NaN wins).
+    want_range: y comes back tagged with the descriptor of its exact max|y|, so a conv2d that follows does not scan it."""
+    x = _req(x, "x")
+    if x.dim() != 4:
+        raise RuntimeError(f"maxpool2: expected an [N, C, H, W] map, got {tuple(x.shape)}")
+    n, c, h, w = x.shape
+    lib = _lib.load()
+    if not lib.mphip_maxpool2_supported(n * c, h, w):
+        raise RuntimeError(f"maxpool2: unsupported shape {tuple(x.shape)} (H, W >= 2, fewer than 2^31 elements; there is no fallback)")
+    y = torch.empty((n, c, h // 2, w // 2), dtype=torch.float32, device=x.device)
+    out_range = new_range(x.device) if want_range else None
+    _lib.check(lib.mphip_maxpool2_fwd(_ptr(x), _ptr(y), _ptr(out_range), n * c, h, w, _stream()), "mphip_maxpool2_fwd")
+    return tag_range(y, out_range)
+
+
+def _aligned16_buffer(nbytes: int, device) -> torch.Tensor:
+    """a workspace of at least nbytes that starts on a 16-byte boundary (the caching allocator's blocks do; a view is re-based if not)"""
+    ws = torch.empty((nbytes + 3) // 4 + 4, dtype=torch.float32, device=device)
+    return ws[(-ws.data_ptr() % 16) // 4:]
+
+
+def feature_l1(y: torch.Tensor, coeff: float, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """coeff * sum |y[:N] - y[N:]| of a map that holds 2N samples, predicted first (mphip_feature_l1): fp32 differences, fp64 sums in a
+    fixed order, one rounding.  out: a one-element fp32 CUDA tensor (e.g. `taps[i:i + 1]` of a vector of taps) that receives the value;
+    a new one otherwise.  No host sync."""
+    y = _req(y, "y")
+    if y.dim() < 1 or y.shape[0] < 2 or y.shape[0] % 2:
+        raise RuntimeError(f"feature_l1: expected 2N samples along dim 0, got {tuple(y.shape)}")
+    n = y.shape[0] // 2
+    m = y.numel() // y.shape[0]
+    lib = _lib.load()
+    if not lib.mphip_feature_l1_supported(n, m):
+        raise RuntimeError(f"feature_l1: unsupported shape {tuple(y.shape)} (fewer than 2^31 elements; there is no fallback)")
+    if out is None:
+        out = torch.empty(1, dtype=torch.float32, device=y.device)
+    elif out.numel() != 1 or out.dtype != torch.float32 or out.device != y.device:
+        raise RuntimeError("feature_l1: out must be one fp32 element on y's device")
+    ws_bytes = lib.mphip_feature_l1_workspace_bytes(n, m)
+    ws = _aligned16_buffer(ws_bytes, y.device)
+    _lib.check(lib.mphip_feature_l1(_ptr(y), n, m, float(coeff), _ptr(out), _ptr(ws), ws_bytes, _stream()), "mphip_feature_l1")
+    return out
+
+
+def feature_grad_assemble(y: torch.Tensor, upstream: Optional[torch.Tensor] = None, coeff: Union[None, float, torch.Tensor] = None):
+    """(g, scale) of mphip_feature_grad_assemble: g [N,C,H,W] = (upstream + coeff * sgn(y[:N] - y[N:])) * (y[:N] > 0) for a saved post-ReLU
+    map y [2N,C,H,W], and the 4-float operand scale ops.grad_prep(g) would return, in one pass.  upstream: None, a same-size gradient
+    [N,C,H,W], or a gradient [N,C,H//2,W//2] of the 2x2 max-pool of y[:N] (routed to the first maximum of each window).  coeff: None (no
+    tap), a float, or a one-element fp32 CUDA tensor (read on the device)."""
+    y = _req(y, "y")
+    if y.dim() != 4 or y.shape[0] < 2 or y.shape[0] % 2:
+        raise RuntimeError(f"feature_grad_assemble: expected a [2N, C, H, W] map, got {tuple(y.shape)}")
+    n, (c, h, w) = y.shape[0] // 2, y.shape[1:]
+    kind = 0
+    if upstream is not None:
+        upstream = _req(upstream, "upstream")
+        if tuple(upstream.shape) == (n, c, h, w):
+            kind = 1
+        elif tuple(upstream.shape) == (n, c, h // 2, w // 2):
+            kind = 2
+        else:
+            raise RuntimeError(f"feature_grad_assemble: upstream {tuple(upstream.shape)} is neither {(n, c, h, w)} nor its 2x2-pooled shape")
+    if coeff is not None:
+        if not isinstance(coeff, torch.Tensor):
+            coeff = torch.full((1,), float(coeff), dtype=torch.float32, device=y.device)
+        coeff = _req(coeff, "coeff")
+        if coeff.numel() != 1:
+            raise RuntimeError("feature_grad_assemble: coeff is one float")
+    elif kind == 0:
+        raise RuntimeError("feature_grad_assemble: neither an upstream gradient nor a tap")
+    lib = _lib.load()
+    if not lib.mphip_feature_grad_assemble_supported(n, c, h, w, kind):
+        raise RuntimeError(f"feature_grad_assemble: unsupported shape {tuple(y.shape)} (fewer than 2^31 elements; there is no fallback)")
+    g = torch.empty((n, c, h, w), dtype=torch.float32, device=y.device)
+    scale = torch.empty(4, dtype=torch.float32, device=y.device)
+    ws_bytes = lib.mphip_feature_grad_assemble_workspace_bytes(n, c, h, w)
+    ws = _aligned16_buffer(ws_bytes, y.device)
+    _lib.check(lib.mphip_feature_grad_assemble(_ptr(y), _ptr(upstream), kind, _ptr(coeff), _ptr(g), _ptr(scale), n, c, h, w, _ptr(ws),
+                                               ws_bytes, _stream()), "mphip_feature_grad_assemble")
+    return g, scale
+
+
+def conv2d_stem_bwd_data(dy: torch.Tensor, weight: torch.Tensor) -> torch.Tensor:
+    """dx [N,3,H,W] of y = conv2d(x, weight, padding=1) with a [Co,3,3,3] weight given dy [N,Co,H,W] (mphip_conv2d_stem_bwd_data): exact
+    fp32 in the fixed FMA order of include/mphip.h, so the gradient of an image is bitwise reproducible."""
+    dy, weight = _req(dy, "dy"), _req(weight.detach(), "conv2d_stem_bwd_data weight")
+    if weight.dim() != 4 or tuple(weight.shape[1:]) != (3, 3, 3) or dy.dim() != 4 or dy.shape[1] != weight.shape[0]:
+        raise RuntimeError(f"conv2d_stem_bwd_data: expected dy [N, Co, H, W] and a [Co, 3, 3, 3] weight, got {tuple(dy.shape)} and {tuple(weight.shape)}")
+    n, co, h, w = dy.shape
+    lib = _lib.load()
+    if not lib.mphip_conv2d_stem_bwd_data_supported(n, co, h, w):
+        raise RuntimeError(f"conv2d_stem_bwd_data: unsupported shape N={n} Co={co} H={h} W={w} (there is no fallback)")
+    dx = torch.empty((n, 3, h, w), dtype=torch.float32, device=dy.device)
+    _lib.check(lib.mphip_conv2d_stem_bwd_data(_ptr(dy), _ptr(weight), _ptr(dx), n, co, h, w, _stream()), "mphip_conv2d_stem_bwd_data")
+    return dx
+
+
 def avgpool2_bwd(dout: torch.Tensor) -> torch.Tensor:
     dout = _req(dout, "dout")
     n, c, d, h, w = dout.shape
