@@ -117,6 +117,20 @@ def lo_plane_operand(shape, frac_bits: int, seed: int) -> torch.Tensor:
     return v
 
 
+def odd_lo_plane_operand(shape, frac_bits: int, seed: int) -> torch.Tensor:
+    """lo_plane_operand with |a| in [2, 4] and b odd: v * 2^frac_bits is an odd integer of at least frac_bits + 1 bits, so EVERY element's lo
+    half is odd and non-zero.  For reductions of a few terms (a 1x1 map), where lo_plane_operand's lo halves, zero on half of the elements,
+    would cancel or vanish too often: an odd number of odd lo terms times +-1 never sums to 0."""
+    g = _exact_gen(seed)
+    a = torch.randint(2, 5, tuple(shape), generator=g).double() * (torch.randint(0, 2, tuple(shape), generator=g).double() * 2 - 1)
+    m = 2 ** (frac_bits - 2)
+    b = torch.randint(-m, m, tuple(shape), generator=g).double() * 2 + 1
+    a.view(-1)[0] = 4.0
+    v = (a + b * 2.0 ** -frac_bits).float()
+    assert torch.equal(v.double(), a + b * 2.0 ** -frac_bits) and 4.0 <= v.abs().max().item() < 4.5
+    return v
+
+
 def lo_plane_pair(kind: str, x_shape, w_shape, x_top: int, seed: int):
     """(x, w) of one of the two data kinds that make the lo planes of the split-f16 2-D convs exact:
       "xlo": x = lo_plane_operand(11 fractional bits), w integers in [-x_top, x_top]  -> Whi*Xlo carries bits, Wlo = 0;
@@ -129,7 +143,67 @@ def lo_plane_pair(kind: str, x_shape, w_shape, x_top: int, seed: int):
     return exact_ints(x_shape, x_top, seed), lo_plane_operand(w_shape, 12, seed + 1)
 
 
-def conv3d_wino_f16_contract(x, w, b=None, padding=1):
+def sparse_ints(shape, density: float, seed: int, top: int = 1, chunk: int = 16) -> torch.Tensor:
+    """Ternary values {-top, 0, top}, non-zero with probability `density`, fp32: the INTEGER operand of a lo-plane case whose reduction is
+    too long for a dense one (the sum of |products| would pass 2^24 units).  Element 0 is `top` (the operand scale is fixed whatever the
+    draw), and every `chunk` channels of dim 1 hold a non-zero (every K chunk of a kernel multiplies something)."""
+    assert 0.0 < density <= 1.0 and len(shape) >= 2
+    g = _exact_gen(seed)
+    keep = torch.rand(tuple(shape), generator=g) < density
+    sign = torch.randint(0, 2, tuple(shape), generator=g).float() * 2 - 1
+    t = keep.float() * sign * float(top)
+    t.view(-1)[0] = float(top)
+    for c0 in range(0, shape[1], chunk):
+        assert bool(t[:, c0:c0 + chunk].any()), (tuple(shape), density, c0)
+    return t
+
+
+def wino_f16x3_operands(x, w, x_scale: float = None):
+    """(th, tl, uh, ul, t, u, sx * sw): the transformed operands of the F(2,3) conv kernels at their scales, and their f16 halves as the
+    three-product kernels form them.  t[i] = (Bt d)_i on the scaled fp32 input (one fp32 operation each), u[i] = (G g)_i * sw in double
+    rounded to float; hi = rne_f16(v), lo = rne_f16(v - hi) AFTER the transform (split_f16_at_scale's rule).  All SCALED, float64, lists of
+    four (t: [N, Ci, D, H, W / 2]; u: [Co, Ci, 3, 3])."""
+    assert w.shape[2:] == (3, 3, 3) and x.shape[-1] % 2 == 0
+    x, w = x.detach().float(), w.detach().float()
+    W = x.shape[-1]
+    sx = pow2_operand_scale(x.abs().max().item(), 14) if x_scale is None else float(x_scale)
+    sw = pow2_operand_scale(w.abs().max().item(), 15)
+    xp = F.pad(x * sx, (1, 1))                                        # W halo; D / H are padded by the conv
+    d = [xp[..., i:i + W:2] for i in range(4)]                         # d_i of output pair j = x[2j - 1 + i]
+    t = [d[0] - d[2], d[1] + d[2], d[2] - d[1], d[1] - d[3]]          # fp32, one rounding each
+    g = w.double()
+    u = [g[..., 0], 0.5 * (g[..., 0] + g[..., 1] + g[..., 2]), 0.5 * (g[..., 0] - g[..., 1] + g[..., 2]), g[..., 2]]
+    u = [(up * sw).float() for up in u]
+    th, uh = [v.half() for v in t], [v.half() for v in u]
+    tl = [(v - h.float()).half() for v, h in zip(t, th)]
+    ul = [(v - h.float()).half() for v, h in zip(u, uh)]
+    f64 = lambda vs: [v.double() for v in vs]                          # noqa: E731
+    return f64(th), f64(tl), f64(uh), f64(ul), f64(t), f64(u), sx * sw
+
+
+def wino_position_sums(t, u):
+    """m[i] = sum over (ci, kd, kh) of t[i] * u[i] per Winograd position i, float64 (exact on the lo-plane data)"""
+    return [F.conv3d(tp, up.unsqueeze(-1), None, padding=(1, 1, 0)) for tp, up in zip(t, u)]
+
+
+def wino_output(m, unit: float):
+    """the output transform At = [[1,1,1,0],[0,1,-1,-1]] and the unscale, both exact"""
+    return torch.stack([m[0] + m[1] + m[2], m[1] - m[2] - m[3]], dim=-1).flatten(-2) / unit
+
+
+def bwd_weight_f16x3_contract(x, dy, grad, products: int = 3):
+    """The split-f16 bwd-weight kernels' contract: x and dy each split at the activations' scale (top 14), the products
+    xhi*dyhi + xhi*dylo + xlo*dyhi (products = 1: xhi*dyhi alone) summed exactly in float64.  `grad(x64, dy64)` is the bilinear map
+    (x, dy) -> dW of the conv (2-D or 3-D, its kernel size and padding)."""
+    assert products in (1, 3)
+    xh, xl, _ = split_f16_at_scale(x, 14)
+    dh, dl, _ = split_f16_at_scale(dy, 14)
+    if products == 1:
+        return grad(xh, dh)
+    return grad(xh, dh) + grad(xh, dl) + grad(xl, dh)
+
+
+def conv3d_wino_f16_contract(x, w, b=None, padding=1, products: int = 1, x_scale: float = None):
     """The arithmetic contract of the F(2,3) conv kernels under the autocast policy (mphip_conv3d_set_half_products), stated without any
     implementation's accumulation order: k = 3, padding = 1, W even.  Along W the 3-tap filter runs in the Winograd F(2,3) domain; what
     is rounded to float16 is the TRANSFORMED operand pair, exactly as the kernels do it —
@@ -138,19 +212,15 @@ def conv3d_wino_f16_contract(x, w, b=None, padding=1):
       filter (csrc/conv3d_f16x3.hip f16x3_pack_body): u = G g in double (g0, (g0+g1+g2)/2, (g0-g1+g2)/2, g2), scaled, rounded
              double -> float -> f16;
     the products are accumulated exactly (float64), the output transform At = [[1,1,1,0],[0,1,-1,-1]] and the unscale are exact, then the
-    bias.  A kernel that follows this contract differs from it only by its fp32 accumulation (~1e-6 of max|y|)."""
-    assert padding == 1 and w.shape[2:] == (3, 3, 3) and x.shape[-1] % 2 == 0
-    x, w = x.detach().float(), w.detach().float()
-    W = x.shape[-1]
-    sx = pow2_operand_scale(x.abs().max().item(), 14)
-    sw = pow2_operand_scale(w.abs().max().item(), 15)
-    xp = F.pad(x * sx, (1, 1))                                        # W halo; D / H are padded by the conv below
-    d = [xp[..., i:i + W:2] for i in range(4)]                         # d_i of output pair j = x[2j - 1 + i]
-    t = [d[0] - d[2], d[1] + d[2], d[2] - d[1], d[1] - d[3]]          # fp32, one rounding each
-    g = w.double()
-    u = [g[..., 0], 0.5 * (g[..., 0] + g[..., 1] + g[..., 2]), 0.5 * (g[..., 0] - g[..., 1] + g[..., 2]), g[..., 2]]
-    m = [F.conv3d(tp.half().double(), (up * sw).float().half().double().unsqueeze(-1), None, padding=(1, 1, 0)) for tp, up in zip(t, u)]
-    y = torch.stack([m[0] + m[1] + m[2], m[1] - m[2] - m[3]], dim=-1).flatten(-2) / (sx * sw)
+    bias.  A kernel that follows this contract differs from it only by its fp32 accumulation (~1e-6 of max|y|).
+    products = 3 is the full-precision launch: t and u are split into hi and lo AFTER the transform (wino_f16x3_operands) and
+    Uhi*Thi + Ulo*Thi + Uhi*Tlo is accumulated; `x_scale` fixes the input scale where a descriptor bounds a fused affine's map."""
+    assert padding == 1 and products in (1, 3)
+    th, tl, uh, ul, _, _, unit = wino_f16x3_operands(x, w, x_scale)
+    m = wino_position_sums(th, uh)
+    if products == 3:
+        m = [a + c + e for a, c, e in zip(m, wino_position_sums(th, ul), wino_position_sums(tl, uh))]
+    y = wino_output(m, unit)
     return y if b is None else y + b.detach().double().view(1, -1, 1, 1, 1)
 
 
